@@ -15,6 +15,8 @@ without the halo exchange, with its parity against the oracle's assembled block)
 steps at 128^3), and "value_unplaced": the same K steps on plainly allocated vectors (see "placement" in include/fluca_hip.h).
 For N > 1 the halo transport is RCCL; if RCCL cannot be initialised the run FAILS (a host-staged curve would be worthless) --
 the host-staged rehearsal has to be asked for with --transport host.
+--dump-outputs DIR writes what the timed solve returned (x, sampled at fixed cells on large grids, and the residual norms) as .npy files: the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -694,6 +696,27 @@ def other_configs(stream, parity=True):
     return cfg
 
 
+DUMP_CELLS = 2 ** 21           # cells of x written by --dump-outputs over the whole job: 16 MB of values + 16 MB of indices
+DUMP_SEED = 20260313
+
+
+def dump_outputs(outdir, x, info, rank, world):
+    """--dump-outputs: what the timed solve handed its caller, outside the timed region -- x after the last timed iteration and the residual norms
+    of the solve.  x is written whole when the rank holds at most its share of DUMP_CELLS cells, otherwise at a fixed set of cells drawn with
+    DUMP_SEED (the same set in every run with the same arguments) and the cell indices beside it, as float64 (exact below 2^53).  Files of a
+    rank other than the only one carry a _rank<r> suffix."""
+    os.makedirs(outdir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    ncell, keep = x.numel(), DUMP_CELLS // world
+    if ncell <= keep:
+        np.save(os.path.join(outdir, f"x{sfx}.npy"), x.cpu().numpy().astype(np.float64))
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED + rank).choice(ncell, keep, replace=False))
+        np.save(os.path.join(outdir, f"x_sample{sfx}.npy"), x[torch.as_tensor(idx, device=x.device)].cpu().numpy().astype(np.float64))
+        np.save(os.path.join(outdir, f"x_sample_index{sfx}.npy"), idx.astype(np.float64))
+    np.save(os.path.join(outdir, f"residual_norms{sfx}.npy"), np.array([info["rnorm0"], info["rnorm"]], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -717,7 +740,11 @@ def main():
     ap.add_argument("--transport", choices=["rccl", "host"], default="rccl",
                     help="halo transport for N > 1: RCCL Send/Recv (production) or the host-staged gloo callbacks "
                          "(rehearsal on a box with fewer GPUs than ranks; never used for a reported number)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed solve returned as DIR/<name>.npy (float64, at most 64 MB in all): "
+                         "the solution x (a fixed seeded sample of it on large grids, with its cell indices) and the residual norms")
     args = ap.parse_args()
+    assert args.steps >= 1, "--steps: at least one timed step"
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -806,6 +833,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t[0])
     assert info["iters"] == args.steps, info
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, x, info, rank, world)
     per_rank, wire = None, None
     if world > 1:
         per_rank = [None] * world

@@ -46,6 +46,26 @@ def test_single_gpu_line_has_the_contract_keys():
     assert "workload" in d["config"] and "model" not in d["config"]
 
 
+def test_dumped_outputs_repeat_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: x after the last timed step and the residual norms, float64; two runs with the same arguments start from the same inputs
+    and write the same answer.  --steps is the number of timed iterations (an odd one: the kernel pair updates x every second iteration)."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        d = tmp_path / str(k)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cells", "64", "--steps", "9", "--warmup", "2", "--skip-cpu", "--skip-configs",
+                              "--skip-extras", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stdout + out.stderr
+        line = _line(out)
+        assert line["steps"] == 9 and line["ms_per_step"] > 0
+        runs.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = runs
+    assert set(a) == {"x", "residual_norms"} and a["x"].dtype == np.float64 and a["x"].shape == (64 ** 3,)
+    assert np.all(np.isfinite(a["x"])) and np.abs(a["x"]).max() > 0 and np.all(np.isfinite(a["residual_norms"])) and a["residual_norms"][0] > 0
+    for k in a:
+        assert np.allclose(a[k], b[k], rtol=1e-12, atol=1e-12 * np.abs(a[k]).max()), k
+
+
 def test_two_ranks_through_the_driver_launch_line():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))

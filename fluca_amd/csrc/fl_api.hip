@@ -1789,6 +1789,54 @@ extern "C" int fldbg_bench(fl_poisson *h, int kernel, int ry, int pf, int nchunk
   return FL_SUCCESS;
 }
 
+// ------------------------------------------------------------------------------------------------ launch plans (tests/launch_regimes.py)
+// Not part of the public C-ABI (not declared in fluca_hip.h): the launch shapes the hot kernels take on an nx x ny x nz block.  Host arithmetic
+// only -- no handle, no HIP call.  Writes FLDBG_NPLAN ints to out (in this order) and returns their number; out == nullptr: the number only.
+//   k_cg_A / k_cg_Bq (plan_cg_A):       0 ry, 1 nw, 2 tiles_x, 3 tiles_y, 4 nchunk, 5 zc, 6 nblocks
+//   k_cheb2 (fl_cheb2_plan):            7 nw, 8 tiles_x, 9 tiles, 10 nchunk, 11 zc, 12 nblocks
+//   k_apply_pc, k_bcgs_pw (tile_plan):  13 ry, 14 tiles_x, 15 nchunk, 16 zc, 17 nblocks
+//   k_project_six:                      18 nxcd, 19 nseg, 20 nbx (blocks per XCD slab), 21 items (row segments per slab)
+//   k_schur_var (schur_var_plan):       22 per_xcd, 23 nseg, 24 band, 25 fixed_seg, 26 items
+//   k_mom2 / k_mom3:                    27 t2x, 28 t2chunk, 29 t2zc, 30 t2blocks
+// The CG, Chebyshev, tile and Schur plans are the functions the launchers call.  The project-six launch (launch_project_six, fl_kernels.hip) and
+// the t2 tiling (fl_momentum_create, fl_momentum.hip) are computed inline there and restated below with their default experiment switches:
+// those two files are fingerprinted by the committed counter passes (fluca_amd/provenance.py), so a change of either must be made in both places.
+constexpr int FLDBG_NPLAN = 31;
+extern "C" int fldbg_launch_plans(int nx, int ny, int nz, int *out, int nout)
+{
+  if (nx < 1 || ny < 1 || nz < 1) return FL_ERR_ARG_OUTOFRANGE;
+  if (!out) return FLDBG_NPLAN;
+  if (nout < FLDBG_NPLAN) return FL_ERR_ARG_SIZ;
+  GridP g{};
+  g.nx = nx;
+  g.ny = ny;
+  g.nz = nz;
+  const PlanA        a  = plan_cg_A(g, 0, 0);
+  const Cheb2Plan    c  = fl_cheb2_plan(g);
+  const TP           t  = tile_plan(g);
+  const SchurVarPlan sv = schur_var_plan(g);
+  // launch_project_six: 1024 blocks of four waves per XCD slab (8 slabs), a multiple of the row segments, no more than the rows of a slab need
+  const int     nseg6 = (nx + 127) / 128, nxcd = ny < 8 ? 1 : 8;
+  const int64_t items6 = (int64_t)nseg6 * ((ny + nxcd - 1) / nxcd) * nz;
+  int64_t       nbx = std::max<int64_t>(1, std::min<int64_t>((items6 + 3) / 4, (int64_t)1024 * (8 / nxcd)));
+  nbx = (nbx + nseg6 - 1) / nseg6 * nseg6;
+  // fl_momentum_create: 128 x 8 tiles of k_mom2 / k_mom3, about 1024 blocks, z chunks of at least 8 planes
+  const int t2x = (nx + 127) / 128, tiles2 = t2x * ((ny + 7) / 8);
+  int       nc2 = std::max(1, (1024 + tiles2 / 2) / tiles2);
+  nc2 = std::max(1, std::min(std::min(nc2, std::max(1, nz / 8)), nz));
+  if (tiles2 * nc2 > MAX_PARTIAL_BLOCKS) nc2 = std::max(1, MAX_PARTIAL_BLOCKS / tiles2);
+  const int t2zc = (nz + nc2 - 1) / nc2, t2chunk = (nz + t2zc - 1) / t2zc;
+  if (items6 > INT32_MAX || nbx > INT32_MAX || sv.items > INT32_MAX) return FL_ERR_ARG_OUTOFRANGE;
+  const int v[FLDBG_NPLAN] = {a.ry, a.nw, a.tiles_x, a.tiles_y, a.nchunk, a.zc, a.nblocks,
+                              c.nw, c.tiles_x, c.tiles, c.nchunk, c.zc, c.nblocks,
+                              t.ry, t.tiles_x, t.nchunk, t.zc, t.nblocks,
+                              nxcd, nseg6, (int)nbx, (int)items6,
+                              sv.per_xcd, sv.nseg, sv.band, sv.fixed_seg, (int)sv.items,
+                              t2x, t2chunk, t2zc, tiles2 * t2chunk};
+  std::memcpy(out, v, sizeof(v));
+  return FLDBG_NPLAN;
+}
+
 #ifdef FL_KBENCH_VARIANTS  // experiments behind the placement notes of DESIGN.md: not in the product
 // Experiment behind fl_poisson_tune_placement (tools/experiments/pool_probe.py): K vectors allocated once, M random
 // assignments of five of them to the roles (r, p0, p1, q, x) of k_cg_A, probe time of each.

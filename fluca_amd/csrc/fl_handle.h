@@ -467,6 +467,17 @@ struct SchurVarT {
 };
 }  // namespace fl
 int       fl_schur_var_apply_fused(fl_poisson *h, const fl::SchurVarT &t, const double *ainv, const double *p_pad, double *y);
+// the launch of k_schur_var: 8 * per_xcd blocks of four waves; fixed_seg: every wave keeps one x segment of 64 cells for all its rows
+struct SchurVarPlan {
+  int     per_xcd, nseg, band, fixed_seg;
+  int64_t items;  // row segments in all
+};
+SchurVarPlan schur_var_plan(const fl::GridP &g);
+// fl_ksp.hip: the tiling of k_apply_pc, k_bcgs_pw and k_cheb (four waves, 128 x 4 ry cells)
+struct TP {
+  int ry, nchunk, zc, tiles_x, nblocks;
+};
+TP tile_plan(const fl::GridP &g);
 void      fl_launch_cheb2_from_zero(fl_poisson *h, const Cheb2Plan &p, bool jac, double *X0, double *X1, const double *B, double *D0, double *D1, const double *subq, const double *suba_dev, double *Bw);
 // fl_mg.hip
 int  fl_solve_cg_mg(fl_poisson *h, const double *b, double *x, const fl_ksp_opts *o, fl_ksp_stats *st);

@@ -954,11 +954,6 @@ using namespace fl;
 
 // ------------------------------------------------------------------------------------------------ drivers
 
-namespace {
-
-struct TP {
-  int ry, nchunk, zc, tiles_x, nblocks;
-};
 TP tile_plan(const GridP &g)
 {
   TP t;
@@ -972,6 +967,8 @@ TP tile_plan(const GridP &g)
   t.nblocks = tiles * t.nchunk;
   return t;
 }
+
+namespace {
 
 template <int RY, bool JAC>
 void apply_pc_t(fl_poisson *h, const TP &tp, const double *x, double *y, const double *o, const KspScal *s, double *partial, int unpadded_y)

@@ -185,6 +185,21 @@ using namespace fl;
 #ifndef FL_SV_BLOCKS_PER_XCD
 #define FL_SV_BLOCKS_PER_XCD 128
 #endif
+SchurVarPlan schur_var_plan(const GridP &g)
+{
+  SchurVarPlan pl;
+  pl.nseg  = (g.nx + 63) / 64;
+  pl.band  = (g.ny + 7) / 8;
+  pl.items = (int64_t)pl.nseg * g.ny * g.nz;
+  // blocks per XCD: every block must be RESIDENT (four per CU, 32 CUs) -- the blocks of an XCD walk their band in step, and one that starts late walks
+  // it again alone, when the planes its neighbours brought in have left the L2 -- and the rows they cover per loop trip should divide the band (64 rows
+  // at 512^3), or the waves straddle two planes: 256 blocks 67.7 B/cell fetched, 96 (48 rows per trip) 84.1, 128 63.5, 64 43.7, 32 36.1 (32 compulsory;
+  // fewer blocks are slower all the same: profiles/r05_schur_var.txt)
+  pl.per_xcd   = (int)std::max<int64_t>(1, std::min<int64_t>((pl.items / 8 + 3) / 4, FL_SV_BLOCKS_PER_XCD));
+  pl.fixed_seg = ((int64_t)pl.per_xcd * 4) % pl.nseg == 0 ? 1 : 0;  // k_schur_var's own test, with its four waves per block
+  return pl;
+}
+
 int fl_schur_var_apply_fused(fl_poisson *h, const SchurVarT &t, const double *ainv, const double *p_pad, double *y)
 {
   if (h->multi) return FL_ERR_SUP;
@@ -211,13 +226,7 @@ int fl_schur_var_apply_fused(fl_poisson *h, const SchurVarT &t, const double *ai
   }
   int per = 0;
   for (int d = 0; d < 3; ++d) per |= h->wrap_local[d] ? (1 << d) : 0;
-  const int64_t items = (int64_t)((g.nx + 63) / 64) * g.ny * g.nz;
-  // blocks per XCD: every block must be RESIDENT (four per CU, 32 CUs) -- the blocks of an XCD walk their band in step, and one that starts late walks
-  // it again alone, when the planes its neighbours brought in have left the L2 -- and the rows they cover per loop trip should divide the band (64 rows
-  // at 512^3), or the waves straddle two planes: 256 blocks 67.7 B/cell fetched, 96 (48 rows per trip) 84.1, 128 63.5, 64 43.7, 32 36.1 (32 compulsory;
-  // fewer blocks are slower all the same: profiles/r05_schur_var.txt)
-  const int     per_xcd = (int)std::max<int64_t>(1, std::min<int64_t>((items / 8 + 3) / 4, FL_SV_BLOCKS_PER_XCD));
-  hipLaunchKernelGGL(k_schur_var, dim3(8 * per_xcd), dim3(256), 0, h->stream, sg, per, p_pad, ainv, y);
+  hipLaunchKernelGGL(k_schur_var, dim3(8 * schur_var_plan(g).per_xcd), dim3(256), 0, h->stream, sg, per, p_pad, ainv, y);
   FL_HIP(hipGetLastError());
   return 0;
 }

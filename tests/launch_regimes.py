@@ -1,0 +1,103 @@
+"""The launch shapes of the hot kernels, named: which plan each kernel takes on a grid (fldbg_launch_plans in fl_api.hip, host arithmetic of
+the launchers) and the grids of the -m gpu regime tests that reach each one.
+
+The kernels pick their tiling, z chunks and grid stride from the grid size, and the toy grids of the parity suite all land in the small plans.
+REGIMES names a grid per plan branch that the product runs at 256^3 - 512^3, made ragged on purpose (partial tiles, a short last z chunk, a
+grid stride that wraps), with the fields of the plans it must get.  tests/test_launch_regimes.py checks the table against the library on the
+CPU; tests/test_gpu_launch_regimes.py checks every kernel on these grids against the oracle."""
+import ctypes as C
+
+from oracle import fluca_oracle as fo
+
+V, O, PER, SYM = fo.BC_VELOCITY, fo.BC_PRESSURE_OUTLET, fo.BC_PERIODIC, fo.BC_SYMMETRY
+CAVITY = [V, V, V, V, SYM, V]            # null space
+CHANNEL = [V, O, V, V, PER, PER]         # outlet; the periodic z seam crosses the z chunks
+XPER = [PER, PER, V, V, PER, PER]        # the periodic x seam joins the partial last tile to tile 0
+
+# fldbg_launch_plans' output, in order: <kernel>.<field>
+FIELDS = ["cg.ry", "cg.nw", "cg.tiles_x", "cg.tiles_y", "cg.nchunk", "cg.zc", "cg.nblocks",
+          "cheb2.nw", "cheb2.tiles_x", "cheb2.tiles", "cheb2.nchunk", "cheb2.zc", "cheb2.nblocks",
+          "tile.ry", "tile.tiles_x", "tile.nchunk", "tile.zc", "tile.nblocks",
+          "six.nxcd", "six.nseg", "six.nbx", "six.items",
+          "schur.per_xcd", "schur.nseg", "schur.band", "schur.fixed_seg", "schur.items",
+          "mom.t2x", "mom.t2chunk", "mom.t2zc", "mom.t2blocks"]
+
+
+def cg_regime(p):
+    """the branch of plan_cg_A a plan comes from, read off its shape: one row per wave (small_ry1), 4-wave tiles (small), 8-wave tiles that
+    alone nearly fill the chip (standard: >= 128 of them), or fewer 8-wave tiles in several z chunks (mid: >= 2^24 cells)"""
+    if p["cg.ry"] == 1:
+        return "small_ry1"
+    if p["cg.nw"] == 4:
+        return "small"
+    return "standard" if p["cg.tiles_x"] * p["cg.tiles_y"] >= 128 else "mid"
+
+
+def cheb2_clamped(p):
+    """fl_cheb2_plan's "never a second round of blocks" fired: the nearest chunk count to one wave of 256 blocks would have made more"""
+    t = p["cheb2.tiles"]
+    return int(t <= 256 and t * max(1, (256 + t // 2) // t) > 256)
+
+
+def launch_plans(n):
+    """{<kernel>.<field>: value} of the plans on an n[0] x n[1] x n[2] block; host arithmetic only (no GPU, no handle)"""
+    from fluca_amd import capi
+    f = capi.lib.fldbg_launch_plans
+    f.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]
+    f.restype = C.c_int
+    m = f(*n, None, 0)
+    assert m == len(FIELDS), (m, len(FIELDS))
+    out = (C.c_int * m)()
+    assert f(*n, out, m) == m
+    d = dict(zip(FIELDS, out))
+    d["cg.regime"] = cg_regime(d)
+    d["cheb2.clamp"] = cheb2_clamped(d)
+    return d
+
+
+def six_trips(p):
+    """grid-stride trips of the busiest wave of k_project_six (four waves per block)"""
+    return -(-p["six.items"] // (4 * p["six.nbx"]))
+
+
+class Regime:
+    def __init__(self, name, n, bcs, expect, reaches):
+        self.name, self.n, self.bcs, self.expect, self.reaches = name, tuple(n), bcs, expect, reaches
+
+    def __repr__(self):
+        return f"{self.name} {self.n[0]}x{self.n[1]}x{self.n[2]}"
+
+
+REGIMES = [
+    Regime("cg_standard_ragged", (300, 680, 21), [CAVITY, XPER],
+           {"cg.regime": "standard", "cg.ry": 2, "cg.nw": 8, "cg.tiles_x": 3, "cg.tiles_y": 43, "cg.nchunk": 2, "cg.zc": 11, "cg.nblocks": 258,
+            "cheb2.nw": 8, "cheb2.tiles": 129, "cheb2.nchunk": 1, "cheb2.clamp": 1,
+            "six.nxcd": 8, "six.nbx": 1026, "six.items": 5355,
+            "schur.per_xcd": 128, "schur.fixed_seg": 0},
+           "tiles16 = 129 in 8-wave tiles (x: 2 full tiles + 44 columns, y: 42.5 tiles); z chunks of 11 + 10; cheb2 clamp; "
+           "project-six 1.3 trips; schur 128 blocks per XCD, general segments"),
+    Regime("cg_mid_ragged", (300, 200, 280), [CHANNEL, XPER],
+           {"cg.regime": "mid", "cg.ry": 2, "cg.nw": 8, "cg.tiles_x": 3, "cg.tiles_y": 13, "cg.nchunk": 6, "cg.zc": 47, "cg.nblocks": 234,
+            "cheb2.nw": 8, "cheb2.tiles": 39, "cheb2.nchunk": 6, "cheb2.zc": 47, "cheb2.nblocks": 234, "cheb2.clamp": 1,
+            "six.nxcd": 8, "six.nbx": 1026, "six.items": 21000},
+           "2^24 cells and more with 39 tiles of 128 x 16: 6 z chunks of 47, the last 45; cheb2 clamp with 6 chunks; project-six 5.1 trips"),
+    Regime("schur_fixed_seg", (200, 37, 40), [CAVITY],
+           {"cg.regime": "small_ry1", "schur.per_xcd": 128, "schur.nseg": 4, "schur.fixed_seg": 1, "schur.band": 5},
+           "schur: 128 blocks per XCD, every wave keeps one x segment (the last one 8 cells wide), y bands of 5 with a last band of 2"),
+    Regime("schur_general", (300, 37, 40), [XPER],
+           {"cg.regime": "small", "schur.per_xcd": 128, "schur.nseg": 5, "schur.fixed_seg": 0, "schur.band": 5},
+           "schur: 128 blocks per XCD, a wave's x segment changes from row to row"),
+]
+BY_NAME = {r.name: r for r in REGIMES}
+
+# the shapes the product runs (512^3 bench, config 5's 512 x 512 x 256 blocks, the multigrid fine levels of 384^3 and 256^3): which plans they take
+PRODUCTION = {
+    (512, 512, 512): {"cg.regime": "standard", "cg.nblocks": 256, "cg.nchunk": 2, "cheb2.nchunk": 2, "cheb2.clamp": 0, "six.nbx": 1024,
+                      "six.items": 131072, "schur.per_xcd": 128, "schur.fixed_seg": 1, "mom.t2chunk": 4},
+    (512, 512, 256): {"cg.regime": "standard", "cg.nblocks": 256, "cg.nchunk": 2, "cheb2.nchunk": 2, "cheb2.clamp": 0, "six.nbx": 1024,
+                      "six.items": 65536, "schur.per_xcd": 128, "schur.fixed_seg": 1, "mom.t2chunk": 4},
+    (384, 384, 384): {"cg.regime": "mid", "cg.nblocks": 216, "cg.nchunk": 3, "cheb2.nchunk": 3, "cheb2.clamp": 1, "six.nbx": 1026,
+                      "six.items": 55296, "schur.per_xcd": 128, "schur.fixed_seg": 0, "mom.t2chunk": 7},
+    (256, 256, 256): {"cg.regime": "mid", "cg.nblocks": 256, "cg.nchunk": 8, "cheb2.nchunk": 8, "cheb2.clamp": 0, "six.nbx": 1024,
+                      "six.items": 16384, "schur.per_xcd": 128, "schur.fixed_seg": 1, "mom.t2chunk": 16},
+}

@@ -543,24 +543,27 @@ int place_vectors(fl_poisson *h)
     KspScal S2[2];
     std::memset(S2, 0, sizeof(S2));
     for (int a = 0; a < 2; ++a) {
-      S2[a].beta = 0.5; S2[a].alpha = 1e-3; S2[a].alpha_old = 1e-3; S2[a].zshift = 1e-4; S2[a].ncell_global = (double)h->ncell; S2[a].maxit = 1 << 30; S2[a].cur = a;
+      S2[a].beta = 0.5; S2[a].alpha = 1e-3; S2[a].zshift = 1e-4; S2[a].ncell_global = (double)h->ncell; S2[a].maxit = 1 << 30; S2[a].cur = a;
+      for (double &al : S2[a].aring) al = 1e-3;
     }
     FL_HIP(hipMemcpy(sc.p, S2, sizeof(S2), hipMemcpyHostToDevice));
   }
   const int verbose = knob(K_placement_verbose);
-  // probe = the pair the solver runs: k_cg_A (r, p -> p') and the odd-iteration k_cg_Bq (p', p_old, r, x -> r, x: every window vector but q)
+  // probe = the pair the solver runs: k_cg_A (r, p -> p') and the x-flushing k_cg_Bq of a two-slot ring (p', p_old, r, x -> r, x: every
+  // window vector but q).  The further slots of a deeper ring (cg_xdepth > 2) are not in the window: plain allocations.
   auto probe = [&](void *arena, size_t b, double *ms_out) -> int {
-    auto vec = [&](int k) { return (double *)((char *)arena + b + (size_t)k * vecb); };
+    auto          vec = [&](int k) { return (double *)((char *)arena + b + (size_t)k * vecb); };
+    const DirRing P   = dir_ring2(vec(1), vec(2));
     auto run = [&](int reps) {
       for (int r = 0; r < reps; ++r)
         for (int par = 0; par < 2; ++par) {
-          launch_cg_A(s, h->g, true, plan, vec(0), vec(1), vec(2), vec(3), vec(4), sc.p + par, h->partial, nullptr, nullptr, 0);
-          launch_cg_Bq(s, h->g, true, plan, 2, vec(1), vec(2), vec(0), vec(4), sc.p + par, h->partial, h->partial_stride, nullptr, nullptr, 0);
+          launch_cg_A(s, h->g, true, plan, vec(0), P, vec(3), vec(4), sc.p + par, h->partial, nullptr, nullptr, 0);
+          launch_cg_Bq(s, h->g, true, plan, 2, false, P, vec(0), vec(4), sc.p + par, h->partial, h->partial_stride, nullptr, nullptr, 0);
         }
     };
     // one untimed pair (TLB / L2 warm-up of the new position), then one timed repetition = two pairs (both direction-buffer parities)
-    launch_cg_A(s, h->g, true, plan, vec(0), vec(1), vec(2), vec(3), vec(4), sc.p, h->partial, nullptr, nullptr, 0);
-    launch_cg_Bq(s, h->g, true, plan, 2, vec(1), vec(2), vec(0), vec(4), sc.p, h->partial, h->partial_stride, nullptr, nullptr, 0);
+    launch_cg_A(s, h->g, true, plan, vec(0), P, vec(3), vec(4), sc.p, h->partial, nullptr, nullptr, 0);
+    launch_cg_Bq(s, h->g, true, plan, 2, false, P, vec(0), vec(4), sc.p, h->partial, h->partial_stride, nullptr, nullptr, 0);
     FL_HIP(hipEventRecord(h->ev0, s));
     run(1);
     FL_HIP(hipEventRecord(h->ev1, s));
@@ -734,6 +737,7 @@ extern "C" int fl_poisson_tune_placement(fl_poisson *h, int max_tries, double pr
     h->nvec = 0;
     h->slab = nullptr;
     for (double **v : {&h->r, &h->P0, &h->P1, &h->q, &h->xp, &h->w0, &h->w1, &h->w2, &h->cd1, &h->rb}) *v = nullptr;
+    for (double *&v : h->Pr) v = nullptr;
     FL_CHK(place_vectors(h));
   }
   if (probe_ms_out) {
@@ -1282,9 +1286,15 @@ static int solve_cg(fl_poisson *h, const double *b, double *x, const fl_ksp_opts
   hipStream_t s = h->stream;
 
   const bool xbatch_env = knob(K_cg_xbatch) != 0;
-  // q-free pair with batched x-updates: the padded x is not zeroed -- the first pair of updates (iteration 1) writes it without reading
-  // it, and until then KspScal::x_valid = 0 tells k_cg_finish that it stands for 0
-  const bool xlazy = !storeq && xbatch_env;
+  // q-free pair with batched x-updates: x is read and written on every K-th iteration only, K = the slots of the direction ring (one rank:
+  // cg_xdepth; several ranks and the stored-q variants: 2).  The padded x is not zeroed -- the first flush (iteration K - 1) writes it
+  // without reading it, and until then KspScal::x_valid = 0 tells k_cg_finish that it stands for 0
+  const bool xlazy  = !storeq && xbatch_env;
+  const int  xdepth = (xlazy && !h->multi && h->nv_il == 1) ? knob(K_cg_xdepth) : 2;
+  if (!cg_xdepth_ok(xdepth)) return FL_ERR_ARG_OUTOFRANGE;
+  for (int k = 2; k < xdepth; ++k) FL_CHK(fl_ensure_vec(h, &h->Pr[k - 2]));
+  DirRing ring = dir_ring2(h->P0, h->P1);
+  for (int k = 2; k < xdepth; ++k) ring.v[k] = h->Pr[k - 2];
   KspScal &S = *h->scal_host;
   std::memset(&S, 0, sizeof(S));
   S.rtol         = o->rtol;
@@ -1296,6 +1306,7 @@ static int solve_cg(fl_poisson *h, const double *b, double *x, const fl_ksp_opts
   S.nullspace    = o->remove_nullspace;
   S.rz_old       = 1.;
   S.x_valid      = xlazy ? 0 : 1;
+  S.xdepth       = xdepth;
 
   FL_HIP(hipEventRecord(h->ev0, s));
   FL_HIP(hipMemcpyAsync(h->scal, h->scal_host, sizeof(KspScal), hipMemcpyHostToDevice, s));
@@ -1303,8 +1314,7 @@ static int solve_cg(fl_poisson *h, const double *b, double *x, const fl_ksp_opts
   // so whatever FINITE numbers an earlier solve left there drop out (wall ghosts included: they only ever meet the stencil
   // coefficient 0).  After a solve that produced NaN / Inf they are cleared.  x is zeroed by the kernel that pads b into r.
   if (h->poisoned) {
-    FL_CHK(fl_zero_vec(h, h->P0));
-    FL_CHK(fl_zero_vec(h, h->P1));
+    for (int k = 0; k < xdepth; ++k) FL_CHK(fl_zero_vec(h, ring.v[k]));
     FL_CHK(fl_zero_vec(h, h->xp));
     h->poisoned = false;
   }
@@ -1338,8 +1348,8 @@ static int solve_cg(fl_poisson *h, const double *b, double *x, const fl_ksp_opts
   while (!done) {
     const int stop = std::min(o->maxit, it + every);
     for (; it < stop; ++it) {
-      // profile = n: the kernels of every n-th PAIR of iterations are bracketed (k_cg_Bq alternates between two forms)
-      const bool prof = o->profile > 0 && (it >> 1) % o->profile == 0 && (size_t)(4 * nprof + 3) < pev.size();
+      // profile = n: the kernels of every n-th GROUP of xdepth iterations are bracketed (one k_cg_Bq of a group also updates x)
+      const bool prof = o->profile > 0 && (it / xdepth) % o->profile == 0 && (size_t)(4 * nprof + 3) < pev.size();
       const int  pi   = 4 * nprof;
       if (prof) ++nprof;
       if (variant == 1) {
@@ -1350,7 +1360,7 @@ static int solve_cg(fl_poisson *h, const double *b, double *x, const fl_ksp_opts
         if (prof) FL_HIP(hipEventRecord(pev[pi + 1], s));
       } else {
         if (prof) FL_HIP(hipEventRecord(pev[pi], s));
-        launch_cg_A(s, g, jac, plan, h->r, h->P0, h->P1, h->q, h->xp, h->scal, h->partial, (fusedfin || fusedsum) ? h->tickets : nullptr, h->hist, nhist, fusedsum ? h->sums : nullptr);
+        launch_cg_A(s, g, jac, plan, h->r, ring, h->q, h->xp, h->scal, h->partial, (fusedfin || fusedsum) ? h->tickets : nullptr, h->hist, nhist, fusedsum ? h->sums : nullptr);
         if (prof) FL_HIP(hipEventRecord(pev[pi + 1], s));
       }
       const int modeA = storeq ? 1 : 3;  // q-free pair: k_cg_A does not touch x (see cg_fin_apply)
@@ -1358,19 +1368,20 @@ static int solve_cg(fl_poisson *h, const double *b, double *x, const fl_ksp_opts
       else if (!fusedfin) FL_CHK(cg_fin(h, modeA, nab, 1, h->hist, nhist));
       hostcur ^= 1;
       // several ranks: the boundary layers of the new r leave now (packed as r - alpha q), the transfers overlap k_cg_B
-      // q-free pair: k_cg_Bq owns the x-update -- both updates of an iteration pair on the odd one (x is read and written every second
-      // iteration only), or one per iteration with FLUCA_CG_XBATCH=0
-      const int  xmode   = xbatch_env ? ((it & 1) ? (it == 1 ? 3 : 2) : 0) : 1;
+      // q-free pair: k_cg_Bq owns the x-update -- all xdepth updates of a group of iterations on its last one (x is read and written
+      // every xdepth-th iteration only), or one per iteration with FLUCA_CG_XBATCH=0
+      const int  xu      = xbatch_env ? (it % xdepth == xdepth - 1 ? xdepth : 0) : 1;
+      const bool xz      = xbatch_env && it == xdepth - 1;  // the first flush: x = 0 is not read
       const bool overlap = ghosts && variant != 1 && h->multi && overlap_env;
       if (overlap) FL_CHK(fl_exchange_r_begin(h, h->r, h->q));
       if (prof) FL_HIP(hipEventRecord(pev[pi + 2], s));
       if (storeq) launch_cg_B(s, g, jac, planB, h->q, h->r, h->scal, h->partial, h->partial_stride, (fusedfin || fusedsum) ? h->tickets + 1 : nullptr, h->hist, nhist, fusedsum ? h->sums : nullptr);
-      else launch_cg_Bq(s, g, jac, planB, xmode, h->P0, h->P1, h->r, h->xp, h->scal, h->partial, h->partial_stride, (fusedfin || fusedsum) ? h->tickets + 1 : nullptr, h->hist, nhist, fusedsum ? h->sums : nullptr);
+      else launch_cg_Bq(s, g, jac, planB, xu, xz, ring, h->r, h->xp, h->scal, h->partial, h->partial_stride, (fusedfin || fusedsum) ? h->tickets + 1 : nullptr, h->hist, nhist, fusedsum ? h->sums : nullptr);
       if (prof) FL_HIP(hipEventRecord(pev[pi + 3], s));
       // the handle's stream joins the exchange BEFORE the all-reduce is enqueued: the two RCCL operations never run at the same time
       // (one communicator, two streams), only the transfers and k_cg_B do
       if (overlap) FL_CHK(fl_exchange_r_end(h, h->r));
-      const int modeB = (!storeq && xmode) ? 4 : 2;
+      const int modeB = (!storeq && xu) ? 4 : 2;
       if (fusedsum) FL_CHK(fin_sums(modeB));
       else if (!fusedfin) FL_CHK(cg_fin(h, modeB, planB.nblocks, 5, h->hist, nhist));
       if (!overlap && ghosts && variant != 1) FL_CHK(fl_fill_ghosts(h, h->r));
@@ -1378,7 +1389,7 @@ static int solve_cg(fl_poisson *h, const double *b, double *x, const fl_ksp_opts
     FL_CHK(fl_poll_scal(h));
     if (h->scal_host->reason != 0 || it >= o->maxit) done = true;
   }
-  launch_cg_finish(s, g, h->P0, h->P1, h->xp, x, h->scal, nsb);  // x = xp + the x-update still owed
+  launch_cg_finish(s, g, ring, h->xp, x, h->scal, nsb);  // x = xp + the x-updates still owed
   FL_HIP(hipEventRecord(h->ev1, s));
   FL_CHK(fl_poll_scal(h));
   FL_HIP(hipGetLastError());
@@ -1399,7 +1410,7 @@ static int solve_cg(fl_poisson *h, const double *b, double *x, const fl_ksp_opts
     // iterations enqueued after the device had stopped are early exits: count only those that ran
     int ran = 0;
     for (int a = 0, q = 0; a < R.it; ++a)
-      if ((a >> 1) % o->profile == 0 && q++ < nprof) ++ran;
+      if ((a / xdepth) % o->profile == 0 && q++ < nprof) ++ran;
     prof_events.mean_of(ran, 4, 0, 1, &st->kernel_ms, &st->kernel_launches);
     prof_events.mean_of(ran, 4, 2, 3, &st->kernel2_ms, &st->kernel2_launches);
   }
@@ -1724,6 +1735,7 @@ extern "C" int fldbg_bench(fl_poisson *h, int kernel, int ry, int pf, int nchunk
     h->nvec = 0;
     h->slab = nullptr;
     for (double **v : {&h->r, &h->P0, &h->P1, &h->q, &h->xp, &h->w0, &h->w1, &h->w2}) *v = nullptr;
+    for (double *&v : h->Pr) v = nullptr;
     *ms_out = 0.;
     return FL_SUCCESS;
   }
@@ -1737,6 +1749,7 @@ extern "C" int fldbg_bench(fl_poisson *h, int kernel, int ry, int pf, int nchunk
     h->nvec = 0;
     h->slab = nullptr;
     for (double **v : {&h->r, &h->P0, &h->P1, &h->q, &h->xp, &h->w0, &h->w1, &h->w2}) *v = nullptr;
+    for (double *&v : h->Pr) v = nullptr;
     for (int a = 0; a < ry; ++a) {
       void *junk = nullptr;
       FL_HIP(hipMalloc(&junk, (size_t)pf << 20));
@@ -1767,7 +1780,7 @@ extern "C" int fldbg_bench(fl_poisson *h, int kernel, int ry, int pf, int nchunk
   if (FL_VARIANT(print_ptrs, 0) && kernel == 0)
     std::fprintf(stderr, "[ptrs] r=%p P0=%p P1=%p q=%p xp=%p w0=%p\n", (void *)h->r, (void *)h->P0, (void *)h->P1, (void *)h->q, (void *)h->xp, (void *)h->w0);
   auto once = [&]() {
-    if (kernel == 0) launch_cg_A(s, g, true, plan, h->r, h->P0, h->P1, h->q, h->xp, h->scal, h->partial, nullptr, nullptr, 0);
+    if (kernel == 0) launch_cg_A(s, g, true, plan, h->r, dir_ring2(h->P0, h->P1), h->q, h->xp, h->scal, h->partial, nullptr, nullptr, 0);
     else if (kernel == 1) launch_cg_B(s, g, true, plan, h->q, h->r, h->scal, h->partial, h->partial_stride, nullptr, nullptr, 0);
     else if (kernel == 2) launch_stream_ref(s, ry, pf, (int64_t)(h->padlen - 256) / 2, h->r, h->P0, h->xp, h->P1, h->q, h->w0);
     else {
@@ -1875,7 +1888,7 @@ extern "C" int fldbg_pool_probe(fl_poisson *h, int K, int M, unsigned seed, doub
     }
     auto probe = [&](int reps) {
       for (int r = 0; r < reps; ++r)
-        for (int par = 0; par < 2; ++par) launch_cg_A(s, h->g, true, plan, pool[sel[0]], pool[sel[1]], pool[sel[2]], pool[sel[3]], pool[sel[4]], scal2 + par, h->partial, nullptr, nullptr, 0);
+        for (int par = 0; par < 2; ++par) launch_cg_A(s, h->g, true, plan, pool[sel[0]], dir_ring2(pool[sel[1]], pool[sel[2]]), pool[sel[3]], pool[sel[4]], scal2 + par, h->partial, nullptr, nullptr, 0);
     };
     probe(1);
     FL_HIP(hipEventRecord(h->ev0, s));
@@ -1987,7 +2000,7 @@ extern "C" int fldbg_kernel_ptrs(fl_poisson *h, int kernel, void *const *ptrs, i
   KspScal *keep = h->scal;
   auto     once = [&]() {
     for (int par = 0; par < 2; ++par) {
-      if (kernel == 0) launch_cg_A(s, h->g, true, plan, v[0], v[1], v[2], v[3], v[4], scal2 + par, h->partial, nullptr, nullptr, 0);
+      if (kernel == 0) launch_cg_A(s, h->g, true, plan, v[0], dir_ring2(v[1], v[2]), v[3], v[4], scal2 + par, h->partial, nullptr, nullptr, 0);
       else {
         h->scal = scal2 + par;
         fl_launch_cheb2(h, cp, true, v[0], v[1], v[2], v[3], v[4]);

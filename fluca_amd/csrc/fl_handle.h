@@ -46,7 +46,7 @@ void launch_reduce(hipStream_t, const double *, int, int, int, double *);
 void launch_cg_fin(hipStream_t, int, const double *, int, int, const double *, KspScal *, double *, int);
 int  stream_blocks(const GridP &);
 void launch_cg_init(hipStream_t, const GridP &, bool, const double *, double *, double *, double *, int, int);
-void launch_cg_finish(hipStream_t, const GridP &, const double *, const double *, const double *, double *, const KspScal *, int);
+void launch_cg_finish(hipStream_t, const GridP &, const DirRing &, const double *, double *, const KspScal *, int);
 struct PlanA {
   int ry, nw, tiles_x, tiles_y, nchunk, zc, nblocks, pf, nt, remap, probe;
   int sq, qb;  // keep in step with the definition in fl_kernels.hip
@@ -54,9 +54,10 @@ struct PlanA {
 PlanA plan_tiles(const GridP &, int ry, int nw, int nchunk_force, int target_blocks, int min_zc = 8);
 PlanA plan_cg_A(const GridP &, int, int);
 PlanA plan_cg_B(const GridP &);
-void  launch_cg_A(hipStream_t, const GridP &, bool, const PlanA &, const double *, double *, double *, double *, double *, KspScal *, double *, unsigned *, double *, int, double *sums = nullptr);
-void  launch_cg_Bq(hipStream_t, const GridP &, bool, const PlanA &, int xmode, const double *P0, const double *P1, double *r, double *x, KspScal *, double *partial, int stride, unsigned *counter, double *hist, int nhist,
-                   double *sums = nullptr);
+void  launch_cg_A(hipStream_t, const GridP &, bool, const PlanA &, const double *r, const DirRing &P, double *q, double *x, KspScal *, double *, unsigned *, double *, int, double *sums = nullptr);
+bool  cg_xdepth_ok(int k);  // the direction-ring depths k_cg_Bq is built for (2, 3, 4, 8)
+void  launch_cg_Bq(hipStream_t, const GridP &, bool, const PlanA &, int xu, bool xz, const DirRing &P, double *r, double *x, KspScal *, double *partial, int stride, unsigned *counter, double *hist,
+                   int nhist, double *sums = nullptr);
 void  launch_cg_B(hipStream_t, const GridP &, bool, const PlanA &, const double *, double *, KspScal *, double *, int, unsigned *, double *, int, double *sums = nullptr);
 void  launch_stream_ref(hipStream_t, int, int, int64_t, const double *, const double *, const double *, double *, double *, double *);
 void  launch_stream_par(hipStream_t, int, int, int, int, int, int64_t, const double *, const double *, const double *, double *, double *, double *);
@@ -331,6 +332,7 @@ struct fl_poisson {
   int         cheb2_agreed[2] = {-1, -1};
   // solver workspace (padded vectors)
   double *r = nullptr, *P0 = nullptr, *P1 = nullptr, *q = nullptr, *xp = nullptr, *w0 = nullptr, *w1 = nullptr, *w2 = nullptr;
+  double *Pr[CG_XRING_MAX - 2] = {};  // CG: slots 2 .. of the direction ring beyond P0 / P1 (cg_xdepth > 2), created by the first solve that needs them
   double *cd1 = nullptr;  // second d buffer of the fused two-step Chebyshev kernel (fl_cheb2.hip)
   void   *sv_pack[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // packed 1-D rows of the fused DIAG / ROWSUM Schur product (fl_schur_var.hip; freed with h->tables)
   double *rb = nullptr;   // where the three-step sweep from a zero guess writes the updated right-hand side; swaps roles with r afterwards

@@ -71,10 +71,24 @@ struct GridP {
   double        kappa;
 };
 
+// CG: the direction buffers form a ring of xdepth (2 .. CG_XRING_MAX) slots; iteration i writes slot (i + 1) mod xdepth, and x owes the
+// updates of the directions still in the ring (k_cg_Bq applies xdepth of them at once, k_cg_finish what is left when the solve stops)
+constexpr int CG_XRING_MAX = 8;
+struct DirRing {
+  double *v[CG_XRING_MAX];  // slots 0 .. xdepth - 1 are used; the others may be null
+};
+inline DirRing dir_ring2(double *P0, double *P1)
+{
+  DirRing R = {};
+  R.v[0]    = P0;
+  R.v[1]    = P1;
+  return R;
+}
+
 // device-side scalar state of a Krylov solve (one per handle)
 struct KspScal {
   double rz, rz_old, pq, alpha, beta, zshift, dp, rnorm0, ttol;
-  double alpha_old;  // CG: the step length of the iteration before (k_cg_Bq applies two x-updates every second iteration)
+  double aring[CG_XRING_MAX];  // CG: the step length of the direction in each ring slot (aring[cur] == alpha)
   double rtol, atol, dtol;
   double ncell_global;
   // BiCGStab
@@ -85,6 +99,7 @@ struct KspScal {
   int    x_valid;  // CG, q-free pair: 0 until k_cg_Bq has written x for the first time (the padded x is not zeroed: the first pair of
                    // updates writes it without reading it)
   int    dcur;  // Chebyshev: which of the two d buffers holds the current d (the fused two-step kernel flips it)
+  int    xdepth;  // CG: slots of the direction ring (DirRing); 0 counts as 2.  pending_x = x-updates owed (0 .. xdepth - 1)
 };
 
 constexpr int MAX_PARTIAL_BLOCKS = 4096;

@@ -667,11 +667,23 @@ __device__ __forceinline__ double cg_norms(KspScal *s, const double *sum, double
   }
 }
 
+// direction ring (DirRing, KspScal::xdepth): slot k of the ring; the select chain keeps a wave-uniform slot in scalar registers
+__device__ __forceinline__ int ring_depth(const KspScal *s) { return s->xdepth > 2 ? s->xdepth : 2; }
+__device__ __forceinline__ double *ring_at(const DirRing &R, int k)
+{
+  double *p = R.v[0];
+#pragma unroll
+  for (int j = 1; j < CG_XRING_MAX; ++j)
+    if (k == j) p = R.v[j];
+  return p;
+}
+
 // mode 0: after k_cg_init.  mode 1: after k_cg_A (alpha).  mode 2: after k_cg_B / k_cg_Bq (beta, convergence).  One thread.
-// Who owes x what (pending_x = 1: x still lacks alpha * p of the current direction; k_cg_finish adds it):
-//   stored-q pair: k_cg_A applies the update deferred from the iteration before (mode 1 clears the flag), k_cg_B leaves one (mode 2);
-//   q-free pair:   k_cg_A never touches x (mode 3 = mode 1 without clearing); k_cg_Bq applies none on even iterations (mode 2) and
-//                  the two it then owes on odd ones (mode 4 = mode 2 with nothing left pending).
+// Who owes x what (pending_x = n: x still lacks the updates of the n newest directions, ring slots cur - n + 1 .. cur; k_cg_finish
+// adds them):
+//   stored-q pair: k_cg_A applies the update deferred from the iteration before (mode 1 clears it), k_cg_B leaves one (mode 2);
+//   q-free pair:   k_cg_A never touches x (mode 3 = mode 1 without clearing); k_cg_Bq applies none (mode 2: one more owed) except on
+//                  every xdepth-th iteration, where it applies all xdepth updates owed (mode 4 = mode 2 with nothing left pending).
 __device__ __forceinline__ void cg_fin_apply(int mode, const double *out, KspScal *__restrict__ s, double *__restrict__ hist, int nhist)
 {
   if (mode == 1 || mode == 3) {
@@ -683,9 +695,9 @@ __device__ __forceinline__ void cg_fin_apply(int mode, const double *out, KspSca
       s->reason = isnan(pq) ? FL_DIVERGED_NANORINF : FL_DIVERGED_INDEFINITE_MAT;
       return;
     }
-    s->cur ^= 1;
-    s->alpha_old = s->alpha;
-    s->alpha     = s->rz / pq;
+    s->cur            = s->cur + 1 == ring_depth(s) ? 0 : s->cur + 1;
+    s->alpha          = s->rz / pq;
+    s->aring[s->cur]  = s->alpha;
     return;
   }
   double       rz;
@@ -702,7 +714,7 @@ __device__ __forceinline__ void cg_fin_apply(int mode, const double *out, KspSca
     s->rz        = rz;
     s->beta      = rz / s->rz_old;
     s->it += 1;
-    s->pending_x = mode == 4 ? 0 : 1;
+    s->pending_x = mode == 4 ? 0 : s->pending_x + 1;
     if (mode == 4) s->x_valid = 1;
   }
   s->dp = dp;
@@ -925,14 +937,20 @@ __global__ void __launch_bounds__(256) k_cg_B(GridP g, const double *__restrict_
 }
 #endif  // FL_KBENCH_VARIANTS
 
-// the x-update still owed when the iteration stops, fused with the copy into the caller's (unpadded) array:
-//   xout = x + alpha p   (p = the current direction; plain copy when nothing is pending).  The padded x is not updated: the
-// next solve starts from its own zeroed copy.
-__global__ void __launch_bounds__(256) k_cg_finish(GridP g, const double *__restrict__ P0, const double *__restrict__ P1, const double *__restrict__ x, double *__restrict__ xout, const KspScal *__restrict__ s, int pairs)
+// the x-updates still owed when the iteration stops, fused with the copy into the caller's (unpadded) array:
+//   xout = x + a_(cur-n+1) p_(cur-n+1) + ... + a_cur p_cur   (n = pending_x ring slots, oldest first, one fma each: the order k_cg_Bq
+// applies them in; plain copy when nothing is pending).  The padded x is not updated: the next solve starts from its own zeroed copy.
+__global__ void __launch_bounds__(256) k_cg_finish(GridP g, DirRing P, const double *__restrict__ x, double *__restrict__ xout, const KspScal *__restrict__ s, int pairs)
 {
-  const double *p     = s->cur ? P1 : P0;
-  const double  alpha = s->pending_x ? s->alpha : 0.;
-  const bool    upd   = s->pending_x != 0;
+  const int     K = ring_depth(s), n = s->pending_x, cur = s->cur;
+  const double *pt[CG_XRING_MAX];  // pt[t], at[t]: the direction t iterations before the current one
+  double        at[CG_XRING_MAX];
+#pragma unroll
+  for (int t = 0; t < CG_XRING_MAX; ++t) {
+    const int k = cur - t < 0 ? cur - t + K : cur - t;
+    pt[t]       = t < n ? ring_at(P, k) : nullptr;
+    at[t]       = t < n ? s->aring[k] : 0.;
+  }
   const bool    xv    = s->x_valid != 0;  // false: x has never been written in this solve (it stands for 0)
   const int     lane  = threadIdx.x & 63;
   const int     nxs   = (g.nx + 127) / 128;
@@ -945,18 +963,23 @@ __global__ void __launch_bounds__(256) k_cg_finish(GridP g, const double *__rest
     const int64_t ob = ((int64_t)k * g.ny + j) * g.nx + i, op = pidx(g, i, j, k);
     if (pairs && i + 1 < g.nx) {
       double2 v = xv ? *reinterpret_cast<const double2 *>(x + op) : make_double2(0., 0.);
-      if (upd) {
-        const double2 pv = *reinterpret_cast<const double2 *>(p + op);
-        v.x += alpha * pv.x;
-        v.y += alpha * pv.y;
-      }
+#pragma unroll
+      for (int t = CG_XRING_MAX - 1; t >= 0; --t)
+        if (t < n) {
+          const double2 pv = *reinterpret_cast<const double2 *>(pt[t] + op);
+          v.x              = fma(at[t], pv.x, v.x);
+          v.y              = fma(at[t], pv.y, v.y);
+        }
       *reinterpret_cast<double2 *>(xout + ob) = v;
     } else {
 #pragma unroll
       for (int c = 0; c < 2; ++c)
         if (i + c < g.nx) {
-          const double xv0 = xv ? x[op + c] : 0.;
-          xout[ob + c]     = upd ? xv0 + alpha * p[op + c] : xv0;
+          double v = xv ? x[op + c] : 0.;
+#pragma unroll
+          for (int t = CG_XRING_MAX - 1; t >= 0; --t)
+            if (t < n) v = fma(at[t], pt[t][op + c], v);
+          xout[ob + c] = v;
         }
     }
   }
@@ -969,7 +992,7 @@ __global__ void __launch_bounds__(256) k_cg_finish(GridP g, const double *__rest
 // SQ: store q (k_cg_B reads it back) and apply the x-update deferred from the iteration before; !SQ: neither -- q is formed again and
 // x is updated by k_cg_Bq, so this kernel reads r, p and writes p' (24 B/cell).
 template <int RY, int NW, bool JAC, int PF, int NT, bool SQ>
-__device__ __forceinline__ void cg_A_body(const GridP &g, const double *__restrict__ r, double *__restrict__ P0, double *__restrict__ P1, double *__restrict__ q, double *__restrict__ x, KspScal *__restrict__ s,
+__device__ __forceinline__ void cg_A_body(const GridP &g, const double *__restrict__ r, const double *__restrict__ pold, double *__restrict__ pnew, double *__restrict__ q, double *__restrict__ x, KspScal *__restrict__ s,
                                                       double *__restrict__ partial, int nchunk, int zc, int tiles_x, int tiles, int remap, FinCtx fin)
 {
   using T               = TileA<RY, NW>;
@@ -982,9 +1005,6 @@ __device__ __forceinline__ void cg_A_body(const GridP &g, const double *__restri
   __shared__ int                                 flag;
   if (s->reason != 0) return;
 
-  const int     cur        = s->cur;
-  const double *pold       = cur ? P1 : P0;
-  double       *pnew       = cur ? P0 : P1;
   const double  beta       = s->beta;
   const double  zs         = s->zshift;
   const double  alpha_prev = s->alpha;  // 0 on the first iteration (and p_old = 0): the deferred x-update is a no-op then
@@ -1213,18 +1233,22 @@ __device__ __forceinline__ void cg_A_body(const GridP &g, const double *__restri
   else if (tid == 0) partial[blockIdx.x] = tot[0];
 }
 
-#define FL_CG_A_ARGS GridP g, const double *__restrict__ r, double *__restrict__ P0, double *__restrict__ P1, double *__restrict__ q, double *__restrict__ x, KspScal *__restrict__ s, double *__restrict__ partial, int nchunk, int zc, int tiles_x, int tiles, int remap, FinCtx fin
+// The kernels pick the two ring slots and hand them to the body as __restrict__ parameters: p' stores that might alias the p loads
+// would pin every prefetch behind them (k_cg_A 0.59 -> 0.62 ms at 512^3 when the body took them from the ring itself).
+#define FL_CG_A_ARGS GridP g, const double *__restrict__ r, DirRing P, double *__restrict__ q, double *__restrict__ x, KspScal *__restrict__ s, double *__restrict__ partial, int nchunk, int zc, int tiles_x, int tiles, int remap, FinCtx fin
 template <int RY, int NW, bool JAC, int PF, int NT, bool SQ>
 __global__ void __launch_bounds__(64 * NW, FL_CGA_WPE) k_cg_A(FL_CG_A_ARGS)
 {
-  cg_A_body<RY, NW, JAC, PF, NT, SQ>(g, r, P0, P1, q, x, s, partial, nchunk, zc, tiles_x, tiles, remap, fin);
+  const int cur = s->cur;  // p_old = ring slot cur; p' goes to the next slot, the oldest direction (x holds its update)
+  cg_A_body<RY, NW, JAC, PF, NT, SQ>(g, r, ring_at(P, cur), ring_at(P, cur + 1 == ring_depth(s) ? 0 : cur + 1), q, x, s, partial, nchunk, zc, tiles_x, tiles, remap, fin);
 }
 // The same code under another name: launched only by fl_poisson_tune_placement, so that profiles keep the probe
 // launches (half of them on deliberately rejected placements) apart from the solver's own launches.
 template <int RY, int NW, bool JAC, int PF, int NT, bool SQ>
 __global__ void __launch_bounds__(64 * NW, 2) k_cg_A_probe(FL_CG_A_ARGS)
 {
-  cg_A_body<RY, NW, JAC, PF, NT, SQ>(g, r, P0, P1, q, x, s, partial, nchunk, zc, tiles_x, tiles, remap, fin);
+  const int cur = s->cur;  // p_old = ring slot cur; p' goes to the next slot, the oldest direction (x holds its update)
+  cg_A_body<RY, NW, JAC, PF, NT, SQ>(g, r, ring_at(P, cur), ring_at(P, cur + 1 == ring_depth(s) ? 0 : cur + 1), q, x, s, partial, nchunk, zc, tiles_x, tiles, remap, fin);
 }
 #undef FL_CG_A_ARGS
 
@@ -1234,15 +1258,17 @@ __global__ void __launch_bounds__(64 * NW, 2) k_cg_A_probe(FL_CG_A_ARGS)
 // (128 x NW*RY tile marching through a z chunk, three p' planes in LDS, raw planes fetched one trip ahead into a second register
 // set, unconditional loads on clamped addresses, masked stores); q comes out of st7 exactly as in k_cg_A.  The ghost layer of p'
 // is complete: k_cg_A stores p' on every star-ghost cell it forms (rows / columns / planes -1 and n).  Sums as in k_cg_B.
-// The x-update lives here too (XM): the direction is in registers anyway.  XM == 2 on odd iterations: x += alpha_old p_old + alpha p'
-// (p_old = the other direction buffer, which k_cg_A overwrites only in the NEXT iteration), XM == 0 on even ones: nothing -- x is read
-// and written every second iteration only (12 instead of 16 B/cell/iteration).  XM == 3: the first odd iteration of a solve, as XM == 2
-// with x = 0 not read (the padded x is not zeroed by k_cg_init then).  XM == 1: x += alpha p' every iteration (A/B runs).
-// The two fma of XM == 2 are the two separate updates in the same order: same x bit for bit.
-template <int RY, int NW, bool JAC, int NT, int XM>
-__device__ __forceinline__ void cg_Bq_body(const GridP &g, const double *__restrict__ P0, const double *__restrict__ P1, double *__restrict__ r, double *__restrict__ x, KspScal *__restrict__ s,
+// The x-update lives here too (XU updates): the direction is in registers anyway.  With a ring of K direction buffers (DirRing,
+// KspScal::xdepth) x is read and written on every K-th iteration only: XU == K there -- x += a_(i-K+1) p_(i-K+1) + ... + a_(i-1) p_(i-1)
+// + alpha p', the K - 1 older directions from their ring slots, which k_cg_A overwrites only from the NEXT iteration on -- and XU == 0
+// on the others: 8 (K - 1) + 16 B/cell per K iterations instead of 16 per iteration.  XZ: the first such launch of a solve, x = 0 is not
+// read (the padded x is not zeroed by k_cg_init then).  XU == 1: x += alpha p' every iteration (cg_xbatch = 0, A/B runs).
+// The fma of XU > 1 are the separate updates in iteration order: same x bit for bit.
+template <int RY, int NW, bool JAC, int NT, int XU, bool XZ>
+__device__ __forceinline__ void cg_Bq_body(const GridP &g, const DirRing &P, double *__restrict__ r, double *__restrict__ x, KspScal *__restrict__ s,
                                            double *__restrict__ partial, int stride, int nchunk, int zc, int tiles_x, int tiles, int remap, FinCtx fin)
 {
+  constexpr int NO = XU > 1 ? XU - 1 : 1;  // older directions read by an x-flush (array extent)
   using T               = TileA<RY, NW>;
   constexpr int TX = T::TX, TY = T::TY, LX = T::LX, LY = T::LY;
   constexpr int NTL = NT >= 2, NTS = NT >= 1;
@@ -1250,9 +1276,17 @@ __device__ __forceinline__ void cg_Bq_body(const GridP &g, const double *__restr
   __shared__ double                              red[5 * NW];
   __shared__ int                                 flag;
   if (s->reason != 0) return;
-  const double *p     = s->cur ? P1 : P0;  // the scalar step after k_cg_A has flipped cur: this is the direction it wrote
-  const double *pprev = s->cur ? P0 : P1;
-  const double  alpha = s->alpha, alpha_old = s->alpha_old;
+  const int     cur   = s->cur;
+  const double *p     = ring_at(P, cur);  // the scalar step after k_cg_A has advanced cur: this is the direction it wrote
+  const double  alpha = s->alpha;
+  const double *pold[NO];  // pold[t], aold[t]: the direction XU - 1 - t iterations before the current one (oldest first)
+  double        aold[NO];
+#pragma unroll
+  for (int t = 0; t < NO; ++t) {
+    const int back = XU - 1 - t, k = cur - back < 0 ? cur - back + ring_depth(s) : cur - back;
+    pold[t]        = XU > 1 ? ring_at(P, k) : p;
+    aold[t]        = XU > 1 ? s->aring[k] : 0.;
+  }
 
   const int b     = remap ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
   const int chunk = b / tiles, tile = b % tiles;
@@ -1298,7 +1332,7 @@ __device__ __forceinline__ void cg_Bq_body(const GridP &g, const double *__restr
   double zlc = 0., zcc = 0., zhc = 0.;  // z-row of plane kk-1 (the plane whose q is formed)
   struct Raw {
     double2 p[RY], r[RY];  // p' of plane kn, r of plane kn - 1
-    double2 x[(XM == 1 || XM == 2) ? RY : 1], pp[XM >= 2 ? RY : 1];  // x (and the direction before) of plane kn - 1
+    double2 x[(XU >= 1 && !XZ) ? RY : 1], pp[NO][XU > 1 ? RY : 1];  // x (and the older directions) of plane kn - 1
     double  hpA, hpB;
     double  zl, zc, zh;
   };
@@ -1309,8 +1343,10 @@ __device__ __forceinline__ void cg_Bq_body(const GridP &g, const double *__restr
     for (int m = 0; m < RY; ++m) {
       R.p[m] = ld2<NTL>(p + RO(m) + pl);
       R.r[m] = ld2<NTL>(r + RO(m) + pr);
-      if (XM == 1 || XM == 2) R.x[m] = ld2<NTL>(x + RO(m) + pr);
-      if (XM >= 2) R.pp[m] = ld2<NTL>(pprev + RO(m) + pr);
+      if (XU >= 1 && !XZ) R.x[m] = ld2<NTL>(x + RO(m) + pr);
+      if (XU > 1)
+#pragma unroll
+        for (int t = 0; t < NO; ++t) R.pp[t][m] = ld2<NTL>(pold[t] + RO(m) + pr);
     }
     R.hpA = p[tbase + pl + hAo];
     R.hpB = p[tbase + pl + hBo];
@@ -1347,12 +1383,14 @@ __device__ __forceinline__ void cg_Bq_body(const GridP &g, const double *__restr
           if (own1) st2<NTS>(r + RO(m) + pc, rn);
           else if (own0) r[RO(m) + pc] = rn.x;
         }
-        if (XM) {
-          double2 xn = XM == 3 ? make_double2(0., 0.) : C.x[m];  // XM == 3: the first pair of updates of a solve, x = 0 is not read
-          if (XM >= 2) {
-            xn.x = fma(alpha_old, C.pp[m].x, xn.x);
-            xn.y = fma(alpha_old, C.pp[m].y, xn.y);
-          }
+        if (XU) {
+          double2 xn = XZ ? make_double2(0., 0.) : C.x[m];  // XZ: the first updates of a solve, x = 0 is not read
+          if (XU > 1)
+#pragma unroll
+            for (int t = 0; t < NO; ++t) {
+              xn.x = fma(aold[t], C.pp[t][m].x, xn.x);
+              xn.y = fma(aold[t], C.pp[t][m].y, xn.y);
+            }
           xn.x = fma(alpha, cen.x, xn.x);
           xn.y = fma(alpha, cen.y, xn.y);
           if (rown[m]) {
@@ -1401,22 +1439,22 @@ __device__ __forceinline__ void cg_Bq_body(const GridP &g, const double *__restr
 #pragma unroll
       for (int q = 0; q < NW; ++q) tot[a] += red[a * NW + q];
   }
-  if (fin.enabled) fused_fin<5, 64 * NW>(XM ? 4 : 2, tot, partial, stride, fin, s, red, &flag);
+  if (fin.enabled) fused_fin<5, 64 * NW>(XU ? 4 : 2, tot, partial, stride, fin, s, red, &flag);
   else if (tid == 0)
 #pragma unroll
     for (int a = 0; a < 5; ++a) partial[(int64_t)a * stride + blockIdx.x] = tot[a];
 }
-#define FL_CG_BQ_ARGS GridP g, const double *__restrict__ P0, const double *__restrict__ P1, double *__restrict__ r, double *__restrict__ x, KspScal *__restrict__ s, double *__restrict__ partial, int stride, int nchunk, int zc, int tiles_x, int tiles, int remap, FinCtx fin
-template <int RY, int NW, bool JAC, int NT, int XM>
+#define FL_CG_BQ_ARGS GridP g, DirRing P, double *__restrict__ r, double *__restrict__ x, KspScal *__restrict__ s, double *__restrict__ partial, int stride, int nchunk, int zc, int tiles_x, int tiles, int remap, FinCtx fin
+template <int RY, int NW, bool JAC, int NT, int XU, bool XZ>
 __global__ void __launch_bounds__(64 * NW, FL_CGB_WPE) k_cg_Bq(FL_CG_BQ_ARGS)
 {
-  cg_Bq_body<RY, NW, JAC, NT, XM>(g, P0, P1, r, x, s, partial, stride, nchunk, zc, tiles_x, tiles, remap, fin);
+  cg_Bq_body<RY, NW, JAC, NT, XU, XZ>(g, P, r, x, s, partial, stride, nchunk, zc, tiles_x, tiles, remap, fin);
 }
 // the placement probe's launches under their own name (see k_cg_A_probe)
-template <int RY, int NW, bool JAC, int NT, int XM>
+template <int RY, int NW, bool JAC, int NT, int XU, bool XZ>
 __global__ void __launch_bounds__(64 * NW, 2) k_cg_Bq_probe(FL_CG_BQ_ARGS)
 {
-  cg_Bq_body<RY, NW, JAC, NT, XM>(g, P0, P1, r, x, s, partial, stride, nchunk, zc, tiles_x, tiles, remap, fin);
+  cg_Bq_body<RY, NW, JAC, NT, XU, XZ>(g, P, r, x, s, partial, stride, nchunk, zc, tiles_x, tiles, remap, fin);
 }
 #undef FL_CG_BQ_ARGS
 
@@ -1720,9 +1758,9 @@ void launch_cg_init(hipStream_t st, const GridP &g, bool jac, const double *b, d
   if (jac) hipLaunchKernelGGL(k_cg_init<true>, dim3(nblocks), dim3(256), 0, st, g, b, r, x0, partial, stride, pairs);
   else hipLaunchKernelGGL(k_cg_init<false>, dim3(nblocks), dim3(256), 0, st, g, b, r, x0, partial, stride, pairs);
 }
-void launch_cg_finish(hipStream_t st, const GridP &g, const double *P0, const double *P1, const double *x, double *xout, const KspScal *s, int nblocks)
+void launch_cg_finish(hipStream_t st, const GridP &g, const DirRing &P, const double *x, double *xout, const KspScal *s, int nblocks)
 {
-  hipLaunchKernelGGL(k_cg_finish, dim3(nblocks), dim3(256), 0, st, g, P0, P1, x, xout, s, unpadded_pairs(g, xout));
+  hipLaunchKernelGGL(k_cg_finish, dim3(nblocks), dim3(256), 0, st, g, P, x, xout, s, unpadded_pairs(g, xout));
 }
 
 // tiling of k_cg_A: returns the number of blocks
@@ -1815,46 +1853,46 @@ PlanA plan_cg_B(const GridP &g)
 }
 
 template <int RY, int NW, int PF, int NT, bool SQ>
-static void launch_cg_A_q(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const double *r, double *P0, double *P1, double *q, double *x, KspScal *s, double *partial, const FinCtx &fin)
+static void launch_cg_A_q(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const double *r, const DirRing &P, double *q, double *x, KspScal *s, double *partial, const FinCtx &fin)
 {
   const int  tiles = p.tiles_x * p.tiles_y;
   const int  rq    = (p.remap ? 1 : 0) | (p.qb ? 2 : 0);  // bit 0: XCD-contiguous block order, bit 1: q on the boundary layers
   const dim3 gr(p.nblocks), bl(64 * NW);
   if (p.probe) {
-    if (jac) hipLaunchKernelGGL((k_cg_A_probe<RY, NW, true, PF, NT, SQ>), gr, bl, 0, st, g, r, P0, P1, q, x, s, partial, p.nchunk, p.zc, p.tiles_x, tiles, rq, fin);
-    else hipLaunchKernelGGL((k_cg_A_probe<RY, NW, false, PF, NT, SQ>), gr, bl, 0, st, g, r, P0, P1, q, x, s, partial, p.nchunk, p.zc, p.tiles_x, tiles, rq, fin);
+    if (jac) hipLaunchKernelGGL((k_cg_A_probe<RY, NW, true, PF, NT, SQ>), gr, bl, 0, st, g, r, P, q, x, s, partial, p.nchunk, p.zc, p.tiles_x, tiles, rq, fin);
+    else hipLaunchKernelGGL((k_cg_A_probe<RY, NW, false, PF, NT, SQ>), gr, bl, 0, st, g, r, P, q, x, s, partial, p.nchunk, p.zc, p.tiles_x, tiles, rq, fin);
   } else {
-    if (jac) hipLaunchKernelGGL((k_cg_A<RY, NW, true, PF, NT, SQ>), gr, bl, 0, st, g, r, P0, P1, q, x, s, partial, p.nchunk, p.zc, p.tiles_x, tiles, rq, fin);
-    else hipLaunchKernelGGL((k_cg_A<RY, NW, false, PF, NT, SQ>), gr, bl, 0, st, g, r, P0, P1, q, x, s, partial, p.nchunk, p.zc, p.tiles_x, tiles, rq, fin);
+    if (jac) hipLaunchKernelGGL((k_cg_A<RY, NW, true, PF, NT, SQ>), gr, bl, 0, st, g, r, P, q, x, s, partial, p.nchunk, p.zc, p.tiles_x, tiles, rq, fin);
+    else hipLaunchKernelGGL((k_cg_A<RY, NW, false, PF, NT, SQ>), gr, bl, 0, st, g, r, P, q, x, s, partial, p.nchunk, p.zc, p.tiles_x, tiles, rq, fin);
   }
 }
 template <int RY, int NW, int PF, int NT>
-static void launch_cg_A_t(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const double *r, double *P0, double *P1, double *q, double *x, KspScal *s, double *partial, const FinCtx &fin)
+static void launch_cg_A_t(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const double *r, const DirRing &P, double *q, double *x, KspScal *s, double *partial, const FinCtx &fin)
 {
 #ifdef FL_KBENCH_VARIANTS
   if (p.sq) {  // variant 2: q stored
-    launch_cg_A_q<RY, NW, PF, NT, true>(st, g, jac, p, r, P0, P1, q, x, s, partial, fin);
+    launch_cg_A_q<RY, NW, PF, NT, true>(st, g, jac, p, r, P, q, x, s, partial, fin);
     return;
   }
 #endif
-  launch_cg_A_q<RY, NW, PF, NT, false>(st, g, jac, p, r, P0, P1, q, x, s, partial, fin);
+  launch_cg_A_q<RY, NW, PF, NT, false>(st, g, jac, p, r, P, q, x, s, partial, fin);
 }
 template <int RY, int NW>
-static void launch_cg_A_v(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const double *r, double *P0, double *P1, double *q, double *x, KspScal *s, double *partial, const FinCtx &fin)
+static void launch_cg_A_v(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const double *r, const DirRing &P, double *q, double *x, KspScal *s, double *partial, const FinCtx &fin)
 {
 #ifdef FL_KBENCH_VARIANTS  // the whole sweep space of tools/kbench.py (build with -DFL_KBENCH_VARIANTS)
   switch (p.pf * 10 + p.nt) {
-  case 0: launch_cg_A_t<RY, NW, 0, 0>(st, g, jac, p, r, P0, P1, q, x, s, partial, fin); return;
-  case 1: launch_cg_A_t<RY, NW, 0, 1>(st, g, jac, p, r, P0, P1, q, x, s, partial, fin); return;
-  case 2: launch_cg_A_t<RY, NW, 0, 2>(st, g, jac, p, r, P0, P1, q, x, s, partial, fin); return;
-  case 10: launch_cg_A_t<RY, NW, 1, 0>(st, g, jac, p, r, P0, P1, q, x, s, partial, fin); return;
-  case 11: launch_cg_A_t<RY, NW, 1, 1>(st, g, jac, p, r, P0, P1, q, x, s, partial, fin); return;
+  case 0: launch_cg_A_t<RY, NW, 0, 0>(st, g, jac, p, r, P, q, x, s, partial, fin); return;
+  case 1: launch_cg_A_t<RY, NW, 0, 1>(st, g, jac, p, r, P, q, x, s, partial, fin); return;
+  case 2: launch_cg_A_t<RY, NW, 0, 2>(st, g, jac, p, r, P, q, x, s, partial, fin); return;
+  case 10: launch_cg_A_t<RY, NW, 1, 0>(st, g, jac, p, r, P, q, x, s, partial, fin); return;
+  case 11: launch_cg_A_t<RY, NW, 1, 1>(st, g, jac, p, r, P, q, x, s, partial, fin); return;
   default: break;
   }
 #endif
-  launch_cg_A_t<RY, NW, 1, 2>(st, g, jac, p, r, P0, P1, q, x, s, partial, fin);  // the shipped variant
+  launch_cg_A_t<RY, NW, 1, 2>(st, g, jac, p, r, P, q, x, s, partial, fin);  // the shipped variant
 }
-void launch_cg_A(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const double *r, double *P0, double *P1, double *q, double *x, KspScal *s, double *partial, unsigned *counter, double *hist, int nhist, double *sums)
+void launch_cg_A(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const double *r, const DirRing &P, double *q, double *x, KspScal *s, double *partial, unsigned *counter, double *hist, int nhist, double *sums)
 {
   FinCtx fin;
   fin.sums    = sums;
@@ -1864,12 +1902,12 @@ void launch_cg_A(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const
   fin.enabled = counter != nullptr;
   switch (p.ry * 10 + p.nw) {
 #ifdef FL_KBENCH_VARIANTS
-  case 48: launch_cg_A_v<4, 8>(st, g, jac, p, r, P0, P1, q, x, s, partial, fin); break;
-  case 44: launch_cg_A_v<4, 4>(st, g, jac, p, r, P0, P1, q, x, s, partial, fin); break;
+  case 48: launch_cg_A_v<4, 8>(st, g, jac, p, r, P, q, x, s, partial, fin); break;
+  case 44: launch_cg_A_v<4, 4>(st, g, jac, p, r, P, q, x, s, partial, fin); break;
 #endif
-  case 28: launch_cg_A_v<2, 8>(st, g, jac, p, r, P0, P1, q, x, s, partial, fin); break;
-  case 24: launch_cg_A_v<2, 4>(st, g, jac, p, r, P0, P1, q, x, s, partial, fin); break;
-  default: launch_cg_A_v<1, 4>(st, g, jac, p, r, P0, P1, q, x, s, partial, fin); break;
+  case 28: launch_cg_A_v<2, 8>(st, g, jac, p, r, P, q, x, s, partial, fin); break;
+  case 24: launch_cg_A_v<2, 4>(st, g, jac, p, r, P, q, x, s, partial, fin); break;
+  default: launch_cg_A_v<1, 4>(st, g, jac, p, r, P, q, x, s, partial, fin); break;
   }
 }
 
@@ -1904,25 +1942,37 @@ void launch_cg_B(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const
 #endif
 }
 
-// k_cg_Bq on the tiling of k_cg_A (plan_cg_A).  xmode: 0 no x-update, 1 x += alpha p', 2 the two updates owed on odd iterations
-template <int RY, int NW, int XM>
-static void launch_cg_Bq_x(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const double *P0, const double *P1, double *r, double *x, KspScal *s, double *partial, int stride, const FinCtx &fin)
+// k_cg_Bq on the tiling of k_cg_A (plan_cg_A).  xu: x-updates applied (0 none, 1 x += alpha p', K the K owed on every K-th iteration of a
+// ring of K direction buffers, K = 2, 3, 4 or 8); xz: the first of those launches in a solve (x = 0 is not read)
+template <int RY, int NW, int XU, bool XZ>
+static void launch_cg_Bq_x(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const DirRing &P, double *r, double *x, KspScal *s, double *partial, int stride, const FinCtx &fin)
 {
   const int  tiles = p.tiles_x * p.tiles_y;
   const dim3 gr(p.nblocks), bl(64 * NW);
-  if (p.probe) hipLaunchKernelGGL((k_cg_Bq_probe<RY, NW, true, 2, XM>), gr, bl, 0, st, g, P0, P1, r, x, s, partial, stride, p.nchunk, p.zc, p.tiles_x, tiles, p.remap, fin);
-  else if (jac) hipLaunchKernelGGL((k_cg_Bq<RY, NW, true, 2, XM>), gr, bl, 0, st, g, P0, P1, r, x, s, partial, stride, p.nchunk, p.zc, p.tiles_x, tiles, p.remap, fin);
-  else hipLaunchKernelGGL((k_cg_Bq<RY, NW, false, 2, XM>), gr, bl, 0, st, g, P0, P1, r, x, s, partial, stride, p.nchunk, p.zc, p.tiles_x, tiles, p.remap, fin);
+  if (p.probe) hipLaunchKernelGGL((k_cg_Bq_probe<RY, NW, true, 2, XU, XZ>), gr, bl, 0, st, g, P, r, x, s, partial, stride, p.nchunk, p.zc, p.tiles_x, tiles, p.remap, fin);
+  else if (jac) hipLaunchKernelGGL((k_cg_Bq<RY, NW, true, 2, XU, XZ>), gr, bl, 0, st, g, P, r, x, s, partial, stride, p.nchunk, p.zc, p.tiles_x, tiles, p.remap, fin);
+  else hipLaunchKernelGGL((k_cg_Bq<RY, NW, false, 2, XU, XZ>), gr, bl, 0, st, g, P, r, x, s, partial, stride, p.nchunk, p.zc, p.tiles_x, tiles, p.remap, fin);
+}
+template <int RY, int NW, int XU>
+static void launch_cg_Bq_z(hipStream_t st, const GridP &g, bool jac, const PlanA &p, bool xz, const DirRing &P, double *r, double *x, KspScal *s, double *partial, int stride, const FinCtx &fin)
+{
+  if (xz) launch_cg_Bq_x<RY, NW, XU, true>(st, g, jac, p, P, r, x, s, partial, stride, fin);
+  else launch_cg_Bq_x<RY, NW, XU, false>(st, g, jac, p, P, r, x, s, partial, stride, fin);
 }
 template <int RY, int NW>
-static void launch_cg_Bq_t(hipStream_t st, const GridP &g, bool jac, const PlanA &p, int xmode, const double *P0, const double *P1, double *r, double *x, KspScal *s, double *partial, int stride, const FinCtx &fin)
+static void launch_cg_Bq_t(hipStream_t st, const GridP &g, bool jac, const PlanA &p, int xu, bool xz, const DirRing &P, double *r, double *x, KspScal *s, double *partial, int stride, const FinCtx &fin)
 {
-  if (xmode == 3) launch_cg_Bq_x<RY, NW, 3>(st, g, jac, p, P0, P1, r, x, s, partial, stride, fin);
-  else if (xmode == 2) launch_cg_Bq_x<RY, NW, 2>(st, g, jac, p, P0, P1, r, x, s, partial, stride, fin);
-  else if (xmode == 1) launch_cg_Bq_x<RY, NW, 1>(st, g, jac, p, P0, P1, r, x, s, partial, stride, fin);
-  else launch_cg_Bq_x<RY, NW, 0>(st, g, jac, p, P0, P1, r, x, s, partial, stride, fin);
+  switch (xu) {
+  case 8: launch_cg_Bq_z<RY, NW, 8>(st, g, jac, p, xz, P, r, x, s, partial, stride, fin); break;
+  case 4: launch_cg_Bq_z<RY, NW, 4>(st, g, jac, p, xz, P, r, x, s, partial, stride, fin); break;
+  case 3: launch_cg_Bq_z<RY, NW, 3>(st, g, jac, p, xz, P, r, x, s, partial, stride, fin); break;
+  case 2: launch_cg_Bq_z<RY, NW, 2>(st, g, jac, p, xz, P, r, x, s, partial, stride, fin); break;
+  case 1: launch_cg_Bq_x<RY, NW, 1, false>(st, g, jac, p, P, r, x, s, partial, stride, fin); break;
+  default: launch_cg_Bq_x<RY, NW, 0, false>(st, g, jac, p, P, r, x, s, partial, stride, fin); break;
+  }
 }
-void launch_cg_Bq(hipStream_t st, const GridP &g, bool jac, const PlanA &p, int xmode, const double *P0, const double *P1, double *r, double *x, KspScal *s, double *partial, int stride, unsigned *counter, double *hist,
+bool cg_xdepth_ok(int k) { return k == 2 || k == 3 || k == 4 || k == 8; }
+void launch_cg_Bq(hipStream_t st, const GridP &g, bool jac, const PlanA &p, int xu, bool xz, const DirRing &P, double *r, double *x, KspScal *s, double *partial, int stride, unsigned *counter, double *hist,
                   int nhist, double *sums)
 {
   FinCtx fin;
@@ -1932,9 +1982,9 @@ void launch_cg_Bq(hipStream_t st, const GridP &g, bool jac, const PlanA &p, int 
   fin.nhist   = nhist;
   fin.enabled = counter != nullptr;
   switch (p.ry * 10 + p.nw) {
-  case 28: launch_cg_Bq_t<2, 8>(st, g, jac, p, xmode, P0, P1, r, x, s, partial, stride, fin); break;
-  case 24: launch_cg_Bq_t<2, 4>(st, g, jac, p, xmode, P0, P1, r, x, s, partial, stride, fin); break;
-  default: launch_cg_Bq_t<1, 4>(st, g, jac, p, xmode, P0, P1, r, x, s, partial, stride, fin); break;
+  case 28: launch_cg_Bq_t<2, 8>(st, g, jac, p, xu, xz, P, r, x, s, partial, stride, fin); break;
+  case 24: launch_cg_Bq_t<2, 4>(st, g, jac, p, xu, xz, P, r, x, s, partial, stride, fin); break;
+  default: launch_cg_Bq_t<1, 4>(st, g, jac, p, xu, xz, P, r, x, s, partial, stride, fin); break;
   }
 }
 

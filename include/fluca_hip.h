@@ -203,8 +203,11 @@ int fl_vec_maxpy(fl_poisson *h, int64_t n, double *x_dev, const double *alphas, 
  *                >= 256 MiB runs the placement search of fl_poisson_tune_placement by itself (about 0.15 s, once per handle; worth
  *                1 - 2 % of the CG iteration rate at 512^3).  A failure inside the search never fails the solve: plain allocations.
  *                "placement_vmm" (1): its arenas live in chunk-mapped virtual memory; "placement_verbose" (0): it narrates on stderr.
- *   "cg_xbatch"  1 (default) = the CG solver updates x every second iteration (both updates of the pair at once, while the older
- *                direction is still in its buffer); 0 = one update per iteration.  The same x bit for bit.
+ *   "cg_xbatch"  1 (default) = the CG solver updates x every cg_xdepth-th iteration (all updates of the group at once, while the older
+ *                directions are still in their buffers); 0 = one update per iteration.  The same x bit for bit.
+ *   "cg_xdepth"  4 (default) = direction buffers of the Jacobi-PCG ring, i.e. iterations per x-update with cg_xbatch = 1: 2, 3, 4 or 8
+ *                (another value fails the solve with FL_ERR_ARG_OUTOFRANGE).  x costs 8 (K - 1) + 16 B/cell per K iterations; the ring
+ *                holds K - 2 more padded vectors than two.  Several ranks and the stored-q variants keep K = 2.
  *   "mg_prolong" 1 (default) = tri-linear prolongation of the FL_PC_MG cycle; 0 = piecewise constant.  (This one and the next change the
  *                preconditioner, i.e. iteration counts -- not the converged answer.)
  *   "mg_flexible" 1 (default) = the CG around the FL_PC_MG cycle forms beta in the Polak-Ribiere way (flexible CG, KSPFCG with

@@ -50,18 +50,21 @@ for k in sorted(f):
               "B_per_cell": round((fb + wb) / N, 2), "rocprof_avg_ms_512cubed_launches": round(statistics.mean(big), 4) if big else None,
               "rocprof_median_ms": round(statistics.median(big), 4) if big else None, "rocprof_launches": len(big)}
 json.dump(out, open(os.path.join(ROOT, "profiles", f"{tag}_pmc_summary.json"), "w"), indent=1)
-# k_cg_Bq alternates between two instantiations (even iterations: r-update only; odd ones: + both x-updates): the per-launch figure
-# quoted by bench.py is their mean
-bq = [out[k] for k in ("fl::k_cg_Bq<2, 8, true, 2, 0>", "fl::k_cg_Bq<2, 8, true, 2, 2>") if k in out]
-if len(bq) == 2:
-    out["fl::k_cg_Bq (mean of the even- and odd-iteration launches)"] = {
-        "fetch_GB": round((bq[0]["fetch_GB"] + bq[1]["fetch_GB"]) / 2, 3), "write_GB": round((bq[0]["write_GB"] + bq[1]["write_GB"]) / 2, 3),
-        "hbm_bytes_per_launch": (bq[0]["hbm_bytes_per_launch"] + bq[1]["hbm_bytes_per_launch"]) / 2,
-        "B_per_cell": round((bq[0]["B_per_cell"] + bq[1]["B_per_cell"]) / 2, 2),
-        "rocprof_avg_ms_512cubed_launches": round((bq[0]["rocprof_avg_ms_512cubed_launches"] + bq[1]["rocprof_avg_ms_512cubed_launches"]) / 2, 4)}
+# k_cg_Bq runs in two instantiations: r-update only (x-updates 0), and on every K-th iteration of a ring of K direction buffers + the K
+# x-updates owed (k_cg_Bq<..., K, false>; <..., K, true> is the first of a solve).  The per-launch figure quoted by bench.py is their mean
+# weighted as in a solve: ((K - 1) plain + 1 flushing) / K.
+BQ0 = "fl::k_cg_Bq<2, 8, true, 2, 0, false>"
+BQK = [k for k in out if k.startswith("fl::k_cg_Bq<2, 8, true, 2, ") and k.endswith(", false>") and k != BQ0]
+BQ_MEAN = "fl::k_cg_Bq (mean over a ring of K iterations: K - 1 plain launches, one with the x-updates)"
+if BQ0 in out and len(BQK) == 1:
+    K = int(BQK[0].split(", ")[-2])
+    bq = [out[BQ0], out[BQK[0]]]
+    mean = lambda f, nd: round(((K - 1) * bq[0][f] + bq[1][f]) / K, nd) if nd is not None else ((K - 1) * bq[0][f] + bq[1][f]) / K
+    out[BQ_MEAN] = {"ring_depth": K, "fetch_GB": mean("fetch_GB", 3), "write_GB": mean("write_GB", 3), "hbm_bytes_per_launch": mean("hbm_bytes_per_launch", None),
+                    "B_per_cell": mean("B_per_cell", 2), "rocprof_avg_ms_512cubed_launches": mean("rocprof_avg_ms_512cubed_launches", 4)}
     json.dump(out, open(os.path.join(ROOT, "profiles", f"{tag}_pmc_summary.json"), "w"), indent=1)
 for k, name in (("fl::k_cg_A<2, 8, true, 1, 2, false>", "pmc_k_cg_A.json"), ("fl::k_cheb2<2, 8, true, 2, false, 0>", "pmc_k_cheb2.json"),   # the two-step sweep of config 3 (Z = 0; round 5 added the template argument)
-                ("fl::k_cg_Bq (mean of the even- and odd-iteration launches)", "pmc_k_cg_Bq.json")):
+                (BQ_MEAN, "pmc_k_cg_Bq.json")):
     if k in out:
         o = dict(out[k])
         key = name[len("pmc_"):-len(".json")]
@@ -76,7 +79,7 @@ for k, name in (("fl::k_cg_A<2, 8, true, 1, 2, false>", "pmc_k_cg_A.json"), ("fl
 for wl, lo, hi, cells in (("c2_256", 0.09, 0.16, 256 ** 3), ("c5_block", 0.45, 0.55, 512 * 512 * 256)):
     rec = {}
     for k in sorted(f):
-        if not ("k_cg_A<2, 8" in k or "k_cg_Bq<2, 8, true, 2, 0>" in k or "k_cg_Bq<2, 8, true, 2, 2>" in k):
+        if not ("k_cg_A<2, 8" in k or k == BQ0 or k in BQK):
             continue
         mf, mw = max(f[k]), max(w.get(k, [0.0]))
         fv, wv = [v for v in f[k] if lo * mf <= v <= hi * mf], [v for v in w.get(k, []) if lo * mw <= v <= hi * mw]
@@ -86,9 +89,10 @@ for wl, lo, hi, cells in (("c2_256", 0.09, 0.16, 256 ** 3), ("c5_block", 0.45, 0
             rec[k]["B_per_cell"] = round(rec[k]["hbm_bytes_per_launch"] / cells, 2)
     a = [v for k, v in rec.items() if "k_cg_A" in k]
     b = [v for k, v in rec.items() if "k_cg_Bq" in k]
-    if len(a) == 1 and len(b) == 2:
-        o = {"workload": wl, "cells": cells, "k_cg_A": a[0]["hbm_bytes_per_launch"], "k_cg_Bq": (b[0]["hbm_bytes_per_launch"] + b[1]["hbm_bytes_per_launch"]) / 2,
-             "B_per_cell_per_iteration": round((a[0]["hbm_bytes_per_launch"] + (b[0]["hbm_bytes_per_launch"] + b[1]["hbm_bytes_per_launch"]) / 2) / cells, 2),
+    if len(a) == 1 and len(b) == 2 and BQ0 in rec:
+        bq = ((K - 1) * rec[BQ0]["hbm_bytes_per_launch"] + rec[BQK[0]]["hbm_bytes_per_launch"]) / K
+        o = {"workload": wl, "cells": cells, "k_cg_A": a[0]["hbm_bytes_per_launch"], "k_cg_Bq": bq,
+             "B_per_cell_per_iteration": round((a[0]["hbm_bytes_per_launch"] + bq) / cells, 2),
              "kernels": rec, "sources_at_profiling": {"k_cg_A": provenance.source_hashes("k_cg_A"), "k_cg_Bq": provenance.source_hashes("k_cg_Bq")},
              "source": f"the launches of this size inside the FETCH_SIZE / WRITE_SIZE passes of the bench command (tools/experiments/pmc_summary.py, {tag})"}
         json.dump(o, open(os.path.join(ROOT, "profiles", f"pmc_workload_{wl}.json"), "w"), indent=1)

@@ -14,11 +14,16 @@ def stretched(n, lo, hi, beta=1.3):
     return lo + (hi - lo) * (np.tanh(beta * (2 * s - 1)) / np.tanh(beta) + 1) / 2
 
 
+def stretched_faces(n, box=CAVITY_BOX):
+    """face coordinates of the non-uniform parity grids: stretched towards both ends of every axis, more strongly along y and z"""
+    return [stretched(n[d], box[d][0], box[d][1], 1.1 + 0.2 * d) for d in range(3)]
+
+
 def make_pair(n, bc, kappa=1e-3, box=CAVITY_BOX, nonuniform=False):
     """-> (fluca_amd.Poisson, oracle Grid) on the same grid / BCs / kappa"""
     from fluca_amd.poisson import Poisson
     if nonuniform:
-        xf = [stretched(n[d], box[d][0], box[d][1], 1.1 + 0.2 * d) for d in range(3)]
+        xf = stretched_faces(n, box)
         return Poisson(n, xf, bc, kappa), fo.Grid(n, xf, bc, kappa)
     return Poisson.uniform(n, box, bc, kappa), fo.Grid.uniform(n, box, bc, kappa)
 

@@ -4,7 +4,7 @@ the launchers) and the grids of the -m gpu regime tests that reach each one.
 The kernels pick their tiling, z chunks and grid stride from the grid size, and the toy grids of the parity suite all land in the small plans.
 REGIMES names a grid per plan branch that the product runs at 256^3 - 512^3, made ragged on purpose (partial tiles, a short last z chunk, a
 grid stride that wraps), with the fields of the plans it must get.  tests/test_launch_regimes.py checks the table against the library on the
-CPU; tests/test_gpu_launch_regimes.py checks every kernel on these grids against the oracle."""
+CPU; tests/test_gpu_launch_regimes.py and tests/test_gpu_momentum_regimes.py check every kernel on these grids against the oracle."""
 import ctypes as C
 
 from oracle import fluca_oracle as fo
@@ -13,6 +13,7 @@ V, O, PER, SYM = fo.BC_VELOCITY, fo.BC_PRESSURE_OUTLET, fo.BC_PERIODIC, fo.BC_SY
 CAVITY = [V, V, V, V, SYM, V]            # null space
 CHANNEL = [V, O, V, V, PER, PER]         # outlet; the periodic z seam crosses the z chunks
 XPER = [PER, PER, V, V, PER, PER]        # the periodic x seam joins the partial last tile to tile 0
+SLAB = [PER, PER, V, V, O, SYM]          # periodic x, walls in y, an outlet and a symmetry plane at the two z ends
 
 # fldbg_launch_plans' output, in order: <kernel>.<field>
 FIELDS = ["cg.ry", "cg.nw", "cg.tiles_x", "cg.tiles_y", "cg.nchunk", "cg.zc", "cg.nblocks",
@@ -60,6 +61,23 @@ def six_trips(p):
     return -(-p["six.items"] // (4 * p["six.nbx"]))
 
 
+def mom_tiles(p, n):
+    """128 x 8 tiles of the t2 tiling (k_mom3, k_mom2, k_mom_pw3) on an n block"""
+    return p["mom.t2x"] * -(-n[1] // 8)
+
+
+def mom_regime(p, n):
+    """the bound that set the z chunk count of the t2 tiling (fl_momentum_create): about 1024 blocks over the tiles ("tile", what 256^3 - 512^3 take:
+    long chunks) or chunks of at least 8 planes ("nz", what the toy grids of the parity suite take)"""
+    tiles = mom_tiles(p, n)
+    return "tile" if (1024 + tiles // 2) // tiles < max(1, n[2] // 8) else "nz"
+
+
+def mom_last_chunk(p, n):
+    """planes of the last z chunk of the t2 tiling"""
+    return n[2] - (p["mom.t2chunk"] - 1) * p["mom.t2zc"]
+
+
 class Regime:
     def __init__(self, name, n, bcs, expect, reaches):
         self.name, self.n, self.bcs, self.expect, self.reaches = name, tuple(n), bcs, expect, reaches
@@ -87,17 +105,42 @@ REGIMES = [
     Regime("schur_general", (300, 37, 40), [XPER],
            {"cg.regime": "small", "schur.per_xcd": 128, "schur.nseg": 5, "schur.fixed_seg": 0, "schur.band": 5},
            "schur: 128 blocks per XCD, a wave's x segment changes from row to row"),
+    # the t2 tiling of the momentum kernels (k_mom3, k_mom2, k_mom_pw3): 128 x 8 tiles, z chunks, XCD-contiguous block order when the blocks
+    # are a multiple of 8.  tests/test_gpu_momentum_regimes.py runs them on these grids, stretched in all three axes.
+    Regime("mom_long_chunks", (3, 505, 879), [CHANNEL],
+           {"mom.t2x": 1, "mom.t2chunk": 16, "mom.t2zc": 55, "mom.t2blocks": 1024},
+           "t2: the tile bound like 384^3 -- 64 tiles, 16 z chunks of 55 planes with a last one of 54, 1024 blocks so the XCD remap is on; "
+           "one x tile holds both x ends; a last y tile of 1 row; the periodic z seam crosses the chunks"),
+    Regime("mom_three_tiles", (257, 17, 71), [CAVITY, XPER],
+           {"mom.t2x": 3, "mom.t2chunk": 8, "mom.t2zc": 9, "mom.t2blocks": 72},
+           "t2: x tiles of 128 / 128 / 1 column and y tiles of 8 / 8 / 1 row, so one tile touches no block end; 8 z chunks of 9, the last 8; "
+           "72 blocks, remapped; the periodic x seam joins the 1-column tile to tile 0"),
+    Regime("mom_pairs_one_plane", (256, 41, 100), [CHANNEL],
+           {"mom.t2x": 2, "mom.t2chunk": 12, "mom.t2zc": 9, "mom.t2blocks": 144},
+           "t2: nx a multiple of 128 -- a full last x tile and 16-byte pair stores (flags & 2); 12 z chunks of 9 with a last chunk of one plane; "
+           "144 blocks, remapped; a last y tile of 1 row"),
+    Regime("mom_unmapped", (130, 37, 43), [CAVITY],
+           {"mom.t2x": 2, "mom.t2chunk": 5, "mom.t2zc": 9, "mom.t2blocks": 50},
+           "t2: 50 blocks, so the block order is not remapped; 5 z chunks of 9, the last 7; x tiles of 128 / 2 columns, a last y tile of 5 rows"),
+    Regime("mom_stored_one_plane", (300, 8, 100), [SLAB],
+           {"mom.t2x": 3, "mom.t2chunk": 12, "mom.t2zc": 9, "mom.t2blocks": 36},
+           "t2 with ny = 8: one tile holds both y ends, so k_mom2 runs also for a state with v0; 12 z chunks of 9 with a last chunk of one plane; "
+           "36 blocks, not remapped; x tiles of 128 / 128 / 44"),
 ]
 BY_NAME = {r.name: r for r in REGIMES}
 
 # the shapes the product runs (512^3 bench, config 5's 512 x 512 x 256 blocks, the multigrid fine levels of 384^3 and 256^3): which plans they take
 PRODUCTION = {
     (512, 512, 512): {"cg.regime": "standard", "cg.nblocks": 256, "cg.nchunk": 2, "cheb2.nchunk": 2, "cheb2.clamp": 0, "six.nbx": 1024,
-                      "six.items": 131072, "schur.per_xcd": 128, "schur.fixed_seg": 1, "mom.t2chunk": 4},
+                      "six.items": 131072, "schur.per_xcd": 128, "schur.fixed_seg": 1, "mom.t2chunk": 4,
+                      "mom.t2x": 4, "mom.t2zc": 128, "mom.t2blocks": 1024},
     (512, 512, 256): {"cg.regime": "standard", "cg.nblocks": 256, "cg.nchunk": 2, "cheb2.nchunk": 2, "cheb2.clamp": 0, "six.nbx": 1024,
-                      "six.items": 65536, "schur.per_xcd": 128, "schur.fixed_seg": 1, "mom.t2chunk": 4},
+                      "six.items": 65536, "schur.per_xcd": 128, "schur.fixed_seg": 1, "mom.t2chunk": 4,
+                      "mom.t2x": 4, "mom.t2zc": 64, "mom.t2blocks": 1024},
     (384, 384, 384): {"cg.regime": "mid", "cg.nblocks": 216, "cg.nchunk": 3, "cheb2.nchunk": 3, "cheb2.clamp": 1, "six.nbx": 1026,
-                      "six.items": 55296, "schur.per_xcd": 128, "schur.fixed_seg": 0, "mom.t2chunk": 7},
+                      "six.items": 55296, "schur.per_xcd": 128, "schur.fixed_seg": 0, "mom.t2chunk": 7,
+                      "mom.t2x": 3, "mom.t2zc": 55, "mom.t2blocks": 1008},
     (256, 256, 256): {"cg.regime": "mid", "cg.nblocks": 256, "cg.nchunk": 8, "cheb2.nchunk": 8, "cheb2.clamp": 0, "six.nbx": 1024,
-                      "six.items": 16384, "schur.per_xcd": 128, "schur.fixed_seg": 1, "mom.t2chunk": 16},
+                      "six.items": 16384, "schur.per_xcd": 128, "schur.fixed_seg": 1, "mom.t2chunk": 16,
+                      "mom.t2x": 2, "mom.t2zc": 16, "mom.t2blocks": 1024},
 }

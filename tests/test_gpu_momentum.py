@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from oracle import fluca_oracle as fo
-from tests.gpu_common import CAVITY, CAVITY_BOX, O, PER, SYM, V, dev, host, stretched
+from tests.gpu_common import CAVITY, CAVITY_BOX, O, PER, SYM, V, dev, host, stretched_faces
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +24,7 @@ def _pair(n, bc, nonuni):
     from fluca_amd.poisson import Momentum, Poisson
     box = CAVITY_BOX
     if nonuni:
-        xf = [stretched(n[d], box[d][0], box[d][1], 1.1 + 0.2 * d) for d in range(3)]
+        xf = stretched_faces(n, box)
         P, g = Poisson(n, xf, bc, 1e-3), fo.Grid(n, xf, bc, 1e-3)
     else:
         P, g = Poisson.uniform(n, box, bc, 1e-3), fo.Grid.uniform(n, box, bc, 1e-3)

@@ -1,10 +1,12 @@
 """The regime table of tests/launch_regimes.py against the plans the library computes (fldbg_launch_plans: host arithmetic, no GPU).
 
-If a threshold of a plan moves, these tests name the regime whose grid no longer reaches its branch: the -m gpu module
-tests/test_gpu_launch_regimes.py then checks another plan than the one it was written for, and the table must be re-aimed."""
+If a threshold of a plan moves, these tests name the regime whose grid no longer reaches its branch: the -m gpu modules
+tests/test_gpu_launch_regimes.py and tests/test_gpu_momentum_regimes.py then check another plan than the one they were written for, and the
+table must be re-aimed."""
 import pytest
 
-from tests.launch_regimes import BY_NAME, FIELDS, PRODUCTION, REGIMES, launch_plans, six_trips
+from tests.launch_regimes import (BY_NAME, FIELDS, PRODUCTION, REGIMES, launch_plans, mom_last_chunk, mom_regime, mom_tiles,
+                                  six_trips)
 
 
 @pytest.mark.parametrize("reg", REGIMES, ids=[r.name for r in REGIMES])
@@ -36,6 +38,83 @@ def test_table_covers_every_branch():
     assert any(bc == CHANNEL and plans[n]["cg.nchunk"] > 1 for n, bc in bcs)
     assert any(bc == XPER and BY_NAME[n].n[0] % 128 != 0 and plans[n]["cg.nw"] == 8 for n, bc in bcs)
     assert any(bc == CAVITY for _, bc in bcs)
+
+
+def test_table_covers_every_branch_of_the_momentum_tiling():
+    """the t2 tiling of k_mom3 / k_mom2 / k_mom_pw3 (fl_momentum_create): both bounds of the chunk count, the seams and ragged edges a tile walk
+    gets wrong, and the block order with and without the XCD remap"""
+    from tests.launch_regimes import CHANNEL
+    mom = {r.name: (r, launch_plans(r.n)) for r in REGIMES if any(k.startswith("mom.") for k in r.expect)}
+    # the chunk count comes from the bound mom_regime names: about 1024 blocks over the tiles, or chunks of at least 8 planes
+    for name, (r, p) in mom.items():
+        nz, reg, tiles = r.n[2], mom_regime(p, r.n), mom_tiles(p, r.n)
+        nc = min((1024 + tiles // 2) // tiles if reg == "tile" else max(1, nz // 8), nz)
+        assert p["mom.t2zc"] == -(-nz // nc) and p["mom.t2blocks"] == tiles * p["mom.t2chunk"], \
+            f"{name} {r.n}: the t2 chunks no longer follow the {reg} bound ({r.reaches}): {nc} chunks wanted, got {p['mom.t2chunk']} of {p['mom.t2zc']}"
+    assert {mom_regime(p, r.n) for r, p in mom.values()} == {"tile", "nz"}
+    assert all(mom_regime(launch_plans(n), n) == "tile" for n in PRODUCTION)        # what 256^3 - 512^3 take
+    covered = {
+        # long chunks like 256^3 - 512^3, the last one shorter
+        "t2zc >= 32, short last chunk": [k for k, (r, p) in mom.items() if p["mom.t2zc"] >= 32 and mom_last_chunk(p, r.n) < p["mom.t2zc"]],
+        # a last chunk of one plane: the pipeline's k+1 / k+2 planes are both past the chunk, for k_mom3 (ny > 8) and for k_mom2 (ny <= 8)
+        "last chunk of one plane, ny > 8": [k for k, (r, p) in mom.items() if p["mom.t2chunk"] > 1 and mom_last_chunk(p, r.n) == 1 and r.n[1] > 8],
+        "last chunk of one plane, ny <= 8": [k for k, (r, p) in mom.items() if p["mom.t2chunk"] > 1 and mom_last_chunk(p, r.n) == 1 and r.n[1] <= 8],
+        # xcd_remap (flags & 1) on and off, each over several chunks
+        "XCD remap, several chunks": [k for k, (r, p) in mom.items() if p["mom.t2blocks"] % 8 == 0 and p["mom.t2chunk"] > 1],
+        "no XCD remap, several chunks": [k for k, (r, p) in mom.items() if p["mom.t2blocks"] % 8 != 0 and p["mom.t2chunk"] > 1],
+        # a full last x tile (16-byte pair stores) and a last x tile of one odd column
+        "nx % 128 == 0": [k for k, (r, p) in mom.items() if r.n[0] % 128 == 0],
+        "last x tile of 1 column": [k for k, (r, p) in mom.items() if r.n[0] % 128 == 1 and p["mom.t2x"] > 1],
+        "last y tile of 1 row, ny > 8": [k for k, (r, p) in mom.items() if r.n[1] % 8 == 1 and r.n[1] > 8],
+        # the periodic z seam of the channel across several chunks
+        "CHANNEL, several chunks": [k for k, (r, p) in mom.items() if CHANNEL in r.bcs and p["mom.t2chunk"] > 1],
+    }
+    missing = [what for what, names in covered.items() if not names]
+    assert not missing, f"no momentum regime reaches: {missing}"
+
+
+MOM = [r for r in REGIMES if r.name.startswith("mom_")]
+
+
+@pytest.mark.parametrize("reg", MOM, ids=[r.name for r in MOM])
+def test_momentum_regime_grid_tells_its_columns_rows_and_planes_apart(reg):
+    """tests/test_gpu_momentum_regimes.py runs the momentum regimes stretched in all three axes.  There the 1-D rows of a cell -- the viscous row
+    and the B rows of its low face -- differ from those of the cell a tiling slip would read instead (the next one; one x tile, y tile or z chunk
+    further) by far more than the parity tolerance of 2e-13: a kernel that takes the numbers of the wrong column, row or plane fails there.  On
+    the uniform grid the same slip reads the same numbers."""
+    import numpy as np
+
+    from oracle import fluca_oracle as fo
+    from tests.gpu_common import CAVITY_BOX, stretched_faces
+
+    def rows(g, d, c):
+        """[cell][offset -2..2] of the viscous rows and [cell][offset -2..1] of the B rows of the cells' low faces"""
+        lap, b = np.zeros((g.n[d], 5)), np.zeros((g.n[d], 4))
+        for i in range(g.n[d]):
+            for off, v in g.lap_row(d, i, c):
+                lap[i, off + 2] += v
+            for col, v in g.B_row(d, i, c):
+                b[i, col - i + 2] += v
+        return lap, b
+
+    def gap(r, s):
+        """per cell pair (i, i + s): how far apart their numbers are, relative to the largest of their kind"""
+        return np.max([np.abs(a[s:] - a[:-s]).max(axis=1) / np.abs(a).max() for a in r], axis=0)
+
+    p = launch_plans(reg.n)
+    for bc in reg.bcs:
+        grids = {"stretched": fo.Grid(reg.n, stretched_faces(reg.n), bc), "uniform": fo.Grid.uniform(reg.n, CAVITY_BOX, bc)}
+        for d, tile in enumerate((128, 8, p["mom.t2zc"])):
+            n = reg.n[d]
+            for c in range(3):
+                R = {k: rows(g, d, c) for k, g in grids.items()}
+                for s in {1, tile}:
+                    if s >= n:
+                        continue
+                    apart = gap(R["stretched"], s).min()
+                    assert apart >= 1e-7, (reg.name, bc, d, c, s, apart)
+                    if n - s >= 3:      # two inner cells that far apart: the uniform grid gives them the same numbers
+                        assert gap(R["uniform"], s)[1:-1].min() <= 1e-14, (reg.name, bc, d, c, s)
 
 
 @pytest.mark.parametrize("n", list(PRODUCTION), ids=["x".join(map(str, n)) for n in PRODUCTION])

@@ -335,6 +335,7 @@ struct fl_poisson {
   double *Pr[CG_XRING_MAX - 2] = {};  // CG: slots 2 .. of the direction ring beyond P0 / P1 (cg_xdepth > 2), created by the first solve that needs them
   double *cd1 = nullptr;  // second d buffer of the fused two-step Chebyshev kernel (fl_cheb2.hip)
   void   *sv_pack[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // packed 1-D rows of the fused DIAG / ROWSUM Schur product (fl_schur_var.hip; freed with h->tables)
+  double *sv_ring[12] = {};  // several ranks: [b] the ring of a^-1 received across boundary b, [6 + b] the plane sent across it (fl_schur_var.hip; freed with h->tables)
   double *rb = nullptr;   // where the three-step sweep from a zero guess writes the updated right-hand side; swaps roles with r afterwards
   std::vector<void *> vec_bases;
   void               *slab = nullptr;
@@ -468,6 +469,8 @@ struct SchurVarT {
   const int    *c0[3];
 };
 }  // namespace fl
+bool      fl_schur_var_usable(const fl_poisson *h);          // the fused product runs on this handle (one rank, or several with the two-deep layout)
+int       fl_schur_var_fill_ghosts(fl_poisson *h, double *p_pad);  // the ghost layers of p the fused product reads (one rank: fl_fill_ghosts)
 int       fl_schur_var_apply_fused(fl_poisson *h, const fl::SchurVarT &t, const double *ainv, const double *p_pad, double *y);
 // the launch of k_schur_var: 8 * per_xcd blocks of four waves; fixed_seg: every wave keeps one x segment of 64 cells for all its rows
 struct SchurVarPlan {

@@ -1652,10 +1652,10 @@ int schur_apply_var(fl_momentum *m, const double *p, double *y)
 {
   fl_poisson   *h = m->p;
   const int64_t N = h->ncell, n3 = 3 * N;
-  if (!h->multi && knob(K_schur_var_fused) != 0) {  // one pass over p and a^-1 (fl_schur_var.hip); several ranks keep the composition below
+  if (knob(K_schur_var_fused) != 0 && fl_schur_var_usable(h)) {  // one pass over p and a^-1 (fl_schur_var.hip), on one rank or several
     FL_CHK(fl_ensure_vec(h, &h->w0));
     launch_pad_copy(h->stream, h->g, p, h->w0);
-    FL_CHK(fl_fill_ghosts(h, h->w0));
+    FL_CHK(fl_schur_var_fill_ghosts(h, h->w0));
     SchurVarT t;
     for (int d = 0; d < 3; ++d) {
       t.w0[d] = m->ft.w0[0][d];

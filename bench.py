@@ -8,11 +8,14 @@ reference's -cart_ranks_{x,y,z}).  Right-hand side: SURVEY 8d micro-benchmark b 
 iteration count (rtol = atol = 0), inputs resident in HBM before the timed region.
 
 One JSON line on rank 0.  value = (cells of the whole job / 512^3) * K / seconds  ==  iterations/s of a 512^3 grid at N=1.
-At N = 1 the line also carries "configs": driver-timed lines for the other single-GPU configurations of BASELINE.json (C2 256^3
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the headline, its roofline from the timed steps'
+own HIP events and the committed counter passes, and at N > 1 the per-rank and wire records; "cpu_baseline" is null.
+With --full (one GPU) the line also carries "configs": driver-timed lines for the other single-GPU configurations of BASELINE.json (C2 256^3
 cavity CG, C3 512^3 channel Chebyshev-Jacobi sweeps, C4 512^3 with the IBM kernels on an immersed sphere), each with its own
 roofline object, "C1" (config 1: the 64^3 cavity's CPU KSP CG + Jacobi, iterations / seconds / cores), "C5_rank_rehearsal" (one rank's share of config 5
 without the halo exchange, with its parity against the oracle's assembled block), "flow_step" (a whole 512^3 time step, and the velocity-field parity of two
-steps at 128^3), and "value_unplaced": the same K steps on plainly allocated vectors (see "placement" in include/fluca_hip.h).
+steps at 128^3), "value_unplaced": the same K steps on plainly allocated vectors (see "placement" in include/fluca_hip.h), "time_to_solution",
+"cpu_baseline" and the box's measured streaming rates under "roofline"; --skip-extras, --skip-configs and --skip-cpu leave parts of that out.
 For N > 1 the halo transport is RCCL; if RCCL cannot be initialised the run FAILS (a host-staged curve would be worthless) --
 the host-staged rehearsal has to be asked for with --transport host.
 --dump-outputs DIR writes what the timed solve returned (x, sampled at fixed cells on large grids, and the residual norms) as .npy files: the
@@ -730,13 +733,17 @@ def main():
                          "iteration weigh as much as its kernels)")
     ap.add_argument("--cpu-cells", type=int, default=256)
     ap.add_argument("--cpu-iters", type=int, default=500, help="iterations of the CPU sample (about 10 s on 16 cores at 256^3)")
-    ap.add_argument("--skip-cpu", action="store_true")
-    ap.add_argument("--skip-extras", action="store_true", help="skip the time-to-solution comparison after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: after the headline, everything else the bench measures and checks (time to solution, the rate on plainly "
+                         "allocated vectors, the other configurations and their oracle parity, the streaming rates, the CPU baseline); a "
+                         "plain run prints the line right after the timed steps")
+    ap.add_argument("--skip-cpu", action="store_true", help="with --full: skip the CPU baseline and the oracle parity of the configurations")
+    ap.add_argument("--skip-extras", action="store_true", help="with --full: skip the time-to-solution comparison, the unplaced rate and the streaming rates")
     ap.add_argument("--placement", choices=["auto", "off"], default="auto",
                     help="auto: the library carves the solver vectors out of one arena where a probe of k_cg_A runs fastest (its "
                          "default); off: one plain allocation per vector")
     ap.add_argument("--placement-tries", type=int, default=None, help="(accepted for compatibility, ignored: placement is no longer a lottery)")
-    ap.add_argument("--skip-configs", action="store_true", help="skip the C2 / C3 / C4 lines after the timed region")
+    ap.add_argument("--skip-configs", action="store_true", help="with --full: skip the lines of the other configurations after the timed region")
     ap.add_argument("--transport", choices=["rccl", "host"], default="rccl",
                     help="halo transport for N > 1: RCCL Send/Recv (production) or the host-staged gloo callbacks "
                          "(rehearsal on a box with fewer GPUs than ranks; never used for a reported number)")
@@ -882,7 +889,8 @@ def main():
         "hbm_bytes_held": P.vector_bytes(),
         "roofline": cg_roofline(info, P.ncell, args.variant, dt / args.steps * 1e3, traffic),
     }
-    if world == 1 and not args.skip_extras:
+    full = world == 1 and args.full       # everything below the headline; a plain run prints the line now
+    if full and not args.skip_extras:
         # not part of the metric: what the iteration rate buys -- time to a converged pressure with the Jacobi preconditioner of
         # the metric and with the multigrid preconditioner (FL_PC_MG), same right-hand side, outside the timed region
         try:
@@ -894,7 +902,7 @@ def main():
             out["time_to_solution"] = tts
         except Exception as e:  # noqa: BLE001
             out["time_to_solution"] = {"error": repr(e)}
-    if world == 1 and not args.skip_extras and args.placement == "auto":
+    if full and not args.skip_extras and args.placement == "auto":
         # the same K steps on plainly allocated vectors (what the library did before the placement step existed)
         try:
             capi.check(capi.lib.fl_tuning_set(b"placement", 0))
@@ -918,7 +926,7 @@ def main():
             out["value_unplaced"] = {"error": repr(e)}
         finally:
             capi.check(capi.lib.fl_tuning_set(b"placement", 1))
-    if world == 1 and not args.skip_configs:
+    if full and not args.skip_configs:
         P.close()
         del b, x, pstar
         torch.cuda.empty_cache()
@@ -926,7 +934,7 @@ def main():
             out["configs"] = other_configs(stream, parity=not args.skip_cpu)
         except Exception as e:  # noqa: BLE001
             out["configs"] = {"error": repr(e)}
-    if world == 1 and not args.skip_extras:
+    if full and not args.skip_extras:
         # the attainable streaming rate on THIS box, reported beside the nominal peak: the library's own streaming kernels
         # (16 B per lane, non-temporal, grid-stride; tools/sbench.py) on 512^3-sized padded vectors -- a copy (1 read + 1 write stream)
         # and the 3 reads + 3 writes mix of the CG kernels
@@ -935,7 +943,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             out["roofline"]["measured_copy_GBps"] = None
             out["roofline"]["measured_copy_error"] = repr(e)
-    if rank == 0 and world == 1 and not args.skip_cpu:
+    if rank == 0 and full and not args.skip_cpu:
         out["cpu_baseline"] = cpu_baseline(args.cpu_cells, args.cpu_iters, args.cells if args.cells >= 512 else None, args.steps)
     elif rank == 0:
         out["cpu_baseline"] = None

@@ -23,7 +23,8 @@ def _line(out):
 
 
 def test_single_gpu_line_has_the_contract_keys():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cells", "64", "--steps", "20", "--warmup", "3", "--cpu-cells", "32", "--cpu-iters", "20", "--skip-configs"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cells", "64", "--steps", "20", "--warmup", "3", "--cpu-cells", "32", "--cpu-iters", "20", "--skip-configs",
+                          "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stdout + out.stderr
     d = _line(out)
     assert KEYS <= set(d)
@@ -44,6 +45,22 @@ def test_single_gpu_line_has_the_contract_keys():
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and "sample" in c and "petsc_cpu" in c
     assert c["parity_on_sample"]["iters_gpu"] == c["parity_on_sample"]["iters_cpu"] and c["parity_on_sample"]["rel_max_diff_x"] < 1e-9
     assert "workload" in d["config"] and "model" not in d["config"]
+
+
+def test_plain_line_is_the_headline_alone():
+    """Without --full the run times its steps and prints the line: the contract keys, the roofline of the timed steps, nothing measured after them."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cells", "64", "--steps", "20", "--warmup", "3"], capture_output=True, text=True,
+                         timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stdout + out.stderr
+    d = _line(out)
+    assert KEYS <= set(d)
+    assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 3 and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["value"] > 0 and abs(d["ms_per_step"] * d["value"] * (512 / 64) ** 3 / 1e3 - 1.0) < 1e-6
+    r = d["roofline"]
+    assert r["bound"] == "hbm" and 0 < r["frac"] <= 1.0 and len(r["kernels"]) == 2 and r["iteration"]["ms"] > 0
+    assert d["placement"]["mode"] == "auto" and d["hbm_bytes_held"] > 0
+    assert d["cpu_baseline"] is None
+    assert not {"configs", "time_to_solution", "value_unplaced"} & set(d) and "measured_copy_GBps" not in r
 
 
 def test_dumped_outputs_repeat_from_run_to_run(tmp_path):

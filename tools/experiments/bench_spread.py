@@ -3,7 +3,7 @@ import json
 import subprocess
 import sys
 
-out = subprocess.run([sys.executable, "bench.py", "--steps", "20", "--warmup", "5", "--skip-cpu", "--skip-configs"], capture_output=True, text=True).stdout
+out = subprocess.run([sys.executable, "bench.py", "--steps", "20", "--warmup", "5", "--full", "--skip-cpu", "--skip-configs"], capture_output=True, text=True).stdout
 d = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
 k = d["roofline"]["kernels"]
 print("value %.1f it/s  ms/step %.4f  unplaced %s  probe %.3f -> %.3f  k_cg_A %.4f k_cg_Bq %.4f  mg %.4f s" % (

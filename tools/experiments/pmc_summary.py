@@ -70,10 +70,10 @@ for k, name in (("fl::k_cg_A<2, 8, true, 1, 2, false>", "pmc_k_cg_A.json"), ("fl
         key = name[len("pmc_"):-len(".json")]
         o.update({"kernel_key": key, "sources_at_profiling": provenance.source_hashes(key)})
         o.update({"kernel": k, "fetch_bytes_corrected": o["fetch_GB"] * 1e9, "write_bytes": o["write_GB"] * 1e9,
-                  "source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over `python3 bench.py --steps 8 --warmup 2 --skip-cpu --skip-extras` "
-                            f"(tools/experiments/r0N_profile.sh, summarised by tools/experiments/pmc_summary.py, {tag}); FETCH_SIZE in KB doubled per MI355X_MICROARCH.md"})
+                  "source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over `python3 bench.py --steps 8 --warmup 2 --full --skip-cpu --skip-extras` "
+                            f"(tools/experiments/r0N_profile.sh, summarised by tools/experiments/pmc_summary.py, {tag}); FETCH_SIZE in KB doubled (on gfx950 it counts half the bytes of a coalesced streaming read)"})
         json.dump(o, open(os.path.join(ROOT, "profiles", name), "w"), indent=1)
-# the other sizes the same passes saw (bench.py's configs run behind the headline): 256^3 (config 2) and the 512 x 512 x 256 block of the config-5
+# the other sizes the same passes saw (bench.py --full runs the configs behind the headline): 256^3 (config 2) and the 512 x 512 x 256 block of the config-5
 # rehearsal -- counter values near 1/8 and 1/2 of the 512^3 ones.  One record per workload: HBM bytes per launch of k_cg_A and of k_cg_Bq (mean of
 # the even- and odd-iteration instantiations), stamped like the others.
 for wl, lo, hi, cells in (("c2_256", 0.09, 0.16, 256 ** 3), ("c5_block", 0.45, 0.55, 512 * 512 * 256)):

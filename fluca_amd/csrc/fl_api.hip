@@ -1850,6 +1850,20 @@ extern "C" int fldbg_launch_plans(int nx, int ny, int nz, int *out, int nout)
   return FLDBG_NPLAN;
 }
 
+// Not part of the public C-ABI either (tests/launch_regimes.py, rr.fused): 1 when a multigrid level of nx x ny x nz cells, halved on every axis,
+// forms the coarse right-hand side with the one-pass residual + restriction (fl_residual_restrict_fusable, the shape test of
+// fl_residual_restrict_padded), 0 when it runs the residual and k_mg_restrict.  Host arithmetic only.  A query of its own rather than a field of
+// fldbg_launch_plans, whose count of FLDBG_NPLAN ints its callers check.
+extern "C" int fldbg_mg_restrict_fused(int nx, int ny, int nz)
+{
+  if (nx < 1 || ny < 1 || nz < 1) return FL_ERR_ARG_OUTOFRANGE;
+  GridP g{};
+  g.nx = nx;
+  g.ny = ny;
+  g.nz = nz;
+  return fl_residual_restrict_fusable(g) ? 1 : 0;
+}
+
 #ifdef FL_KBENCH_VARIANTS  // experiments behind the placement notes of DESIGN.md: not in the product
 // Experiment behind fl_poisson_tune_placement (tools/experiments/pool_probe.py): K vectors allocated once, M random
 // assignments of five of them to the roles (r, p0, p1, q, x) of k_cg_A, probe time of each.

@@ -440,6 +440,7 @@ int  fl_exchange_sr_begin(fl_poisson *h, const double *r, const double *sb, cons
 int fl_apply_tiled(fl_poisson *h, const double *xpad, double *y, int unpadded_y);
 int fl_residual(fl_poisson *h, const double *x, const double *b, double *r);
 int fl_residual_padded(fl_poisson *h, double *xpad, const double *bpad, double *rpad);
+bool fl_residual_restrict_fusable(const GridP &g);
 int fl_residual_restrict_padded(fl_poisson *h, double *xpad, const double *bpad, const double *wx, const double *wy, const double *wz, fl_poisson *hc, double *cpad);
 int fl_apply_padded_dot(fl_poisson *h, double *xpad, double *ypad, double *xy);
 int fl_cheb_smooth_padded(fl_poisson *h, int nu, bool jac, bool guess_zero, bool *mgdots = nullptr, const double *subq = nullptr, const double *suba_dev = nullptr);

@@ -1164,16 +1164,26 @@ int fl_residual_padded(fl_poisson *h, double *xpad, const double *bpad, double *
   return 0;
 }
 
+// The shape test of the one-pass residual + restriction below: a block of this shape, halved on every axis, takes it when the block is even in
+// every direction and the walk pairs rows and planes the way the children pair (two rows per wave, even z chunks).  Host arithmetic only
+// (fldbg_launch_plans reports it as rr.fused).
+bool fl_residual_restrict_fusable(const GridP &g)
+{
+  const PlanA p = plan_cg_A(g, 0, 0);
+  if (p.ry != 2 || (p.nw != 8 && p.nw != 4) || (p.nchunk > 1 && (p.zc & 1))) return false;
+  return !((g.nx & 1) || (g.ny & 1) || (g.nz & 1));
+}
+
 // The coarse right-hand side of a multigrid cycle in one pass: cpad (padded, level hc) = R (b - S x), R = k_mg_restrict's weighted sum over the
-// eight children.  Only where every axis is halved, the block is even in every direction and the walk pairs rows and planes the way the
-// children pair (two rows per wave, even z chunks); returns 1 where it does not apply (the caller runs the residual and the restriction).
+// eight children.  Only where every axis is halved and fl_residual_restrict_fusable holds; returns 1 where it does not apply (the caller runs
+// the residual and the restriction).
 int fl_residual_restrict_padded(fl_poisson *h, double *xpad, const double *bpad, const double *wx, const double *wy, const double *wz, fl_poisson *hc, double *cpad)
 {
   const int on = FL_VARIANT(mg_fused_restrict, 1);  // 0: residual and restriction as two passes (A/B runs)
   const GridP &g = h->g, &gc = hc->g;
-  const PlanA  p = plan_cg_A(g, 0, 0);
-  if (!on || cheb_staged_mode() == 0 || p.ry != 2 || (p.nw != 8 && p.nw != 4) || (p.nchunk > 1 && (p.zc & 1))) return 1;
-  if ((g.nx & 1) || (g.ny & 1) || (g.nz & 1) || gc.nx * 2 != g.nx || gc.ny * 2 != g.ny || gc.nz * 2 != g.nz) return 1;
+  if (!on || cheb_staged_mode() == 0 || !fl_residual_restrict_fusable(g)) return 1;
+  if (gc.nx * 2 != g.nx || gc.ny * 2 != g.ny || gc.nz * 2 != g.nz) return 1;
+  const PlanA p = plan_cg_A(g, 0, 0);
   FL_CHK(fl_fill_ghosts(h, xpad));
   StAux ax;
   ax.csx  = gc.sx;

@@ -437,9 +437,12 @@ class MgOracle:
     V(nu,nu) cycle as left preconditioner.  `bounds[l]` = the eigenvalue bound of D^-1 S the product uses on level l
     (fl_poisson_gershgorin); None = the row-wise Gershgorin bound of the assembled matrix."""
 
-    def __init__(self, g, max_levels=0, nu=3, nullspace=True, bounds=None, prolong="constant", flexible=True):
+    def __init__(self, g, max_levels=0, nu=3, nullspace=True, bounds=None, prolong="constant", flexible=True, record_coarse=False):
         # flexible: the outer CG's beta in the Polak-Ribiere form, -alpha (q . z_new) / (r_old . z_old) (fl_mg.hip "mg_flexible", the default)
+        # record_coarse: every coarsest-level solve appends (reason, its residual norms / its first at the last two iterations) to coarse_stops --
+        # how far the solve stopped from its rtol of 1e-2 (a device that rounds differently takes the same number of iterations only with a margin)
         self.nu, self.nullspace, self.prolong, self.flexible = int(nu), bool(nullspace), prolong, bool(flexible)
+        self.coarse_stops = [] if record_coarse else None
         self.grids, self.S, self.ratio = [g], [g.assemble_S()], []
         while max_levels <= 0 or len(self.grids) < max_levels:
             gf = self.grids[-1]
@@ -502,7 +505,11 @@ class MgOracle:
     def vcycle(self, b, l=0):
         S = self.S[l]
         if l + 1 == self.nlevels:
-            x, _ = S.solve(b, ksp=KSP_CG, pc=PC_JACOBI, nullspace=self.nullspace, rtol=1e-2, maxit=200, history=False)
+            rec = self.coarse_stops is not None
+            x, info = S.solve(b, ksp=KSP_CG, pc=PC_JACOBI, nullspace=self.nullspace, rtol=1e-2, maxit=200, history=rec)
+            if rec:
+                h = info["history"]
+                self.coarse_stops.append((info["reason"], h[-2:] / h[0]))
             return x
         x = self._smooth(l, b)
         r = b - S.mult(x)
@@ -510,8 +517,9 @@ class MgOracle:
         r = b - S.mult(x)
         return x + self._smooth(l, r)
 
-    def pcg(self, b, rtol=1e-5, atol=1e-50, dtol=1e5, maxit=10000):
-        """KSPCG, left preconditioning, preconditioned norm, zero initial guess (same recurrences as fl_solve_cg_mg)."""
+    def pcg(self, b, rtol=1e-5, atol=1e-50, dtol=1e5, maxit=10000, iterates=None):
+        """KSPCG, left preconditioning, preconditioned norm, zero initial guess (same recurrences as fl_solve_cg_mg).
+        iterates: a list that receives the answer after every iteration (what pcg with maxit = 1, 2, ... returns)."""
         S = self.S[0]
         proj = (lambda v: v - v.mean()) if self.nullspace else (lambda v: v)
         x = np.zeros_like(b)
@@ -532,6 +540,8 @@ class MgOracle:
                 break
             alpha = rz / pq
             x += alpha * p
+            if iterates is not None:
+                iterates.append(np.array(proj(x)))      # a copy: without a null space proj(x) is x, which the next iterations update in place
             r -= alpha * q
             z = proj(self.vcycle(r))
             rz_old, dp, rz = rz, np.linalg.norm(z), r @ z

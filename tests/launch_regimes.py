@@ -3,8 +3,9 @@ the launchers) and the grids of the -m gpu regime tests that reach each one.
 
 The kernels pick their tiling, z chunks and grid stride from the grid size, and the toy grids of the parity suite all land in the small plans.
 REGIMES names a grid per plan branch that the product runs at 256^3 - 512^3, made ragged on purpose (partial tiles, a short last z chunk, a
-grid stride that wraps), with the fields of the plans it must get.  tests/test_launch_regimes.py checks the table against the library on the
-CPU; tests/test_gpu_launch_regimes.py and tests/test_gpu_momentum_regimes.py check every kernel on these grids against the oracle."""
+grid stride that wraps), with the fields of the plans it must get; the multigrid regimes name, per level of the hierarchy, the plans of the cycle
+(mg_plans).  tests/test_launch_regimes.py checks the table against the library on the CPU; tests/test_gpu_launch_regimes.py,
+tests/test_gpu_momentum_regimes.py and tests/test_gpu_mg_regimes.py check every kernel on these grids against the oracle."""
 import ctypes as C
 
 from oracle import fluca_oracle as fo
@@ -78,9 +79,92 @@ def mom_last_chunk(p, n):
     return n[2] - (p["mom.t2chunk"] - 1) * p["mom.t2zc"]
 
 
+# ---- the multigrid cycle of FL_PC_MG (fl_mg.hip) on one rank
+MG_BLOCKS = 4096          # the grid of k_mg_restrict, k_mg_pwd and k_mg_dots is capped at this many 256-thread blocks (nblk)
+MG_COARSE_MAX = 4096      # a coarsest level of at most this many cells is solved by one workgroup (k_mg_coarse_cg), else by the public Jacobi-PCG
+CHEB2_MIN_CELLS = 32768   # fl_cheb2_agree: a level of at least this many cells smooths with the fused kernel (k_cheb2; cheb_fuse = 1)
+
+
+def mg_restrict_fused(n):
+    """fldbg_mg_restrict_fused (fl_api.hip, host arithmetic): 1 when a level of n cells, halved on every axis, forms the coarse right-hand side
+    with the one-pass residual + restriction (k_bcgs_st MODE 11), 0 when it runs the residual and k_mg_restrict"""
+    from fluca_amd import capi
+    f = capi.lib.fldbg_mg_restrict_fused
+    f.argtypes = [C.c_int, C.c_int, C.c_int]
+    f.restype = C.c_int
+    r = f(*n)
+    assert r in (0, 1), (n, r)
+    return r
+
+
+def mg_levels(n):
+    """the level shapes of mg_build_levels on one rank: every axis whose cell count is even and >= 8 is halved, until none is"""
+    levels = [tuple(n)]
+    while True:
+        r = [2 if m % 2 == 0 and m >= 8 else 1 for m in levels[-1]]
+        if max(r) == 1:
+            return levels
+        levels.append(tuple(m // q for m, q in zip(levels[-1], r)))
+
+
+def _chunks(n, size):
+    """lengths of the pieces of n cells cut into pieces of size"""
+    return [min(size, n - a) for a in range(0, n, size)]
+
+
+def mg_trips(items):
+    """grid-stride trips (items per thread of the whole grid) of a 256-thread kernel whose grid is capped at MG_BLOCKS (nblk in fl_mg.hip)"""
+    return items / (256 * max(1, min(-(-items // 256), MG_BLOCKS)))
+
+
+def mg_plans(n):
+    """per level of the hierarchy on an n block, what the cycle runs there (host arithmetic of vcycle and fl_solve_cg_mg):
+      n, cells, ratio (to the next level; None on the coarsest), cg.regime and cg.nw of the level's own plan_cg_A, rr.fused (mg_restrict_fused),
+      smoother: "fused" (k_cheb2, the three steps from zero in one sweep) or "single" (k_cheb_st);
+    on a level with a coarser one
+      rr: "fused" (k_bcgs_st MODE 11 on the level's plan) or "fallback" (the residual, then k_mg_restrict: restrict_trips grid-stride trips),
+      prolong: "cc" (k_mg_prolong_lin_cc, every axis halved: prolong.xblocks of 62 coarse columns, prolong.zchunks of 4 coarse planes) or "tile"
+      (k_mg_prolong_lin_tile<false>: x tiles of 128 fine columns, z chunks of 8 fine planes);
+    on the coarsest level
+      coarse: "coarse_cg" (k_mg_coarse_cg) or "pcg" (the public Jacobi-PCG);
+    on level 0
+      pw_trips: the grid-stride trips of k_mg_pwd and k_mg_dots (a thread per cell pair)"""
+    levels = mg_levels(n)
+    out = []
+    for l, m in enumerate(levels):
+        p = launch_plans(m)
+        cells = m[0] * m[1] * m[2]
+        lv = {"n": m, "cells": cells, "ratio": None, "cg.regime": p["cg.regime"], "cg.nw": p["cg.nw"], "rr.fused": mg_restrict_fused(m),
+              "smoother": "fused" if cells >= CHEB2_MIN_CELLS and min(m) >= 2 else "single"}
+        if l == 0:
+            lv["pw_trips"] = mg_trips((m[0] + 1) // 2 * m[1] * m[2])
+        if l + 1 == len(levels):
+            lv["coarse"] = "coarse_cg" if cells <= MG_COARSE_MAX else "pcg"
+        else:
+            c = levels[l + 1]
+            lv["ratio"] = tuple(a // b for a, b in zip(m, c))
+            full = lv["ratio"] == (2, 2, 2)
+            lv["rr"] = "fused" if full and lv["rr.fused"] else "fallback"
+            if lv["rr"] == "fallback":
+                lv["restrict_trips"] = mg_trips(c[0] * c[1] * c[2])
+            if full:
+                lv.update({"prolong": "cc", "prolong.xblocks": _chunks(c[0], 62), "prolong.zchunks": _chunks(c[2], 4)})
+            else:
+                lv.update({"prolong": "tile", "prolong.xblocks": _chunks(m[0], 128), "prolong.zchunks": _chunks(m[2], 8)})
+        out.append(lv)
+    return out
+
+
+def mg_summary(n):
+    """{mg.<field>: value} of the hierarchy on an n block: its depth, the levels that take the one-pass residual + restriction, the coarse solve"""
+    lv = mg_plans(n)
+    return {"mg.levels": len(lv), "mg.rr_fused": tuple(l for l, v in enumerate(lv) if v.get("rr") == "fused"), "mg.coarse": lv[-1]["coarse"]}
+
+
 class Regime:
-    def __init__(self, name, n, bcs, expect, reaches):
-        self.name, self.n, self.bcs, self.expect, self.reaches = name, tuple(n), bcs, expect, reaches
+    def __init__(self, name, n, bcs, expect, reaches, mg=None):
+        # mg: the multigrid regimes only -- per level of mg_plans(n), the fields that level must have (one dict per level, the coarsest included)
+        self.name, self.n, self.bcs, self.expect, self.reaches, self.mg = name, tuple(n), bcs, expect, reaches, mg
 
     def __repr__(self):
         return f"{self.name} {self.n[0]}x{self.n[1]}x{self.n[2]}"
@@ -126,6 +210,53 @@ REGIMES = [
            {"mom.t2x": 3, "mom.t2chunk": 12, "mom.t2zc": 9, "mom.t2blocks": 36},
            "t2 with ny = 8: one tile holds both y ends, so k_mom2 runs also for a state with v0; 12 z chunks of 9 with a last chunk of one plane; "
            "36 blocks, not remapped; x tiles of 128 / 128 / 44"),
+    # the multigrid cycle (mg_plans): the one-pass residual + restriction, the prolongations, the grid-stride kernels and both coarse solves in
+    # the plans of 256^3 - 512^3.  tests/test_gpu_mg_regimes.py runs MG-PCG on these grids, uniform and stretched in all three axes.
+    Regime("mg_standard", (304, 680, 28), [CAVITY, XPER],
+           {"cg.regime": "standard", "cg.nw": 8, "cg.tiles_x": 3, "cg.tiles_y": 43, "cg.nchunk": 2, "cg.zc": 14, "cg.nblocks": 258},
+           "L0 in the standard plan: 129 tiles of 8 waves (x tiles of 128 / 128 / 48, a half y tile), 2 z chunks of 14, the one-pass kernel with 8 "
+           "waves; lin_cc onto 152 x 340 x 14 with x blocks of 62 / 62 / 28 and z chunks of 4 / 4 / 4 / 2; L1's z chunks are odd: the fallback; "
+           "then (2,2,1) and (2,1,1) and a coarsest level of 11305 cells (the public PCG)",
+           mg=[{"n": (304, 680, 28), "ratio": (2, 2, 2), "cg.regime": "standard", "cg.nw": 8, "rr.fused": 1, "rr": "fused", "smoother": "fused", "prolong": "cc",
+                "prolong.xblocks": [62, 62, 28], "prolong.zchunks": [4, 4, 4, 2]},
+               {"n": (152, 340, 14), "ratio": (2, 2, 2), "cg.nw": 4, "rr.fused": 0, "rr": "fallback", "smoother": "fused", "prolong": "cc",
+                "prolong.xblocks": [62, 14], "prolong.zchunks": [4, 3]},
+               {"n": (76, 170, 7), "ratio": (2, 2, 1), "rr": "fallback", "smoother": "fused", "prolong": "tile"},
+               {"n": (38, 85, 7), "ratio": (2, 1, 1), "rr": "fallback", "smoother": "single", "prolong": "tile"},
+               {"n": (19, 85, 7), "cells": 11305, "coarse": "pcg"}]),
+    Regime("mg_mid", (288, 392, 160), [CHANNEL],
+           {"cg.regime": "mid", "cg.nw": 8, "cg.tiles_x": 3, "cg.tiles_y": 25, "cg.nchunk": 3, "cg.zc": 54},
+           "L0 in the mid plan: 8 waves, z chunks of 54 / 54 / 52; the one-pass kernel on L0 (8 waves), L1 and L2 (4 waves); lin_cc with x blocks "
+           "of 62 / 62 / 20; then (2,1,2) twice and a coarsest level of 2205 cells (k_mg_coarse_cg)",
+           mg=[{"n": (288, 392, 160), "ratio": (2, 2, 2), "cg.regime": "mid", "cg.nw": 8, "rr.fused": 1, "rr": "fused", "smoother": "fused", "prolong": "cc",
+                "prolong.xblocks": [62, 62, 20]},
+               {"n": (144, 196, 80), "ratio": (2, 2, 2), "cg.nw": 4, "rr": "fused", "prolong": "cc"},
+               {"n": (72, 98, 40), "ratio": (2, 2, 2), "cg.nw": 4, "rr": "fused", "prolong": "cc"},
+               {"n": (36, 49, 20), "ratio": (2, 1, 2), "rr": "fallback", "prolong": "tile", "prolong.zchunks": [8, 8, 4]},
+               {"n": (18, 49, 10), "ratio": (2, 1, 2), "rr": "fallback", "prolong": "tile"},
+               {"n": (9, 49, 5), "cells": 2205, "coarse": "coarse_cg"}]),
+    Regime("mg_semi", (304, 208, 273), [XPER],
+           {"cg.regime": "mid", "cg.nw": 8, "cg.tiles_x": 3, "cg.tiles_y": 13, "cg.nchunk": 6, "cg.zc": 46},
+           "(2,2,1) at 17 M cells: the fallback residual on the mid 8-wave plan, then k_mg_restrict over 4096 blocks (4.1 trips); "
+           "lin_tile<false> with x tiles of 128 / 128 / 48 and z chunks of 8, the last one a single plane; z is never coarsened: a coarsest level of "
+           "67431 cells (the public PCG, which ends on its 200 iterations there, short of rtol 1e-2)",
+           mg=[{"n": (304, 208, 273), "ratio": (2, 2, 1), "cg.regime": "mid", "cg.nw": 8, "rr.fused": 0, "rr": "fallback", "smoother": "fused", "prolong": "tile",
+                "prolong.xblocks": [128, 128, 48], "prolong.zchunks": [8] * 34 + [1]},
+               {"n": (152, 104, 273), "ratio": (2, 2, 1), "prolong": "tile", "prolong.xblocks": [128, 24]},
+               {"n": (76, 52, 273), "ratio": (2, 2, 1), "prolong": "tile"},
+               {"n": (38, 26, 273), "ratio": (2, 2, 1), "prolong": "tile"},
+               {"n": (19, 13, 273), "cells": 67431, "coarse": "pcg"}]),
+    Regime("production_256", (256, 256, 256), [CAVITY],
+           {"cg.regime": "mid", "cg.nw": 8, "cg.nchunk": 8, "cg.zc": 32},
+           "exactly what a 256^3 solve runs: the one-pass kernel on L0 (8 waves), L1 and L2 (4 waves), the fallback from 32^3 on; lin_cc onto 128^3 "
+           "with x blocks of 62 / 62 / 4; 7 levels down to 4^3 (k_mg_coarse_cg)",
+           mg=[{"n": (256, 256, 256), "ratio": (2, 2, 2), "cg.nw": 8, "rr.fused": 1, "rr": "fused", "prolong": "cc", "prolong.xblocks": [62, 62, 4]},
+               {"n": (128, 128, 128), "cg.nw": 4, "rr": "fused"},
+               {"n": (64, 64, 64), "cg.nw": 4, "rr": "fused"},
+               {"n": (32, 32, 32), "cg.regime": "small_ry1", "rr": "fallback", "smoother": "fused"},
+               {"n": (16, 16, 16), "rr": "fallback", "smoother": "single"},
+               {"n": (8, 8, 8), "rr": "fallback"},
+               {"n": (4, 4, 4), "cells": 64, "coarse": "coarse_cg"}]),
 ]
 BY_NAME = {r.name: r for r in REGIMES}
 
@@ -143,4 +274,12 @@ PRODUCTION = {
     (256, 256, 256): {"cg.regime": "mid", "cg.nblocks": 256, "cg.nchunk": 8, "cheb2.nchunk": 8, "cheb2.clamp": 0, "six.nbx": 1024,
                       "six.items": 16384, "schur.per_xcd": 128, "schur.fixed_seg": 1, "mom.t2chunk": 16,
                       "mom.t2x": 2, "mom.t2zc": 16, "mom.t2blocks": 1024},
+}
+# and the multigrid hierarchy a single-rank solve builds on them (mg_summary): its depth, the levels that take the one-pass residual + restriction,
+# the coarse solve
+PRODUCTION_MG = {
+    (512, 512, 512): {"mg.levels": 8, "mg.rr_fused": (0, 1, 2, 3), "mg.coarse": "coarse_cg"},
+    (512, 512, 256): {"mg.levels": 8, "mg.rr_fused": (0, 1, 2), "mg.coarse": "coarse_cg"},
+    (384, 384, 384): {"mg.levels": 7, "mg.rr_fused": (0, 1), "mg.coarse": "coarse_cg"},
+    (256, 256, 256): {"mg.levels": 7, "mg.rr_fused": (0, 1, 2), "mg.coarse": "coarse_cg"},
 }

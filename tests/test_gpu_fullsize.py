@@ -175,6 +175,43 @@ def test_c3_channel_chebyshev_matches_oracle_at_512():
     assert par["rel_max_diff_x"] <= 1e-12 and par["rel_l2_diff_x"] <= 1e-12, par
 
 
+def test_multigrid_first_iterate_matches_oracle_at_512():
+    """FL_PC_MG on the 512^3 cavity, the hierarchy bench.py's multigrid line times: the one-pass residual + restriction on L0 (standard plan, 8
+    waves), L1 (mid plan, 8 waves), L2 and L3 (4 waves), k_mg_prolong_lin_cc onto 256^3 in five x blocks (the last of 8 columns), k_mg_pwd and
+    k_mg_dots over 32 grid-stride trips.  x after one MG-PCG iteration (two cycles) and the residual norms against MgOracle's assembled hierarchy
+    (the oracle side: about 14 GB for the matrices of the eight levels)."""
+    import resource
+    import time
+
+    from fluca_amd.poisson import Poisson
+    from tests.gpu_common import CAVITY, dev, host, mean_free_rhs
+    from tests.launch_regimes import mg_summary
+    from tests.test_gpu_mg import _bounds
+    _needs_host_memory(48.0)
+    assert mg_summary(N512)["mg.rr_fused"] == (0, 1, 2, 3)
+    _bench()._oracle_threads()
+    t0 = time.perf_counter()
+    g = fo.Grid.uniform(N512, CAVITY_BOX, CAVITY, 1e-3)
+    mg = fo.MgOracle(g, nullspace=True, prolong="linear", record_coarse=True)
+    mg.bounds = _bounds(mg)
+    _, b = mean_free_rhs(mg.S[0], g.ncell)
+    xs = []
+    _, io = mg.pcg(b, rtol=0.0, atol=0.0, maxit=1, iterates=xs)
+    seconds = time.perf_counter() - t0
+    margin = min(abs(q / 1e-2 - 1.0) for _, qs in mg.coarse_stops for q in qs)
+    del mg
+    P = Poisson.uniform(N512, CAVITY_BOX, CAVITY, 1e-3)
+    x, ig = P.solve(dev(b), history=True, type=0, pc=2, remove_nullspace=1, rtol=0.0, atol=0.0, maxit=1)
+    P.close()
+    dx = float(np.abs(host(x) - xs[0]).max() / np.abs(xs[0]).max())
+    dh = float(np.abs(ig["history"] / io["history"] - 1.0).max())
+    print(f"\n[mg] 512^3 cavity: x_1 {dx:.2e} history {dh:.2e} coarse-stop margin {margin:.3e}; oracle {seconds:.0f} s, "
+          f"peak host memory of the process {resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 2**20:.1f} GB")
+    assert ig["iters"] == io["iters"] == 1 and ig["reason"] == io["reason"] == -3
+    assert margin >= 1e-6, margin
+    assert dx <= 1e-10 and dh <= 1e-10, (dx, dh)
+
+
 def test_momentum_block_matches_the_assembled_oracle_at_256():
     _needs_host_memory(40.0)
     bench = _bench()

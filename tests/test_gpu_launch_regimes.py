@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import fluca_oracle as fo
-from tests.gpu_common import CAVITY_BOX, dev, host, mean_free_rhs
+from tests.gpu_common import CAVITY_BOX, dev, host, mean_free_rhs, stretched_faces
 from tests.launch_regimes import BY_NAME, CAVITY, CHANNEL, XPER, launch_plans, six_trips
 
 pytestmark = pytest.mark.gpu
@@ -20,10 +20,11 @@ BCNAME = {tuple(CAVITY): "cavity", tuple(CHANNEL): "channel", tuple(XPER): "xper
 _GRIDS, _MATS = {}, {}
 
 
-def _grid(n, bc):
-    key = (tuple(n), tuple(bc))
+def _grid(n, bc, stretched=False):
+    """stretched: the faces of stretched_faces (every axis stretched towards both ends) instead of the uniform cavity box"""
+    key = (tuple(n), tuple(bc)) + (("stretched",) if stretched else ())
     if key not in _GRIDS:
-        _GRIDS[key] = fo.Grid.uniform(n, CAVITY_BOX, bc, 1e-3)
+        _GRIDS[key] = fo.Grid(n, stretched_faces(n), bc, 1e-3) if stretched else fo.Grid.uniform(n, CAVITY_BOX, bc, 1e-3)
     return _GRIDS[key]
 
 

@@ -1,12 +1,12 @@
 """The regime table of tests/launch_regimes.py against the plans the library computes (fldbg_launch_plans: host arithmetic, no GPU).
 
 If a threshold of a plan moves, these tests name the regime whose grid no longer reaches its branch: the -m gpu modules
-tests/test_gpu_launch_regimes.py and tests/test_gpu_momentum_regimes.py then check another plan than the one they were written for, and the
+tests/test_gpu_launch_regimes.py, tests/test_gpu_momentum_regimes.py and tests/test_gpu_mg_regimes.py then check another plan than the one they were written for, and the
 table must be re-aimed."""
 import pytest
 
-from tests.launch_regimes import (BY_NAME, FIELDS, PRODUCTION, REGIMES, launch_plans, mom_last_chunk, mom_regime, mom_tiles,
-                                  six_trips)
+from tests.launch_regimes import (BY_NAME, CAVITY, CHANNEL, FIELDS, PER, PRODUCTION, PRODUCTION_MG, REGIMES, SYM, O, V, launch_plans, mg_levels,
+                                  mg_plans, mg_restrict_fused, mg_summary, mom_last_chunk, mom_regime, mom_tiles, six_trips)
 
 
 @pytest.mark.parametrize("reg", REGIMES, ids=[r.name for r in REGIMES])
@@ -115,6 +115,87 @@ def test_momentum_regime_grid_tells_its_columns_rows_and_planes_apart(reg):
                     assert apart >= 1e-7, (reg.name, bc, d, c, s, apart)
                     if n - s >= 3:      # two inner cells that far apart: the uniform grid gives them the same numbers
                         assert gap(R["uniform"], s)[1:-1].min() <= 1e-14, (reg.name, bc, d, c, s)
+
+
+MG = [r for r in REGIMES if r.mg]
+
+
+@pytest.mark.parametrize("reg", MG, ids=[r.name for r in MG])
+def test_multigrid_regime_grid_takes_its_levels(reg):
+    """the hierarchy of the regime, level by level: shape, ratio, the plans of the residual + restriction, prolongation, smoother and coarse solve"""
+    got = mg_plans(reg.n)
+    assert [lv["n"] for lv in got] == [lv["n"] for lv in reg.mg], f"regime {reg.name}: the hierarchy changed ({reg.reaches})"
+    wrong = {(l, k): (v, got[l].get(k)) for l, want in enumerate(reg.mg) for k, v in want.items() if got[l].get(k) != v}
+    assert not wrong, f"regime {reg.name} {reg.n} left its plans ({reg.reaches}); (level, field): (expected, got) {wrong}"
+
+
+def test_table_covers_every_branch_of_the_multigrid_cycle():
+    """the edges of the cycle at 256^3 - 512^3 that the toy grids of tests/test_gpu_mg.py never reach (all their levels take the small_ry1 plan)"""
+    levels = [(r, l, lv) for r in MG for l, lv in enumerate(mg_plans(r.n))]
+    inner = [(r, l, lv) for r, l, lv in levels if lv["ratio"] is not None]
+    covered = {
+        # k_bcgs_st MODE 11 as <2, 8, 11> and <2, 4, 11>, and the two-pass fallback on a level of 8-wave tiles
+        "one-pass residual + restriction, 8 waves": [r.name for r, l, lv in inner if lv["rr"] == "fused" and lv["cg.nw"] == 8],
+        "one-pass residual + restriction, 4 waves": [r.name for r, l, lv in inner if lv["rr"] == "fused" and lv["cg.nw"] == 4],
+        "fallback on an 8-wave level": [r.name for r, l, lv in inner if lv["rr"] == "fallback" and lv["cg.nw"] == 8],
+        # k_mg_prolong_lin_cc: three or more 62-column blocks, the last partial; a last z chunk shorter than 4
+        "lin_cc, >= 3 x blocks, partial last": [r.name for r, l, lv in inner if lv["prolong"] == "cc" and len(lv["prolong.xblocks"]) >= 3
+                                                and lv["prolong.xblocks"][-1] < 62],
+        "lin_cc, short last z chunk": [r.name for r, l, lv in inner if lv["prolong"] == "cc" and lv["prolong.zchunks"][-1] < 4
+                                       and len(lv["prolong.zchunks"]) > 1],
+        # k_mg_prolong_lin_tile<false>: three x tiles and a last z chunk of one plane
+        "lin_tile<false>, 3 x tiles": [r.name for r, l, lv in inner if lv["prolong"] == "tile" and len(lv["prolong.xblocks"]) >= 3],
+        "lin_tile<false>, last z chunk of one plane": [r.name for r, l, lv in inner if lv["prolong"] == "tile" and lv["prolong.zchunks"][-1] == 1
+                                                       and len(lv["prolong.zchunks"]) > 1],
+        # the grid-stride kernels take several trips: k_mg_restrict, and k_mg_pwd / k_mg_dots on level 0
+        "k_mg_restrict, several trips": [r.name for r, l, lv in inner if lv["rr"] == "fallback" and lv["restrict_trips"] > 2],
+        "k_mg_pwd / k_mg_dots, several trips": [r.name for r, l, lv in levels if l == 0 and lv["pw_trips"] > 2],
+        # the three fused smoothing steps from zero on 8-wave tiles with several z chunks
+        "fused smoother, 8 waves, several z chunks": [r.name for r, l, lv in levels if lv["smoother"] == "fused" and lv["cg.nw"] == 8
+                                                      and launch_plans(lv["n"])["cheb2.nchunk"] > 1],
+        # both coarse solves
+        "k_mg_coarse_cg": [r.name for r, l, lv in levels if lv.get("coarse") == "coarse_cg"],
+        "the public Jacobi-PCG as coarse solve": [r.name for r, l, lv in levels if lv.get("coarse") == "pcg"],
+    }
+    missing = [what for what, names in covered.items() if not names]
+    assert not missing, f"no multigrid regime reaches: {missing}"
+    # and the toy grids reach none of the one-pass kernel
+    for n in ((32, 32, 16), (32, 16, 16), (24, 20, 16), (32, 24, 16), (64, 64, 32)):
+        assert all(lv.get("rr") != "fused" for lv in mg_plans(n)), n
+
+
+@pytest.mark.parametrize("n,bc", [
+    ((32, 32, 16), CAVITY), ((32, 16, 16), [PER] * 6), ((24, 20, 16), CHANNEL), ((64, 64, 32), CAVITY), ((15, 15, 15), CAVITY),
+    ((40, 24, 16), [O, V, V, V, V, V]), ((64, 32, 32), [PER, PER, V, V, SYM, V]), ((160, 40, 36), CAVITY), ((130, 18, 34), [V, V, PER, PER, SYM, V]),
+    ((34, 10, 12), CAVITY),
+])
+def test_mg_levels_follow_the_oracle(n, bc):
+    """mg_levels restates mg_build_levels' rule; the oracle's MgOracle builds its hierarchy by the same rule (the grids of tests/test_gpu_mg.py)"""
+    from oracle import fluca_oracle as fo
+    g = fo.Grid.uniform(n, [(0.0, 1.0), (0.0, 1.0), (0.0, 0.5)], bc, 1e-3)
+    assert mg_levels(n) == [gl.n for gl in fo.MgOracle(g).grids]
+
+
+@pytest.mark.parametrize("n", list(PRODUCTION_MG), ids=["x".join(map(str, n)) for n in PRODUCTION_MG])
+def test_production_shapes_build_their_hierarchy(n):
+    got = mg_summary(n)
+    want = PRODUCTION_MG[n]
+    wrong = {k: (v, got[k]) for k, v in want.items() if got[k] != v}
+    assert not wrong, f"production shape {n}: multigrid hierarchy moved; field: (expected, got) {wrong}"
+
+
+def test_restrict_query_restates_the_launcher():
+    """fldbg_mg_restrict_fused against the shape test of fl_residual_restrict_padded, restated from the fields of plan_cg_A: two rows per wave,
+    4- or 8-wave tiles, even z chunks, an even block; out-of-range sizes are refused"""
+    from fluca_amd import capi
+    shapes = [r.n for r in REGIMES] + list(PRODUCTION) + [lv["n"] for r in MG for lv in mg_plans(r.n)]
+    shapes += [(a, b, c) for a in (2, 8, 62, 130, 256) for b in (6, 8, 16, 32, 34, 200) for c in (1, 4, 14, 15, 28, 30)]
+    for n in shapes:
+        p = launch_plans(n)
+        want = int(p["cg.ry"] == 2 and p["cg.nw"] in (4, 8) and (p["cg.nchunk"] == 1 or p["cg.zc"] % 2 == 0) and all(m % 2 == 0 for m in n))
+        assert mg_restrict_fused(n) == want, (n, p)
+    assert {mg_restrict_fused(n) for n in shapes} == {0, 1}
+    assert capi.lib.fldbg_mg_restrict_fused(0, 4, 4) < 0 and capi.lib.fldbg_mg_restrict_fused(4, 4, -1) < 0
 
 
 @pytest.mark.parametrize("n", list(PRODUCTION), ids=["x".join(map(str, n)) for n in PRODUCTION])

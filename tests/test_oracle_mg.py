@@ -93,3 +93,24 @@ def test_flexible_beta_keeps_a_nonsymmetric_cycle_converging():
     bu = Su.mult(p - p.mean())
     same = [fo.MgOracle(gu, nu=3, prolong="constant", flexible=fl).pcg(bu, rtol=1e-8, maxit=100)[1] for fl in (False, True)]
     assert same[0]["iters"] == same[1]["iters"] and np.allclose(same[0]["history"], same[1]["history"], rtol=2e-3)   # the coarsest level is solved to a tolerance: not exactly a fixed operator
+
+
+@pytest.mark.parametrize("bc,nullspace", [([V, V, V, V, SYM, V], True), ([V, O, V, V, PER, PER], False)])
+def test_recorded_iterates_and_coarse_stops_change_nothing(bc, nullspace):
+    """pcg(iterates=...) hands out what pcg(maxit=k) returns for every k, and record_coarse only records (tests/test_gpu_mg_regimes.py compares the
+    device with these): the same answers and histories as a plain run, one coarsest solve per cycle"""
+    n = (40, 24, 20)
+    g = fo.Grid(n, [_stretched(n[d], 0.0, (1.0, 1.0, 0.5)[d], 1.1 + 0.2 * d) for d in range(3)], bc, 1e-3)
+    mg = fo.MgOracle(g, nullspace=nullspace, prolong="linear", record_coarse=True)
+    p = np.random.default_rng(5).standard_normal(g.ncell)
+    b = mg.S[0].mult(p - p.mean() if nullspace else p)
+    xs = []
+    x3, info = mg.pcg(b, rtol=0.0, atol=0.0, maxit=3, iterates=xs)
+    assert info["iters"] == 3 and len(xs) == 3 and np.array_equal(xs[2], x3)
+    assert len(mg.coarse_stops) == 4
+    for reason, (before, last) in mg.coarse_stops:
+        assert reason == 2 and last <= 1e-2 < before
+    for k in (1, 2):
+        xk, ik = fo.MgOracle(g, nullspace=nullspace, prolong="linear").pcg(b, rtol=0.0, atol=0.0, maxit=k)
+        assert np.array_equal(xs[k - 1], xk) and np.array_equal(ik["history"], info["history"][:k + 1]), k
+        assert not np.array_equal(xs[k - 1], x3)

@@ -12,16 +12,12 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-# the product lives in lib/; a build with FL_KBENCH_VARIANTS=1 (superseded kernels and experiment switches compiled in, fl_knobs.h) goes to
-# lib_kbench/ and never replaces it -- point FLUCA_LIB_DIR at that directory to load it (tools/kbench.py, tools/experiments/)
-KBENCH = bool(os.environ.get("FL_KBENCH_VARIANTS"))
-LIBDIR = os.path.join(HERE, "lib_kbench" if KBENCH else "lib")
+LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libflucahip.so")
 SOURCES = ["fl_coeff.cpp", "fl_kernels.hip", "fl_api.hip", "fl_ksp.hip", "fl_cheb2.hip", "fl_layout.hip", "fl_ibm.hip", "fl_momentum.hip", "fl_mg.hip", "fl_schur_var.hip"]
 HEADERS = ["fl_internal.h", "fl_knobs.h", "fl_handle.h", "fl_device.h", "fl_stencil.h", "fl_mom_tile.h", "fl_mom_tile3.h", os.path.join("..", "..", "include", "fluca_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = (["-DFL_KBENCH_VARIANTS"] if KBENCH else []) + [f"-D{d}" for d in os.environ.get("FL_DEFINES", "").split()] + ([f"-DFL_MOM_WPE={int(os.environ['FL_MOM_WPE'])}"] if os.environ.get("FL_MOM_WPE") else []) + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
-         "-Wno-unused-result"]
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
 MANIFEST = os.path.join(LIBDIR, "manifest.json")
 
 
@@ -116,7 +112,7 @@ def build(force=False, verbose=False):
             _record(o, [s] + hdrs, cmd)
         objs.append(o)
     # the build id: a translation unit of its own, regenerated whenever any source differs
-    sid = source_id() + ("+kbench" if KBENCH else "")
+    sid = source_id()
     idsrc, idobj = os.path.join(LIBDIR, "fl_build_id.cpp"), os.path.join(LIBDIR, "fl_build_id.cpp.o")
     text = f'extern "C" const char *fl_build_id(void) {{ return "{sid}"; }}\n'
     if not os.path.exists(idsrc) or open(idsrc).read() != text:

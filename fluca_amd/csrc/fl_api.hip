@@ -118,14 +118,6 @@ static int poisson_init(fl_poisson *h, const fl_grid *grid, const int bc[6], dou
   g.fx    = fl_[0];
   g.fy    = fl_[1];
   g.fz    = fl_[2];
-  // Row-interleaved vector layout (FLUCA_INTERLEAVE=NV > 1): row (j,k) of vector v lives at ((k*sy + j)*NV + v)*sx0, i.e. the
-  // same row of all NV solver vectors is contiguous in memory and a kernel that streams several vectors sweeps ONE
-  // address range instead of NV ranges a gigabyte apart.  Kernels only ever see (pointer, row stride, plane stride).
-  {
-    h->nv_il = FL_VARIANT(interleave, FL_DEFAULT_INTERLEAVE);
-    if (h->nv_il < 2) h->nv_il = 1;
-    if (h->nv_il > 8) h->nv_il = 8;
-  }
   // Ghost width of the padded layout: 1 = the reference's star stencil (cart.c:66,91), what every operator needs; 2 where a neighbouring RANK
   // sits behind a boundary, so that the two-deep exchange of fl_fill_ghosts_deep has somewhere to put its second layer and the fused
   // two-step smoother (k_cheb2) can run on several ranks.  Kernels only ever see (off0, sx, sxy): the width is a property of the handle,
@@ -133,11 +125,10 @@ static int poisson_init(fl_poisson *h, const fl_grid *grid, const int bc[6], dou
   {
     const int forced = knob(K_ghost_width);
     h->gw            = forced > 0 ? forced : (h->multi && !h->loopback ? 2 : 1);
-    if (h->gw < 1 || h->gw > 2 || h->nv_il > 1) h->gw = 1;
+    if (h->gw < 1 || h->gw > 2) h->gw = 1;
   }
   const int gw = h->gw;
-  h->sx0  = ((PADX + g.nx + gw + 15) / 16) * 16;
-  g.sx    = h->sx0 * h->nv_il;
+  g.sx    = ((PADX + g.nx + gw + 15) / 16) * 16;
   g.sxy   = (int64_t)g.sx * (g.ny + 2 * gw);
   g.off0  = (int64_t)gw * g.sxy + (int64_t)gw * g.sx + PADX;
   g.kappa = kappa;
@@ -369,7 +360,7 @@ struct KnobEntry {
 };
 KnobEntry g_knobs[K_COUNT + 1] = {
 #define X(n, d) {#n, (d), {(d)}},
-    FL_PUBLIC_KNOBS(X) FL_VARIANT_KNOBS(X)
+    FL_PUBLIC_KNOBS(X)
 #undef X
         {nullptr, 0, {0}}};
 // the one place where the library reads its environment: FLUCA_<NAME> gives a knob its initial value
@@ -402,9 +393,6 @@ int knob_find(const char *name)
   return -1;
 }
 const char *knob_name(int k) { return k >= 0 && k < K_COUNT ? g_knobs[k].name : nullptr; }
-#ifdef FL_KBENCH_VARIANTS
-const char *variant_env(const char *name) { return std::getenv(name); }
-#endif
 }  // namespace fl
 
 extern "C" int fl_tuning_set(const char *name, int value)
@@ -516,7 +504,7 @@ constexpr int    PL_SIDE      = 3;                   // pool slots on either sid
 
 int place_vectors(fl_poisson *h)
 {
-  if (h->placed || h->nv_il > 1) return 0;
+  if (h->placed) return 0;
   h->placed = true;  // whatever happens below is final for this handle
   hipStream_t  s    = h->stream;
   const size_t vecb = ((sizeof(double) * h->padlen + ((size_t)2 << 20) - 1) / ((size_t)2 << 20)) * ((size_t)2 << 20);
@@ -631,9 +619,7 @@ int place_vectors(fl_poisson *h)
       best    = abest;
       best_ms = abest_ms;
     }
-    const char  *te = variant_env("FLUCA_PLACEMENT_THRESH");  // experiments: 0 walks through all PL_ARENAS arenas
-    const double thresh = te ? std::atof(te) : 0.97;
-    if (best_ms <= thresh * first_ms) break;  // a seam was found
+    if (best_ms <= 0.97 * first_ms) break;  // a seam was found
   }
   if (!arena) return 0;  // no memory for an arena: plain allocations
   // A chunk-mapped arena gives back everything but the chunks under the chosen window: the handle keeps five vectors (plus at most two
@@ -726,7 +712,7 @@ extern "C" int fl_poisson_tune_placement(fl_poisson *h, int max_tries, double pr
   if (!h) return FL_ERR_ARG_NULL;
   if (max_tries < 1) return FL_ERR_ARG_OUTOFRANGE;
   FL_HIP(hipSetDevice(h->device));
-  if (!h->placed && h->nv_il == 1) {
+  if (!h->placed) {
     FL_HIP(hipStreamSynchronize(h->stream));
     // vectors that exist already (a solve ran before this call) are dropped: every solve re-creates what it needs
     fl_mg_destroy(h);
@@ -735,7 +721,6 @@ extern "C" int fl_poisson_tune_placement(fl_poisson *h, int max_tries, double pr
     h->vec_bases.clear();
     h->vec_bytes = 0;
     h->nvec = 0;
-    h->slab = nullptr;
     for (double **v : {&h->r, &h->P0, &h->P1, &h->q, &h->xp, &h->w0, &h->w1, &h->w2, &h->cd1, &h->rb}) *v = nullptr;
     for (double *&v : h->Pr) v = nullptr;
     FL_CHK(place_vectors(h));
@@ -757,13 +742,11 @@ extern "C" int fl_poisson_vector_bytes(fl_poisson *h, int64_t *bytes_out)
 
 // ------------------------------------------------------------------------------------------------ workspace / ghosts
 
-// Padded solver vectors.  Each one starts at a different offset inside its allocation (multiples of FLUCA_SKEW bytes,
-// default 0): the hot kernels touch the same logical index of up to six vectors at the same time, and identical
-// low address bits put those six streams on the same HBM channel.
+// Padded solver vectors: from the placement window or the pool where the handle has one, else one allocation per vector (placement).
 int fl_ensure_vec(fl_poisson *h, double **v)
 {
   if (*v) return 0;
-  if (h->nv_il == 1 && !h->placed && h->nvec == 0 && knob(K_placement) > 0 && sizeof(double) * h->padlen >= PL_MIN_VEC) {
+  if (!h->placed && h->nvec == 0 && knob(K_placement) > 0 && sizeof(double) * h->padlen >= PL_MIN_VEC) {
     // carves r, P0, P1, q, xp out of one allocation (see "placement" above).  A failure in there (memory short, a probe launch refused)
     // is no reason to fail the caller's solve: whatever the search held is released and the vectors become plain allocations.
     if (place_vectors(h) != 0) {
@@ -777,47 +760,20 @@ int fl_ensure_vec(fl_poisson *h, double **v)
     h->nvec++;
     return 0;
   }
-  if (h->nv_il > 1) {
-    // interleaved: one slab, vector k starts k*sx0 doubles into it
-    if (!h->slab) {
-      FL_CHK(fl_dev_alloc(h, &h->slab, sizeof(double) * h->padlen, true));
-      h->vec_bases.push_back(h->slab);
-    }
-    if (h->nvec >= h->nv_il) return FL_ERR_MEM;
-    *v = (double *)h->slab + (size_t)h->sx0 * (size_t)h->nvec++;
-    return 0;
-  }
-  const long gap = ((long)FL_VARIANT(gap, FL_DEFAULT_GAP) / 128) * 128;
-  constexpr int NSLOTS = 8;
-  const size_t  slot   = ((sizeof(double) * h->padlen + 127) / 128) * 128 + (size_t)gap;
-  const bool use_slab = FL_VARIANT(slab, 0) != 0;  // default: one hipMalloc per vector (placement)
-  if (!use_slab) {
-    void *base = nullptr;
-    FL_CHK(fl_dev_alloc(h, &base, slot, true));
-    h->vec_bases.push_back(base);
-    h->vec_bytes += slot;
-    h->nvec++;
-    *v = (double *)base;
-    return 0;
-  }
-  if (!h->slab) {
-    FL_CHK(fl_dev_alloc(h, &h->slab, slot * NSLOTS, true));
-    h->vec_bases.push_back(h->slab);
-  }
-  if (h->nvec >= NSLOTS) return FL_ERR_MEM;
-  *v = (double *)((char *)h->slab + slot * (size_t)h->nvec++);
+  const size_t slot = ((sizeof(double) * h->padlen + 127) / 128) * 128;
+  void        *base = nullptr;
+  FL_CHK(fl_dev_alloc(h, &base, slot, true));
+  h->vec_bases.push_back(base);
+  h->vec_bytes += slot;
+  h->nvec++;
+  *v = (double *)base;
   return 0;
 }
 
 // zero a padded vector (ghosts included) on the handle's stream
 int fl_zero_vec(fl_poisson *h, double *v)
 {
-  if (h->nv_il <= 1) {
-    FL_HIP(hipMemsetAsync(v, 0, sizeof(double) * h->padlen, h->stream));
-    return 0;
-  }
-  const size_t rows = (size_t)(h->g.ny + 2) * (size_t)(h->g.nz + 2);
-  FL_HIP(hipMemset2DAsync(v, sizeof(double) * (size_t)h->g.sx, 0, sizeof(double) * (size_t)h->sx0, rows, h->stream));
+  FL_HIP(hipMemsetAsync(v, 0, sizeof(double) * h->padlen, h->stream));
   return 0;
 }
 
@@ -996,9 +952,9 @@ int fl_fill_ghosts_deep(fl_poisson *h, double *v)
   return 0;
 }
 
-// The CG iteration's ghost exchange of r, hidden behind k_cg_B (the DMGlobalToLocalBegin / ...End pair of the reference,
+// The CG iteration's ghost exchange of r, hidden behind k_cg_Bq (the DMGlobalToLocalBegin / ...End pair of the reference,
 // fdapply.c:71, cnlinearcart3d.c:893-894).  begin: the boundary layers of r - alpha q are packed on the handle's stream BEFORE
-// k_cg_B forms the new r; a second stream waits for the pack, runs the transfers and writes the ghost layers, which k_cg_B neither
+// k_cg_Bq forms the new r; a second stream waits for the pack, runs the transfers and writes the ghost layers, which k_cg_Bq neither
 // reads nor writes.  end: the handle's stream waits for the ghosts (and fills the locally wrapped axes) before k_cg_A needs them.
 int fl_exchange_r_begin(fl_poisson *h, double *r, const double *q)  // q: valid on the boundary layers of the block at least (PlanA::qb)
 {
@@ -1124,11 +1080,8 @@ extern "C" int fl_poisson_project(fl_poisson *h, const double *p_dev, double *vx
   if (!h || !p_dev) return FL_ERR_ARG_NULL;
   FL_HIP(hipSetDevice(h->device));
   double *v[3] = {vx, vy, vz}, *V[3] = {Vx, Vy, Vz};
-  // A/B runs.  0: one kernel per output array (round 1); 1: k_project_all (round 3); 2: k_project_six on the padded p; 3 (shipped): on the caller's p where
-  // one rank holds the grid
-  const int fused = FL_VARIANT(project_fused, 3);
   // all six arrays (PCApply_ABF's call), one rank: k_project_six reads the caller's p itself -- no padded copy, no ghost layers
-  if (fused >= 3 && !h->multi && project_six_usable(h->g, p_dev, v, V)) {
+  if (!h->multi && project_six_usable(h->g, p_dev, v, V)) {
     int per = 0;
     for (int d = 0; d < 3; ++d) per |= h->wrap_local[d] ? (1 << d) : 0;
     launch_project_six(h->stream, h->g, p_dev, true, per, v, V);
@@ -1138,21 +1091,11 @@ extern "C" int fl_poisson_project(fl_poisson *h, const double *p_dev, double *vx
   FL_CHK(fl_ensure_vec(h, &h->w0));
   launch_pad_copy(h->stream, h->g, p_dev, h->w0);
   FL_CHK(fl_fill_ghosts(h, h->w0));
-  if (fused >= 2 && project_six_usable(h->g, nullptr, v, V)) {
+  if (project_six_usable(h->g, nullptr, v, V)) {  // several ranks: the same kernel on the padded p
     launch_project_six(h->stream, h->g, h->w0, false, 0, v, V);
     FL_HIP(hipGetLastError());
     return FL_SUCCESS;
   }
-#ifdef FL_KBENCH_VARIANTS
-  if (!fused) {
-    for (int d = 0; d < 3; ++d) {
-      if (v[d]) launch_project_cells(h->stream, h->g, h->w0, v[d], d);
-      if (V[d]) launch_project_faces(h->stream, h->g, h->w0, V[d], d);
-    }
-    FL_HIP(hipGetLastError());
-    return FL_SUCCESS;
-  }
-#endif
   launch_project_all(h->stream, h->g, h->w0, v, V);  // any subset of the six arrays, one pass over p
   FL_HIP(hipGetLastError());
   return FL_SUCCESS;
@@ -1247,6 +1190,7 @@ static int cg_fin(fl_poisson *h, int mode, int nblocks, int nslot, double *hist,
 
 static int solve_cg(fl_poisson *h, const double *b, double *x, const fl_ksp_opts *o, fl_ksp_stats *st)
 {
+  if (o->variant != 0) return FL_ERR_SUP;  // the superseded forms of the iteration left the library (include/fluca_hip.h, fl_ksp_opts.variant)
   const GridP &g   = h->g;
   const bool   jac = o->pc == FL_PC_JACOBI;
   FL_CHK(fl_ensure_vec(h, &h->r));
@@ -1254,43 +1198,21 @@ static int solve_cg(fl_poisson *h, const double *b, double *x, const fl_ksp_opts
   FL_CHK(fl_ensure_vec(h, &h->P1));
   FL_CHK(fl_ensure_vec(h, &h->q));
   FL_CHK(fl_ensure_vec(h, &h->xp));
-  // variant 0 (default): k_cg_A<SQ = false> + k_cg_Bq, q = S p' formed twice and never stored (64 B/cell/iteration);
-  // variant 2: k_cg_A stores q, k_cg_B reads it back (72 B/cell; the default until round 2); variant 1: one kernel per step
-  const int variant_forced = FL_VARIANT(cg_variant, -1);
-  const int variant = (o->variant == 0 && variant_forced >= 0) ? variant_forced : o->variant;
-#ifndef FL_KBENCH_VARIANTS
-  if (variant != 0) return FL_ERR_SUP;  // variants 1 and 2 (superseded, A/B material) live in the kbench build only (include/fluca_hip.h, fl_ksp_opts.variant)
-#endif
-  const bool storeq = variant != 0;  // variants 1 and 2 keep q in memory and update r with k_cg_B
-  PlanA       plan = plan_cg_A(g, 0, 0);
-  plan.sq          = storeq ? 1 : 0;
-  const int qb_env = FL_VARIANT(cg_qb, 1);  // experiments (only with "overlap" = 0): 0 = k_cg_A stores no q at all
-  plan.qb          = (!storeq && h->multi && qb_env) ? 1 : 0;  // several ranks: q of the boundary layers is kept for the overlapped exchange of r
-  const int bq_chunks_env = FL_VARIANT(cgbq_chunks, 0);  // experiments: z chunks of k_cg_Bq (default: those of k_cg_A)
-  PlanA planB = storeq ? plan_cg_B(g) : (bq_chunks_env > 0 ? plan_tiles(g, plan.ry, plan.nw, bq_chunks_env, 0) : plan);  // k_cg_Bq walks the tiles of k_cg_A
-  {
-    struct Force { int ry = 0, nw = 0, nchunk = 0; };
-    Force fb;
-    if (const char *e = variant_env("FLUCA_CGBQ_PLAN")) std::sscanf(e, "%d,%d,%d", &fb.ry, &fb.nw, &fb.nchunk);  // experiments: a tiling of its own for k_cg_Bq
-    if (!storeq && (fb.ry == 1 || fb.ry == 2) && (fb.nw == 4 || (fb.nw == 8 && fb.ry == 2)) && fb.nchunk > 0 && g.ny >= 8) {
-      const PlanA keep = planB;
-      planB            = plan_tiles(g, fb.ry, fb.nw, fb.nchunk, 0);
-      planB.pf = keep.pf; planB.nt = keep.nt; planB.remap = keep.remap; planB.sq = keep.sq; planB.qb = keep.qb;
-    }
-  }
+  // k_cg_A + k_cg_Bq: q = S p' is formed twice and never stored (64 B/cell/iteration, less with batched x-updates); k_cg_Bq walks the tiles of k_cg_A
+  PlanA plan = plan_cg_A(g, 0, 0);
+  plan.qb    = h->multi ? 1 : 0;  // several ranks: q of the boundary layers is kept for the overlapped exchange of r
   const int   nsb  = stream_blocks(g);
-  const int   nab  = variant == 1 ? apply_dot_blocks(g) : plan.nblocks;
-  FL_CHK(fl_ensure_partials(h, std::max(std::max(nsb, nab), planB.nblocks)));
+  FL_CHK(fl_ensure_partials(h, std::max(nsb, plan.nblocks)));
   const int nhist = o->maxit + 1;
   FL_CHK(fl_ensure_hist(h, nhist));
   hipStream_t s = h->stream;
 
   const bool xbatch_env = knob(K_cg_xbatch) != 0;
-  // q-free pair with batched x-updates: x is read and written on every K-th iteration only, K = the slots of the direction ring (one rank:
-  // cg_xdepth; several ranks and the stored-q variants: 2).  The padded x is not zeroed -- the first flush (iteration K - 1) writes it
+  // batched x-updates: x is read and written on every K-th iteration only, K = the slots of the direction ring (one rank: cg_xdepth; several
+  // ranks: 2).  The padded x is not zeroed -- the first flush (iteration K - 1) writes it
   // without reading it, and until then KspScal::x_valid = 0 tells k_cg_finish that it stands for 0
-  const bool xlazy  = !storeq && xbatch_env;
-  const int  xdepth = (xlazy && !h->multi && h->nv_il == 1) ? knob(K_cg_xdepth) : 2;
+  const bool xlazy  = xbatch_env;
+  const int  xdepth = (xlazy && !h->multi) ? knob(K_cg_xdepth) : 2;
   if (!cg_xdepth_ok(xdepth)) return FL_ERR_ARG_OUTOFRANGE;
   for (int k = 2; k < xdepth; ++k) FL_CHK(fl_ensure_vec(h, &h->Pr[k - 2]));
   DirRing ring = dir_ring2(h->P0, h->P1);
@@ -1322,14 +1244,11 @@ static int solve_cg(fl_poisson *h, const double *b, double *x, const fl_ksp_opts
   FL_CHK(cg_fin(h, 0, nsb, 5, h->hist, nhist));
   const bool ghosts = fl_any_ghost_exchange(h);
   if (ghosts) FL_CHK(fl_fill_ghosts(h, h->r));
-  // single rank: the last block of k_cg_A / k_cg_B performs the scalar update itself (no k_cg_fin launches)
-  const bool fusedfin_env = FL_VARIANT(fusedfin, 1) != 0;
   const bool overlap_env  = knob(K_overlap) != 0;  // 0: pack / transfer / unpack after the update kernel, on the handle's stream (A/B measurements, tests)
-  const bool fusedfin = !h->multi && variant != 1 && fusedfin_env;
-  // several ranks: the last block of k_cg_A / k_cg_B still reduces the rank's partial sums (no k_reduce launch); the
-  // all-reduce and the scalar kernel follow
-  const bool fusedsum = h->multi && variant != 1 && fusedfin_env;
-  if (fusedfin || fusedsum) FL_HIP(hipMemsetAsync(h->tickets, 0, sizeof(unsigned) * 2, s));
+  // single rank: the last block of k_cg_A / k_cg_Bq performs the scalar update itself (no k_cg_fin launches); several ranks: it still reduces
+  // the rank's partial sums (no k_reduce launch), the all-reduce and the scalar kernel follow
+  const bool fusedsum = h->multi;
+  FL_HIP(hipMemsetAsync(h->tickets, 0, sizeof(unsigned) * 2, s));
   auto fin_sums = [&](int mode) -> int {
     FL_CHK(h->comm.allreduce(s, h->sums, NSLOT));
     launch_cg_fin(s, mode, nullptr, 0, 0, h->sums, h->scal, h->hist, nhist);
@@ -1338,12 +1257,11 @@ static int solve_cg(fl_poisson *h, const double *b, double *x, const fl_ksp_opts
 
   ProfEvents               prof_events;
   std::vector<hipEvent_t> &pev = prof_events.ev;
-  if (o->profile) FL_CHK(prof_events.create(4 * (size_t)std::min(o->maxit, 4096)));  // around k_cg_A, around k_cg_Bq / k_cg_B
+  if (o->profile) FL_CHK(prof_events.create(4 * (size_t)std::min(o->maxit, 4096)));  // around k_cg_A, around k_cg_Bq
 
   const int every = o->check_every > 0 ? o->check_every : 16;
   int       it    = 0;
   int       nprof = 0;    // iterations whose kernels are bracketed by events so far
-  int       hostcur = 0;  // host's view of KspScal::cur (exact while the device has not stopped)
   bool      done  = false;
   while (!done) {
     const int stop = std::min(o->maxit, it + every);
@@ -1352,39 +1270,25 @@ static int solve_cg(fl_poisson *h, const double *b, double *x, const fl_ksp_opts
       const bool prof = o->profile > 0 && (it / xdepth) % o->profile == 0 && (size_t)(4 * nprof + 3) < pev.size();
       const int  pi   = 4 * nprof;
       if (prof) ++nprof;
-      if (variant == 1) {
-        launch_cg_pupdate(s, g, jac, h->r, h->P0, h->P1, h->scal);
-        if (ghosts) FL_CHK(fl_fill_ghosts(h, hostcur ? h->P0 : h->P1));
-        if (prof) FL_HIP(hipEventRecord(pev[pi], s));
-        launch_cg_apply_dot(s, g, h->P0, h->P1, h->q, h->xp, h->scal, h->partial);
-        if (prof) FL_HIP(hipEventRecord(pev[pi + 1], s));
-      } else {
-        if (prof) FL_HIP(hipEventRecord(pev[pi], s));
-        launch_cg_A(s, g, jac, plan, h->r, ring, h->q, h->xp, h->scal, h->partial, (fusedfin || fusedsum) ? h->tickets : nullptr, h->hist, nhist, fusedsum ? h->sums : nullptr);
-        if (prof) FL_HIP(hipEventRecord(pev[pi + 1], s));
-      }
-      const int modeA = storeq ? 1 : 3;  // q-free pair: k_cg_A does not touch x (see cg_fin_apply)
-      if (fusedsum) FL_CHK(fin_sums(modeA));
-      else if (!fusedfin) FL_CHK(cg_fin(h, modeA, nab, 1, h->hist, nhist));
-      hostcur ^= 1;
-      // several ranks: the boundary layers of the new r leave now (packed as r - alpha q), the transfers overlap k_cg_B
-      // q-free pair: k_cg_Bq owns the x-update -- all xdepth updates of a group of iterations on its last one (x is read and written
+      if (prof) FL_HIP(hipEventRecord(pev[pi], s));
+      launch_cg_A(s, g, jac, plan, h->r, ring, h->q, h->xp, h->scal, h->partial, h->tickets, h->hist, nhist, fusedsum ? h->sums : nullptr);
+      if (prof) FL_HIP(hipEventRecord(pev[pi + 1], s));
+      if (fusedsum) FL_CHK(fin_sums(3));  // k_cg_A does not touch x (see cg_fin_apply)
+      // several ranks: the boundary layers of the new r leave now (packed as r - alpha q), the transfers overlap k_cg_Bq
+      // k_cg_Bq owns the x-update -- all xdepth updates of a group of iterations on its last one (x is read and written
       // every xdepth-th iteration only), or one per iteration with FLUCA_CG_XBATCH=0
       const int  xu      = xbatch_env ? (it % xdepth == xdepth - 1 ? xdepth : 0) : 1;
       const bool xz      = xbatch_env && it == xdepth - 1;  // the first flush: x = 0 is not read
-      const bool overlap = ghosts && variant != 1 && h->multi && overlap_env;
+      const bool overlap = ghosts && h->multi && overlap_env;
       if (overlap) FL_CHK(fl_exchange_r_begin(h, h->r, h->q));
       if (prof) FL_HIP(hipEventRecord(pev[pi + 2], s));
-      if (storeq) launch_cg_B(s, g, jac, planB, h->q, h->r, h->scal, h->partial, h->partial_stride, (fusedfin || fusedsum) ? h->tickets + 1 : nullptr, h->hist, nhist, fusedsum ? h->sums : nullptr);
-      else launch_cg_Bq(s, g, jac, planB, xu, xz, ring, h->r, h->xp, h->scal, h->partial, h->partial_stride, (fusedfin || fusedsum) ? h->tickets + 1 : nullptr, h->hist, nhist, fusedsum ? h->sums : nullptr);
+      launch_cg_Bq(s, g, jac, plan, xu, xz, ring, h->r, h->xp, h->scal, h->partial, h->partial_stride, h->tickets + 1, h->hist, nhist, fusedsum ? h->sums : nullptr);
       if (prof) FL_HIP(hipEventRecord(pev[pi + 3], s));
       // the handle's stream joins the exchange BEFORE the all-reduce is enqueued: the two RCCL operations never run at the same time
-      // (one communicator, two streams), only the transfers and k_cg_B do
+      // (one communicator, two streams), only the transfers and k_cg_Bq do
       if (overlap) FL_CHK(fl_exchange_r_end(h, h->r));
-      const int modeB = (!storeq && xu) ? 4 : 2;
-      if (fusedsum) FL_CHK(fin_sums(modeB));
-      else if (!fusedfin) FL_CHK(cg_fin(h, modeB, planB.nblocks, 5, h->hist, nhist));
-      if (!overlap && ghosts && variant != 1) FL_CHK(fl_fill_ghosts(h, h->r));
+      if (fusedsum) FL_CHK(fin_sums(xu ? 4 : 2));
+      if (!overlap && ghosts) FL_CHK(fl_fill_ghosts(h, h->r));
     }
     FL_CHK(fl_poll_scal(h));
     if (h->scal_host->reason != 0 || it >= o->maxit) done = true;
@@ -1715,48 +1619,16 @@ extern "C" int fl_poisson_comm_info(fl_poisson *h, fl_comm_info *out)
   return FL_SUCCESS;
 }
 
-// ------------------------------------------------------------------------------------------------ kernel micro-bench (tools/kbench.py)
-// Not part of the public C-ABI (not declared in fluca_hip.h): times one hot kernel in isolation with HIP events.
-//   kernel 0: k_cg_A (ry, pf, nchunk)   1: k_cg_B (ry, nchunk)   2: streaming reference with ry reads / pf writes
+// ------------------------------------------------------------------------------------------------ kernel micro-bench (bench.py, tools/sbench.py)
+// Not part of the public C-ABI (not declared in fluca_hip.h): times one kernel in isolation with HIP events.
+//   kernel 0: k_cg_A on 128 x (NW * RY) tiles, ry = 10 * RY + NW, nchunk z chunks (0: the chunking rule), pf / 100 = XCD-contiguous block order
+//   kernel 2: streaming reference with ry reads / pf writes   3: parametric stream, ry = 10 * NR + NW, pf = 10 * U + NT, nchunk = blocks
 extern "C" int fldbg_bench(fl_poisson *h, int kernel, int ry, int pf, int nchunk, int reps, const double *src_dev, double *ms_out, int *nblocks_out)
 {
   if (!h || !ms_out) return FL_ERR_ARG_NULL;
-#ifndef FL_KBENCH_VARIANTS
-  if (kernel != 0 && kernel != 2 && kernel != 3) return FL_ERR_SUP;  // the product keeps what bench.py measures with: k_cg_A and the streaming probes
-#endif
+  if (kernel != 0 && kernel != 2 && kernel != 3) return FL_ERR_SUP;
   FL_HIP(hipSetDevice(h->device));
   const GridP &g = h->g;
-  if (kernel == 8) {
-    // experiment: forget the current padded vectors WITHOUT freeing them (they stay allocated, so the next set must land
-    // on different physical memory)
-    FL_HIP(hipStreamSynchronize(h->stream));
-    h->vec_bases.clear();
-    h->vec_bytes = 0;
-    h->nvec = 0;
-    h->slab = nullptr;
-    for (double **v : {&h->r, &h->P0, &h->P1, &h->q, &h->xp, &h->w0, &h->w1, &h->w2}) *v = nullptr;
-    for (double *&v : h->Pr) v = nullptr;
-    *ms_out = 0.;
-    return FL_SUCCESS;
-  }
-  if (kernel == 9) {
-    // experiment: drop every padded vector so that the next call gets fresh physical memory (ry extra junk allocations
-    // of pf MiB each are made first and kept, to shift the placement)
-    FL_HIP(hipStreamSynchronize(h->stream));
-    for (void *p : h->vec_bases) (void)hipFree(p);
-    h->vec_bases.clear();
-    h->vec_bytes = 0;
-    h->nvec = 0;
-    h->slab = nullptr;
-    for (double **v : {&h->r, &h->P0, &h->P1, &h->q, &h->xp, &h->w0, &h->w1, &h->w2}) *v = nullptr;
-    for (double *&v : h->Pr) v = nullptr;
-    for (int a = 0; a < ry; ++a) {
-      void *junk = nullptr;
-      FL_HIP(hipMalloc(&junk, (size_t)pf << 20));
-    }
-    *ms_out = 0.;
-    return FL_SUCCESS;
-  }
   for (double **v : {&h->r, &h->P0, &h->P1, &h->q, &h->xp, &h->w0}) FL_CHK(fl_ensure_vec(h, v));
   hipStream_t s = h->stream;
   if (src_dev) {
@@ -1765,28 +1637,17 @@ extern "C" int fldbg_bench(fl_poisson *h, int kernel, int ry, int pf, int nchunk
     launch_pad_copy(s, g, src_dev, h->xp);
     launch_pad_copy(s, g, src_dev, h->q);
   }
-  // ry = 10*RY + NW(4|8) ; pf = 100*remap + 10*PF + NT
-  PlanA plan = (kernel <= 1) ? plan_tiles(g, ry / 10, ry % 10, nchunk, 512) : plan_cg_A(g, 0, 0);
-  if (kernel <= 1) {
-    plan.remap = pf / 100;
-    plan.pf    = (pf / 10) % 10;
-    plan.nt    = pf % 10;
-  }
+  PlanA plan = kernel == 0 ? plan_tiles(g, ry / 10, ry % 10, nchunk, 512) : plan_cg_A(g, 0, 0);
+  if (kernel == 0) plan.remap = pf / 100;
   FL_CHK(fl_ensure_partials(h, plan.nblocks));
   KspScal &S = *h->scal_host;
   std::memset(&S, 0, sizeof(S));
   S.beta = 0.5; S.alpha = 1e-3; S.zshift = 1e-4; S.ncell_global = (double)h->ncell; S.maxit = 1 << 30; S.pending_x = 1; S.nullspace = 1; S.rz = 1.;
   FL_HIP(hipMemcpyAsync(h->scal, h->scal_host, sizeof(KspScal), hipMemcpyHostToDevice, s));
-  if (FL_VARIANT(print_ptrs, 0) && kernel == 0)
-    std::fprintf(stderr, "[ptrs] r=%p P0=%p P1=%p q=%p xp=%p w0=%p\n", (void *)h->r, (void *)h->P0, (void *)h->P1, (void *)h->q, (void *)h->xp, (void *)h->w0);
   auto once = [&]() {
     if (kernel == 0) launch_cg_A(s, g, true, plan, h->r, dir_ring2(h->P0, h->P1), h->q, h->xp, h->scal, h->partial, nullptr, nullptr, 0);
-    else if (kernel == 1) launch_cg_B(s, g, true, plan, h->q, h->r, h->scal, h->partial, h->partial_stride, nullptr, nullptr, 0);
     else if (kernel == 2) launch_stream_ref(s, ry, pf, (int64_t)(h->padlen - 256) / 2, h->r, h->P0, h->xp, h->P1, h->q, h->w0);
-    else {
-      // kernel 3: parametric stream.  ry = 10*NR + NW, pf = 10*U + NT, nchunk = blocks
-      launch_stream_par(s, ry / 10, ry % 10, pf / 10, pf % 10, nchunk, (int64_t)(h->padlen - 256) / 2, h->r, h->P0, h->xp, h->P1, h->q, h->w0);
-    }
+    else launch_stream_par(s, ry / 10, ry % 10, pf / 10, pf % 10, nchunk, (int64_t)(h->padlen - 256) / 2, h->r, h->P0, h->xp, h->P1, h->q, h->w0);
   };
   once();
   once();
@@ -1808,12 +1669,10 @@ extern "C" int fldbg_bench(fl_poisson *h, int kernel, int ry, int pf, int nchunk
 //   k_cg_A / k_cg_Bq (plan_cg_A):       0 ry, 1 nw, 2 tiles_x, 3 tiles_y, 4 nchunk, 5 zc, 6 nblocks
 //   k_cheb2 (fl_cheb2_plan):            7 nw, 8 tiles_x, 9 tiles, 10 nchunk, 11 zc, 12 nblocks
 //   k_apply_pc, k_bcgs_pw (tile_plan):  13 ry, 14 tiles_x, 15 nchunk, 16 zc, 17 nblocks
-//   k_project_six:                      18 nxcd, 19 nseg, 20 nbx (blocks per XCD slab), 21 items (row segments per slab)
+//   k_project_six (project_six_plan):   18 nxcd, 19 nseg, 20 nbx (blocks per XCD slab), 21 items (row segments per slab)
 //   k_schur_var (schur_var_plan):       22 per_xcd, 23 nseg, 24 band, 25 fixed_seg, 26 items
-//   k_mom2 / k_mom3:                    27 t2x, 28 t2chunk, 29 t2zc, 30 t2blocks
-// The CG, Chebyshev, tile and Schur plans are the functions the launchers call.  The project-six launch (launch_project_six, fl_kernels.hip) and
-// the t2 tiling (fl_momentum_create, fl_momentum.hip) are computed inline there and restated below with their default experiment switches:
-// those two files are fingerprinted by the committed counter passes (fluca_amd/provenance.py), so a change of either must be made in both places.
+//   k_mom2 / k_mom3 (mom_plan):         27 t2x, 28 t2chunk, 29 t2zc, 30 t2blocks
+// Every field comes from the plan function the launcher itself calls.
 constexpr int FLDBG_NPLAN = 31;
 extern "C" int fldbg_launch_plans(int nx, int ny, int nz, int *out, int nout)
 {
@@ -1828,24 +1687,15 @@ extern "C" int fldbg_launch_plans(int nx, int ny, int nz, int *out, int nout)
   const Cheb2Plan    c  = fl_cheb2_plan(g);
   const TP           t  = tile_plan(g);
   const SchurVarPlan sv = schur_var_plan(g);
-  // launch_project_six: 1024 blocks of four waves per XCD slab (8 slabs), a multiple of the row segments, no more than the rows of a slab need
-  const int     nseg6 = (nx + 127) / 128, nxcd = ny < 8 ? 1 : 8;
-  const int64_t items6 = (int64_t)nseg6 * ((ny + nxcd - 1) / nxcd) * nz;
-  int64_t       nbx = std::max<int64_t>(1, std::min<int64_t>((items6 + 3) / 4, (int64_t)1024 * (8 / nxcd)));
-  nbx = (nbx + nseg6 - 1) / nseg6 * nseg6;
-  // fl_momentum_create: 128 x 8 tiles of k_mom2 / k_mom3, about 1024 blocks, z chunks of at least 8 planes
-  const int t2x = (nx + 127) / 128, tiles2 = t2x * ((ny + 7) / 8);
-  int       nc2 = std::max(1, (1024 + tiles2 / 2) / tiles2);
-  nc2 = std::max(1, std::min(std::min(nc2, std::max(1, nz / 8)), nz));
-  if (tiles2 * nc2 > MAX_PARTIAL_BLOCKS) nc2 = std::max(1, MAX_PARTIAL_BLOCKS / tiles2);
-  const int t2zc = (nz + nc2 - 1) / nc2, t2chunk = (nz + t2zc - 1) / t2zc;
-  if (items6 > INT32_MAX || nbx > INT32_MAX || sv.items > INT32_MAX) return FL_ERR_ARG_OUTOFRANGE;
+  const ProjectSixPlan p6 = project_six_plan(g);
+  const MomPlan        m2 = mom_plan(g);
+  if (p6.items > INT32_MAX || p6.nbx > INT32_MAX || sv.items > INT32_MAX) return FL_ERR_ARG_OUTOFRANGE;
   const int v[FLDBG_NPLAN] = {a.ry, a.nw, a.tiles_x, a.tiles_y, a.nchunk, a.zc, a.nblocks,
                               c.nw, c.tiles_x, c.tiles, c.nchunk, c.zc, c.nblocks,
                               t.ry, t.tiles_x, t.nchunk, t.zc, t.nblocks,
-                              nxcd, nseg6, (int)nbx, (int)items6,
+                              p6.nxcd, p6.nseg, (int)p6.nbx, (int)p6.items,
                               sv.per_xcd, sv.nseg, sv.band, sv.fixed_seg, (int)sv.items,
-                              t2x, t2chunk, t2zc, tiles2 * t2chunk};
+                              m2.t2x, m2.t2chunk, m2.t2zc, m2.t2blocks};
   std::memcpy(out, v, sizeof(v));
   return FLDBG_NPLAN;
 }
@@ -1864,174 +1714,3 @@ extern "C" int fldbg_mg_restrict_fused(int nx, int ny, int nz)
   return fl_residual_restrict_fusable(g) ? 1 : 0;
 }
 
-#ifdef FL_KBENCH_VARIANTS  // experiments behind the placement notes of DESIGN.md: not in the product
-// Experiment behind fl_poisson_tune_placement (tools/experiments/pool_probe.py): K vectors allocated once, M random
-// assignments of five of them to the roles (r, p0, p1, q, x) of k_cg_A, probe time of each.
-extern "C" int fldbg_pool_probe(fl_poisson *h, int K, int M, unsigned seed, double *ms_out, int *sel_out)
-{
-  if (!h || !ms_out || K < 5 || K > 64) return FL_ERR_ARG_WRONG;
-  FL_HIP(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  PlanA       plan = plan_cg_A(h->g, 0, 0);
-  plan.probe       = 1;
-  FL_CHK(fl_ensure_partials(h, plan.nblocks));
-  std::vector<double *> pool(K, nullptr);
-  for (int k = 0; k < K; ++k) {
-    FL_HIP(hipMalloc((void **)&pool[k], sizeof(double) * h->padlen));
-    FL_HIP(hipMemsetAsync(pool[k], 0x3f, sizeof(double) * h->padlen, s));
-  }
-  KspScal *scal2 = nullptr;
-  FL_HIP(hipMalloc((void **)&scal2, 2 * sizeof(KspScal)));
-  KspScal S2[2];
-  std::memset(S2, 0, sizeof(S2));
-  for (int a = 0; a < 2; ++a) {
-    S2[a].beta = 0.5; S2[a].alpha = 1e-3; S2[a].zshift = 1e-4; S2[a].ncell_global = (double)h->ncell; S2[a].maxit = 1 << 30; S2[a].cur = a;
-  }
-  FL_HIP(hipMemcpy(scal2, S2, sizeof(S2), hipMemcpyHostToDevice));
-  unsigned st = seed * 2654435761u + 12345u;
-  auto     rnd = [&]() { st = st * 1664525u + 1013904223u; return st >> 8; };
-  for (int m = 0; m < M; ++m) {
-    int sel[5];
-    for (int a = 0; a < 5; ++a) {
-      bool ok;
-      do {
-        sel[a] = (int)(rnd() % (unsigned)K);
-        ok     = true;
-        for (int b = 0; b < a; ++b) ok &= sel[b] != sel[a];
-      } while (!ok);
-    }
-    auto probe = [&](int reps) {
-      for (int r = 0; r < reps; ++r)
-        for (int par = 0; par < 2; ++par) launch_cg_A(s, h->g, true, plan, pool[sel[0]], dir_ring2(pool[sel[1]], pool[sel[2]]), pool[sel[3]], pool[sel[4]], scal2 + par, h->partial, nullptr, nullptr, 0);
-    };
-    probe(1);
-    FL_HIP(hipEventRecord(h->ev0, s));
-    probe(2);
-    FL_HIP(hipEventRecord(h->ev1, s));
-    FL_HIP(hipStreamSynchronize(s));
-    float ms = 0.f;
-    FL_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    ms_out[m] = ms / 4.;
-    if (sel_out)
-      for (int a = 0; a < 5; ++a) sel_out[m * 5 + a] = sel[a];
-  }
-  (void)hipFree(scal2);
-  for (double *p : pool) (void)hipFree(p);
-  return 0;
-}
-
-// Experiment behind the placement note in DESIGN.md (tools/experiments/arena_probe.py): one arena allocated once, six
-// streams (nr reads, nw writes of n doubles each) placed at caller-chosen byte offsets inside it, launch time of the plain
-// streaming kernel.  Not part of the public C-ABI.
-extern "C" int fldbg_arena_probe(fl_poisson *h, int64_t arena_bytes, const int64_t *off_bytes, int64_t n, int nr, int nw, int reps, double *ms_out, void **arena_out)
-{
-  if (!h || !off_bytes || !ms_out) return FL_ERR_ARG_NULL;
-  FL_HIP(hipSetDevice(h->device));
-  static void   *arena = nullptr;
-  static int64_t cap   = 0;
-  if (arena_bytes < 0) {  // release
-    if (arena) (void)hipFree(arena);
-    arena = nullptr;
-    cap   = 0;
-    return FL_SUCCESS;
-  }
-  if (cap < arena_bytes) {
-    if (arena) (void)hipFree(arena);
-    arena = nullptr;
-    FL_HIP(hipMalloc(&arena, (size_t)arena_bytes));
-    FL_HIP(hipMemset(arena, 0, (size_t)arena_bytes));
-    cap = arena_bytes;
-  }
-  if (arena_out) *arena_out = arena;
-  double *v[6];
-  for (int a = 0; a < 6; ++a) {
-    if (off_bytes[a] < 0 || off_bytes[a] + n * 8 > cap || (off_bytes[a] & 15)) return FL_ERR_ARG_OUTOFRANGE;
-    v[a] = (double *)((char *)arena + off_bytes[a]);
-  }
-  hipStream_t s = h->stream;
-  auto once = [&]() { launch_stream_ref(s, nr, nw, n / 2, v[0], v[1], v[2], v[3], v[4], v[5]); };
-  once();
-  FL_HIP(hipEventRecord(h->ev0, s));
-  for (int a = 0; a < reps; ++a) once();
-  FL_HIP(hipEventRecord(h->ev1, s));
-  FL_HIP(hipStreamSynchronize(s));
-  FL_HIP(hipGetLastError());
-  float ms = 0.f;
-  FL_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  *ms_out = ms / reps;
-  return FL_SUCCESS;
-}
-
-// tools/experiments/arena_probe3.py: the plain streaming kernel on six caller-owned device pointers.  Not part of the C-ABI.
-extern "C" int fldbg_stream_ptrs(fl_poisson *h, void *const *ptrs, int64_t n, int nr, int nw, int reps, double *ms_out)
-{
-  if (!h || !ptrs || !ms_out) return FL_ERR_ARG_NULL;
-  FL_HIP(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  double     *v[6];
-  for (int a = 0; a < 6; ++a) v[a] = (double *)ptrs[a];
-  auto once = [&]() { launch_stream_ref(s, nr, nw, n / 2, v[0], v[1], v[2], v[3], v[4], v[5]); };
-  once();
-  once();
-  FL_HIP(hipEventRecord(h->ev0, s));
-  for (int a = 0; a < reps; ++a) once();
-  FL_HIP(hipEventRecord(h->ev1, s));
-  FL_HIP(hipStreamSynchronize(s));
-  FL_HIP(hipGetLastError());
-  float ms = 0.f;
-  FL_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  *ms_out = ms / reps;
-  return FL_SUCCESS;
-}
-
-// tools/experiments/phase_scan.py: k_cg_A (kernel 0: pointers r, P0, P1, q, x) or the fused two-step Chebyshev kernel
-// (kernel 1: X0, X1, B, D0, D1) on five caller-owned padded vectors, both parities of the double buffers.  Not part of the C-ABI.
-extern "C" int fldbg_kernel_ptrs(fl_poisson *h, int kernel, void *const *ptrs, int nchunk, int reps, double *ms_out)
-{
-  if (!h || !ptrs || !ms_out) return FL_ERR_ARG_NULL;
-  FL_HIP(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  double     *v[5];
-  for (int a = 0; a < 5; ++a) v[a] = (double *)ptrs[a];
-  KspScal *scal2 = nullptr;
-  FL_HIP(hipMalloc((void **)&scal2, 2 * sizeof(KspScal)));
-  KspScal S2[2];
-  std::memset(S2, 0, sizeof(S2));
-  for (int a = 0; a < 2; ++a) {
-    S2[a].beta = 0.5; S2[a].alpha = 1e-3; S2[a].zshift = 1e-4; S2[a].ncell_global = (double)h->ncell; S2[a].maxit = 1 << 30; S2[a].cur = a; S2[a].dcur = a;
-    S2[a].cheb_rho = 0.3; S2[a].cheb_c = 0.2; S2[a].mu = 1.2; S2[a].ck = 1.5; S2[a].ckm1 = 1.2; S2[a].omegaprod = 2.4; S2[a].scale = 0.9;
-  }
-  FL_HIP(hipMemcpy(scal2, S2, sizeof(S2), hipMemcpyHostToDevice));
-  PlanA     plan = plan_cg_A(h->g, 0, nchunk);
-  Cheb2Plan cp   = fl_cheb2_plan(h->g);
-  if (nchunk > 0 && kernel == 1) {
-    cp.nchunk  = nchunk;
-    cp.zc      = (h->g.nz + nchunk - 1) / nchunk;
-    cp.nchunk  = (h->g.nz + cp.zc - 1) / cp.zc;
-    cp.nblocks = cp.tiles * cp.nchunk;
-  }
-  FL_CHK(fl_ensure_partials(h, std::max(plan.nblocks, cp.nblocks)));
-  KspScal *keep = h->scal;
-  auto     once = [&]() {
-    for (int par = 0; par < 2; ++par) {
-      if (kernel == 0) launch_cg_A(s, h->g, true, plan, v[0], dir_ring2(v[1], v[2]), v[3], v[4], scal2 + par, h->partial, nullptr, nullptr, 0);
-      else {
-        h->scal = scal2 + par;
-        fl_launch_cheb2(h, cp, true, v[0], v[1], v[2], v[3], v[4]);
-      }
-    }
-  };
-  once();
-  FL_HIP(hipEventRecord(h->ev0, s));
-  for (int a = 0; a < reps; ++a) once();
-  FL_HIP(hipEventRecord(h->ev1, s));
-  FL_HIP(hipStreamSynchronize(s));
-  h->scal = keep;
-  (void)hipFree(scal2);
-  FL_HIP(hipGetLastError());
-  float ms = 0.f;
-  FL_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  *ms_out = ms / (2 * reps);
-  return FL_SUCCESS;
-}
-#endif  // FL_KBENCH_VARIANTS

@@ -37,8 +37,6 @@ void launch_apply(hipStream_t, const GridP &, const double *, double *, int);
 void launch_diagonal(hipStream_t, const GridP &, double *);
 void launch_rhs(hipStream_t, const GridP &, const double *, const double *, const double *, const double *, const double *, const double *, const double *, double *);
 void launch_face_plane0(hipStream_t, const GridP &, const double *, double *, int);
-void launch_project_faces(hipStream_t, const GridP &, const double *, double *, int);
-void launch_project_cells(hipStream_t, const GridP &, const double *, double *, int);
 void launch_gst_bc(hipStream_t, const GridP &, const double *, double *, int, int, double, int add = 0);
 void launch_bc_add_cells(hipStream_t, const GridP &, const double *, double *, int, int, double);
 void launch_pressure_update(hipStream_t, int64_t, int, const double *, const double *, double *, double *);
@@ -47,23 +45,12 @@ void launch_cg_fin(hipStream_t, int, const double *, int, int, const double *, K
 int  stream_blocks(const GridP &);
 void launch_cg_init(hipStream_t, const GridP &, bool, const double *, double *, double *, double *, int, int);
 void launch_cg_finish(hipStream_t, const GridP &, const DirRing &, const double *, double *, const KspScal *, int);
-struct PlanA {
-  int ry, nw, tiles_x, tiles_y, nchunk, zc, nblocks, pf, nt, remap, probe;
-  int sq, qb;  // keep in step with the definition in fl_kernels.hip
-};
-PlanA plan_tiles(const GridP &, int ry, int nw, int nchunk_force, int target_blocks, int min_zc = 8);
-PlanA plan_cg_A(const GridP &, int, int);
-PlanA plan_cg_B(const GridP &);
 void  launch_cg_A(hipStream_t, const GridP &, bool, const PlanA &, const double *r, const DirRing &P, double *q, double *x, KspScal *, double *, unsigned *, double *, int, double *sums = nullptr);
 bool  cg_xdepth_ok(int k);  // the direction-ring depths k_cg_Bq is built for (2, 3, 4, 8)
 void  launch_cg_Bq(hipStream_t, const GridP &, bool, const PlanA &, int xu, bool xz, const DirRing &P, double *r, double *x, KspScal *, double *partial, int stride, unsigned *counter, double *hist,
                    int nhist, double *sums = nullptr);
-void  launch_cg_B(hipStream_t, const GridP &, bool, const PlanA &, const double *, double *, KspScal *, double *, int, unsigned *, double *, int, double *sums = nullptr);
 void  launch_stream_ref(hipStream_t, int, int, int64_t, const double *, const double *, const double *, double *, double *, double *);
 void  launch_stream_par(hipStream_t, int, int, int, int, int, int64_t, const double *, const double *, const double *, double *, double *, double *);
-void  launch_cg_pupdate(hipStream_t, const GridP &, bool, const double *, double *, double *, const KspScal *);
-int   apply_dot_blocks(const GridP &);
-void  launch_cg_apply_dot(hipStream_t, const GridP &, const double *, const double *, double *, double *, const KspScal *, double *);
 
 // ------------------------------------------------------------------------------------------------ transports
 
@@ -325,7 +312,6 @@ struct fl_poisson {
   std::vector<void *> tables;
   int64_t     ncell = 0, nface[3] = {0, 0, 0};
   size_t      padlen = 0;
-  int         nv_il = 1, sx0 = 0;  // row-interleave factor of the padded vectors and the un-interleaved row length
   int         gw = 1;              // ghost layers of the padded layout around the owned block (2 on several ranks: fl_fill_ghosts_deep)
   // fused two-step Chebyshev (fl_cheb2.hip) on several ranks: the ranks' AGREED answers to "legal on my block" [0] and "legal and large
   // enough to pay" [1], -1 = not asked yet (one all-reduce per handle / multigrid level: fl_cheb2_agree)
@@ -338,7 +324,6 @@ struct fl_poisson {
   double *sv_ring[12] = {};  // several ranks: [b] the ring of a^-1 received across boundary b, [6 + b] the plane sent across it (fl_schur_var.hip; freed with h->tables)
   double *rb = nullptr;   // where the three-step sweep from a zero guess writes the updated right-hand side; swaps roles with r afterwards
   std::vector<void *> vec_bases;
-  void               *slab = nullptr;
   // placement (fl_api.hip): one arena, the five CG vectors in a window found by probing, two side pools for the rest
   void  *arena = nullptr;
   size_t arena_bytes = 0, pool_vec = 0;
@@ -353,7 +338,7 @@ struct fl_poisson {
   double *partial = nullptr;
   int     partial_stride = 0;
   double *sums = nullptr;
-  unsigned *tickets = nullptr;  // [2] device-scope arrival counters of the fused finalisation (k_cg_A, k_cg_B)
+  unsigned *tickets = nullptr;  // [2] device-scope arrival counters of the fused finalisation (k_cg_A, k_cg_Bq)
   KspScal *scal = nullptr, *scal_host = nullptr;
   double  *hist = nullptr;
   int      hist_cap = 0;
@@ -363,7 +348,7 @@ struct fl_poisson {
   size_t   xcap = 0;  // doubles each of them holds
   Comm     comm;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // halo exchange overlapped with k_cg_B (fl_exchange_r_begin / _end): its own stream and the two events that order it
+  // halo exchange overlapped with k_cg_Bq (fl_exchange_r_begin / _end): its own stream and the two events that order it
   hipStream_t comm_stream = nullptr;
   hipEvent_t  ev_packed = nullptr, ev_ghosts = nullptr;
   hipEvent_t  ev_upload = nullptr;  // behind the last fl_poisson_upload (fl_poisson_upload_fence waits for it)

@@ -189,83 +189,12 @@ __global__ void __launch_bounds__(256) k_ibm_interp(IbmP P, const int *__restric
   }
 }
 
-// f[c*ncell + x] += sum_l w_l(x) F[c*L + l] dV_l / (hx hy hz), gather over the tile's bin, markers in ascending id order
-#ifdef FL_KBENCH_VARIANTS  // round 1's spreading loop (A/B runs)
-__global__ void __launch_bounds__(256) k_ibm_spread_v1(IbmP P, const int *__restrict__ i0, const double *__restrict__ w, const int *__restrict__ off, const int *__restrict__ list, const int *__restrict__ active, int ncomp, int64_t ncell, const double *__restrict__ F,
-                                                      const double *__restrict__ dV, double *__restrict__ f)
-{
-  __shared__ int    sraw[BIN_CHUNK];
-  __shared__ int    si0[3][BIN_CHUNK];
-  __shared__ double sw[3][4][BIN_CHUNK];
-  __shared__ double sF[3][BIN_CHUNK];
-  const int tile = active[blockIdx.x];  // only tiles with a non-empty bin are launched
-  const int beg = off[tile], end = off[tile + 1];
-  if (beg == end) return;
-  const int tx = tile % P.nt[0], ty = (tile / P.nt[0]) % P.nt[1], tz = tile / (P.nt[0] * P.nt[1]);
-  const bool   uni = P.uniform[0] && P.uniform[1] && P.uniform[2];
-  const double ih  = uni ? 1. / (P.h[0] * P.h[1] * P.h[2]) : 1.;  // stretched grids: 1 / (volume of the target cell), applied per cell below
-  // this thread's two cells: (ci, cj, ck) and (ci, cj, ck + 4)
-  const int li = threadIdx.x & 7, lj = (threadIdx.x >> 3) & 7, lk = threadIdx.x >> 6;
-  const int ci = tx * TB + li, cj = ty * TB + lj;
-  double    acc[2][3] = {{0., 0., 0.}, {0., 0., 0.}};
-  // the bin is staged in id-sorted chunks; since every chunk is rank-sorted and chunks are visited in list order, the
-  // whole list must already be chunk-monotone -> sort the FULL bin when it fits (the common case), else fall back to
-  // a two-level order (chunk order = list order) which is still deterministic because k_ibm_sort_bins sorted the list.
-  for (int c0 = beg; c0 < end; c0 += BIN_CHUNK) {
-    const int n = min(BIN_CHUNK, end - c0);
-    __syncthreads();
-    if ((int)threadIdx.x < n) sraw[threadIdx.x] = list[c0 + threadIdx.x];
-    __syncthreads();
-    if ((int)threadIdx.x < n) {
-      const int m = sraw[threadIdx.x];
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        si0[d][threadIdx.x] = i0[d * P.L + m];
-#pragma unroll
-        for (int a = 0; a < 4; ++a) sw[d][a][threadIdx.x] = w[(d * 4 + a) * P.L + m];
-      }
-      const double dv = dV[m] * ih;
-      for (int c = 0; c < 3; ++c) sF[c][threadIdx.x] = c < ncomp ? F[(int64_t)c * P.L + m] * dv : 0.;
-    }
-    __syncthreads();
-    if (ci < P.n[0] && cj < P.n[1]) {
-      for (int e = 0; e < n; ++e) {
-        int a = ci + P.lo[0] - si0[0][e], b = cj + P.lo[1] - si0[1][e];
-        if (P.periodic[0]) { if (a < 0) a += P.ng[0]; else if (a >= P.ng[0]) a -= P.ng[0]; }
-        if (P.periodic[1]) { if (b < 0) b += P.ng[1]; else if (b >= P.ng[1]) b -= P.ng[1]; }
-        if (a < 0 || a >= P.S || b < 0 || b >= P.S) continue;
-        const double wxy = sw[0][a][e] * sw[1][b][e];
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-          const int ck = tz * TB + lk + 4 * half;
-          int       c3 = ck + P.lo[2] - si0[2][e];
-          if (P.periodic[2]) { if (c3 < 0) c3 += P.ng[2]; else if (c3 >= P.ng[2]) c3 -= P.ng[2]; }
-          if (ck >= P.n[2] || c3 < 0 || c3 >= P.S) continue;
-          const double wt = wxy * sw[2][c3][e];
-          acc[half][0] += wt * sF[0][e];
-          acc[half][1] += wt * sF[1][e];
-          acc[half][2] += wt * sF[2][e];
-        }
-      }
-    }
-  }
-  if (ci < P.n[0] && cj < P.n[1])
-    for (int half = 0; half < 2; ++half) {
-      const int ck = tz * TB + lk + 4 * half;
-      if (ck >= P.n[2]) continue;
-      const int64_t cell = ((int64_t)ck * P.n[1] + cj) * P.n[0] + ci;
-      const double  vinv = uni ? 1. : P.idx[0][ci] * P.idx[1][cj] * P.idx[2][ck];
-      for (int c = 0; c < ncomp && c < 3; ++c)
-        if (acc[half][c] != 0.) f[(int64_t)c * ncell + cell] += acc[half][c] * vinv;
-    }
-}
-#endif  // FL_KBENCH_VARIANTS
-
-// Round 4.  The loop above is a chain of dependent LDS reads per marker (its first cell -> the index into its weights -> the weight) behind two
+// f[c*ncell + x] += sum_l w_l(x) F[c*L + l] dV_l / (hx hy hz), gather over the tile's bin, markers in ascending id order.
+// A loop that looks every marker's weights up (its first cell -> the index into its weights -> the weight) is a chain of dependent LDS reads behind two
 // divergent tests, one wave per SIMD and block: about 300 cycles per marker and 150 markers per bin of config 4's sphere.  Here the staging step expands
 // every marker's 1-D weights onto the tile's eight cells per axis (zero outside the support, periodic wrap and all), so the loop reads four weights and
 // three forces at addresses that depend on nothing but the thread and the loop counter -- no test, no dependent read, unrolled.  A cell outside a marker's
-// support adds an exact zero, so the sums (ascending marker id per cell, as before) are the same bits.
+// support adds an exact zero, so the sums (ascending marker id per cell) are the same bits as that loop's.
 __global__ void __launch_bounds__(256) k_ibm_spread(IbmP P, const int *__restrict__ i0, const double *__restrict__ w, const int *__restrict__ off, const int *__restrict__ list, const int *__restrict__ active, int ncomp, int64_t ncell, const double *__restrict__ F,
                                                     const double *__restrict__ dV, double *__restrict__ f)
 {
@@ -480,37 +409,13 @@ extern "C" int fl_ibm_interp(fl_ibm *m, int ncomp, const double *u, double *U)
   return FL_SUCCESS;
 }
 
-// bin statistics of the current marker positions (experiments): tiles with a non-empty bin, entries of all bins, the largest bin
-#ifdef FL_KBENCH_VARIANTS  // bin statistics for tools/ibm_bench.py
-extern "C" int fldbg_ibm_stats(fl_ibm *m, int *nactive, int *entries, int *maxbin)
-{
-  if (!m) return FL_ERR_ARG_NULL;
-  std::vector<int> off((size_t)m->ntiles + 1);
-  FL_HIP(hipStreamSynchronize(m->gp->stream));
-  FL_HIP(hipMemcpy(off.data(), m->off, sizeof(int) * off.size(), hipMemcpyDeviceToHost));
-  int mx = 0;
-  for (int t = 0; t < m->ntiles; ++t) mx = std::max(mx, off[(size_t)t + 1] - off[(size_t)t]);
-  if (nactive) *nactive = m->nactive;
-  if (entries) *entries = off[(size_t)m->ntiles];
-  if (maxbin) *maxbin = mx;
-  return FL_SUCCESS;
-}
-#endif  // FL_KBENCH_VARIANTS
-
 extern "C" int fl_ibm_spread(fl_ibm *m, int ncomp, const double *F, const double *dV, double *f)
 {
   if (!m || !F || !dV || !f) return FL_ERR_ARG_NULL;
   if (ncomp < 1 || ncomp > 3) return FL_ERR_ARG_OUTOFRANGE;
   fl_poisson *h = m->gp;
   FL_HIP(hipSetDevice(h->device));
-  if (m->nactive > 0) {
-#ifdef FL_KBENCH_VARIANTS
-    if (FL_VARIANT(ibm_spread, 0) == 1)  // round 1's loop over the bin (A/B runs)
-      hipLaunchKernelGGL(k_ibm_spread_v1, dim3(m->nactive), dim3(256), 0, h->stream, m->P, m->i0, m->w, m->off, m->list, m->active, ncomp, h->ncell, F, dV, f);
-    else
-#endif
-      hipLaunchKernelGGL(k_ibm_spread, dim3(m->nactive), dim3(256), 0, h->stream, m->P, m->i0, m->w, m->off, m->list, m->active, ncomp, h->ncell, F, dV, f);
-  }
+  if (m->nactive > 0) hipLaunchKernelGGL(k_ibm_spread, dim3(m->nactive), dim3(256), 0, h->stream, m->P, m->i0, m->w, m->off, m->list, m->active, ncomp, h->ncell, F, dV, f);
   FL_HIP(hipGetLastError());
   return FL_SUCCESS;
 }

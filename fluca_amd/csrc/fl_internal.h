@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <vector>
@@ -104,5 +105,43 @@ struct KspScal {
 
 constexpr int MAX_PARTIAL_BLOCKS = 4096;
 constexpr int NSLOT              = 8;  // partial-sum slots per kernel
+
+// ---- launch plans: host arithmetic only, shared by the launchers and fldbg_launch_plans (fl_api.hip) ---------------------------------
+// The z chunks of a tile walk (a 128-wide tile marching through its chunk of planes), one rule for every plan that cuts the z axis: about
+// target_blocks blocks over `tiles` tiles, chunks of at least min_zc planes (every chunk pays a prologue of two planes: 8 keeps it <= 25 %),
+// never more chunks than planes ...
+inline int z_chunk_count(int tiles, int nz, int target_blocks, int min_zc = 8)
+{
+  const int nchunk = std::min(std::max(1, (target_blocks + tiles / 2) / tiles), std::max(1, nz / min_zc));
+  return std::max(1, std::min(nchunk, nz));
+}
+// ... and every chunk holds a plane: zc planes each, the count that leaves none empty
+struct ZChunks {
+  int nchunk, zc;
+};
+inline ZChunks z_chunks(int nz, int nchunk)
+{
+  const int zc = (nz + nchunk - 1) / nchunk;
+  return {(nz + zc - 1) / zc, zc};
+}
+// tiling of k_cg_A / k_cg_Bq: 128 x (nw * ry) tiles, nchunk z chunks of zc planes
+struct PlanA {
+  int ry, nw, tiles_x, tiles_y, nchunk, zc, nblocks, remap, probe;
+  int qb;  // k_cg_A stores q on the six boundary layers of the block (the overlapped halo exchange packs r - alpha q there)
+};
+PlanA plan_tiles(const GridP &, int ry, int nw, int nchunk_force, int target_blocks, int min_zc = 8);
+PlanA plan_cg_A(const GridP &, int, int);
+// the launch of k_project_six: nxcd slabs of rows (one per XCD), nbx blocks of four waves per slab -- a multiple of the nseg row segments of
+// 128 cells (a wave keeps its segment), no more than the `items` row segments of a slab need
+struct ProjectSixPlan {
+  int     nxcd, nseg;
+  int64_t nbx, items;
+};
+ProjectSixPlan project_six_plan(const GridP &);
+// the 128 x 8 x t2zc tiles of k_mom2 / k_mom3 / k_mom_pw3 (fl_momentum.hip)
+struct MomPlan {
+  int t2x, t2chunk, t2zc, t2blocks;
+};
+MomPlan mom_plan(const GridP &);
 
 }  // namespace fl

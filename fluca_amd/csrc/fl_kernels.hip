@@ -7,24 +7,21 @@
 // 7-point stencil whose coefficients come from nine 1-D tables (fl_coeff.cpp).
 //
 // Hot kernels (Jacobi-PCG, KSPSolve(kspS) of fluca/src/ns/utils/abfpc/abfpc.c:77):
-//   k_cg_A  p' = z + beta p (z = r/diag - mean), q = S p', partial p'.q, and the deferred x += alpha_prev p:
-//           reads r,p,x  writes p',q,x  = 48 B/cell.  128 x (4*RY) tiles marching in z; p' planes staged in LDS
-//           (2 buffers, one barrier per plane), z-neighbours in registers, global loads prefetched one plane ahead.
-//   k_cg_B  r -= alpha q with the five partial sums the PETSc-style convergence test needs: 24 B/cell.
-// Together 72 B/cell/iteration against the 88 B/cell of the textbook sequence.
-//   k_cg_Bq the same update with q = S p' formed again from the stored direction (k_cg_A<SQ = false> writes no q): the
-//           pair moves 40 + 24 = 64 B/cell/iteration (+ tile rings).  The solver's default since round 2.
+//   k_cg_A  p' = z + beta p (z = r/diag - mean), q = S p', partial p'.q:  reads r,p  writes p'  = 24 B/cell.  128 x (NW*RY) tiles
+//           marching in z; p' planes staged in LDS (3 buffers, one barrier per plane), z-neighbours in registers, global loads
+//           prefetched one plane ahead.  q is not stored.
+//   k_cg_Bq r -= alpha q with q = S p' formed again from the stored direction, the partial sums the PETSc-style convergence test
+//           needs, and the x-updates of a group of iterations on the group's last one.
+// The pair moves 56 - 64 B/cell/iteration (+ tile rings) against the 88 B/cell of the textbook sequence.
 #include "fl_internal.h"
 #include "fl_stencil.h"
 #include "fl_knobs.h"
 
-#ifndef FL_CGA_WPE
-#define FL_CGA_WPE 2  // waves per SIMD the register allocator must leave room for: 2 = up to 256 VGPRs (one 512-thread block per CU), 4 = at most 128 (two blocks)
-#endif
-#ifndef FL_CGB_WPE
-#define FL_CGB_WPE 2
-#endif
 namespace fl {
+
+// waves per SIMD the register allocator must leave room for in k_cg_A / k_cg_Bq: 2 = up to 256 VGPRs (one 512-thread block per CU); 4 would cap
+// them at 128 (two blocks)
+constexpr int CG_WPE = 2;
 
 // ------------------------------------------------------------------------------------------------ helpers
 
@@ -176,9 +173,9 @@ __global__ void k_pack_faces(GridP g, const double *__restrict__ v, FaceBufs fb)
   const int64_t p = axis == 0 ? pidx(g, c, a, b) : (axis == 1 ? pidx(g, a, c, b) : pidx(g, a, b, c));
   buf[(int64_t)b * na + a] = v[p];
 }
-// The boundary layers of the NEW residual r - alpha q, packed before k_cg_B has formed it anywhere: the halo exchange then runs on
-// a second stream while k_cg_B streams the whole block (same fma as k_cg_B, so the neighbour's ghost equals this rank's cell bit
-// for bit).  After the iteration has stopped (reason != 0) k_cg_B leaves r alone: so does this.
+// The boundary layers of the NEW residual r - alpha q, packed before k_cg_Bq has formed it anywhere: the halo exchange then runs on
+// a second stream while k_cg_Bq streams the whole block (same fma as k_cg_Bq, so the neighbour's ghost equals this rank's cell bit
+// for bit).  After the iteration has stopped (reason != 0) k_cg_Bq leaves r alone: so does this.
 __global__ void k_pack_faces_rq(GridP g, const double *__restrict__ r, const double *__restrict__ q, const KspScal *__restrict__ s, FaceBufs fb)
 {
   const int bnd = blockIdx.z, axis = bnd / 2, side = bnd % 2;
@@ -275,37 +272,6 @@ __global__ void k_face_plane0(GridP g, const double *__restrict__ V, double *__r
 }
 
 // V_d -= kappa * Gst p on the owned faces of axis d (p padded with ghosts)
-#ifdef FL_KBENCH_VARIANTS  // round 1: one projection kernel per output array
-__global__ void k_project_faces(GridP g, const double *__restrict__ p, double *__restrict__ V, int axis)
-{
-  const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
-  const int lx = axis == 0 ? g.fx : g.nx, ly = axis == 1 ? g.fy : g.ny;
-  if (i >= lx || j >= ly) return;
-  const int     f  = axis == 0 ? i : (axis == 1 ? j : k);
-  const int     c0 = g.gc0[axis][f];
-  const int64_t st = axis == 0 ? 1 : (axis == 1 ? (int64_t)g.sx : g.sxy);
-  const int64_t pc = axis == 0 ? pidx(g, c0, j, k) : (axis == 1 ? pidx(g, i, c0, k) : pidx(g, i, j, c0));
-  const double  gr = g.ga0[axis][f] * p[pc] + g.ga1[axis][f] * p[pc + st];
-  const int64_t fi = axis == 0 ? ((int64_t)k * g.ny + j) * g.fx + i : (axis == 1 ? ((int64_t)k * g.fy + j) * g.nx + i : ((int64_t)k * g.ny + j) * g.nx + i);
-  V[fi] -= g.kappa * gr;
-}
-
-// v_d -= kappa * (G p)_d at cell centres.  p padded with TWO-deep access only at physical walls (inside the block), so
-// one ghost layer is enough: the 3-point one-sided rows start at the wall cell itself.
-__global__ void k_project_cells(GridP g, const double *__restrict__ p, double *__restrict__ v, int axis)
-{
-  const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
-  if (i >= g.nx || j >= g.ny) return;
-  const int     c  = axis == 0 ? i : (axis == 1 ? j : k);
-  const int     s0 = g.Gs[axis][c];
-  const int64_t st = axis == 0 ? 1 : (axis == 1 ? (int64_t)g.sx : g.sxy);
-  const int64_t pc = axis == 0 ? pidx(g, s0, j, k) : (axis == 1 ? pidx(g, i, s0, k) : pidx(g, i, j, s0));
-  double        gr = g.Gv0[axis][c] * p[pc] + g.Gv1[axis][c] * p[pc + st];
-  const double  v2 = g.Gv2[axis][c];
-  if (v2 != 0.) gr += v2 * p[pc + 2 * st];
-  v[((int64_t)k * g.ny + j) * g.nx + i] -= g.kappa * gr;
-}
-#endif  // FL_KBENCH_VARIANTS
 
 // The whole stage-2 update of PCApply_ABF (abfpc.c:79-101) in ONE pass over p:  v_d -= kappa (G p)_d on the cells and V_d -= kappa (Gst p)_d on the
 // owned faces of all three axes -- the rows and the arithmetic of k_project_cells / k_project_faces (same products, same order: bit-identical), but p is
@@ -678,12 +644,11 @@ __device__ __forceinline__ double *ring_at(const DirRing &R, int k)
   return p;
 }
 
-// mode 0: after k_cg_init.  mode 1: after k_cg_A (alpha).  mode 2: after k_cg_B / k_cg_Bq (beta, convergence).  One thread.
+// mode 0: after k_cg_init.  mode 3: after k_cg_A (alpha).  mode 2 / 4: after k_cg_Bq (beta, convergence).  One thread.
 // Who owes x what (pending_x = n: x still lacks the updates of the n newest directions, ring slots cur - n + 1 .. cur; k_cg_finish
-// adds them):
-//   stored-q pair: k_cg_A applies the update deferred from the iteration before (mode 1 clears it), k_cg_B leaves one (mode 2);
-//   q-free pair:   k_cg_A never touches x (mode 3 = mode 1 without clearing); k_cg_Bq applies none (mode 2: one more owed) except on
-//                  every xdepth-th iteration, where it applies all xdepth updates owed (mode 4 = mode 2 with nothing left pending).
+// adds them): k_cg_A never touches x (mode 3); k_cg_Bq applies none (mode 2: one more owed) except on every xdepth-th iteration, where it
+// applies all xdepth updates owed (mode 4 = mode 2 with nothing left pending).  Mode 1 (mode 3 that also clears pending_x: a k_cg_A that
+// applied a deferred update itself) has no caller left; the arm stays so that k_cg_fin's code is what it was.
 __device__ __forceinline__ void cg_fin_apply(int mode, const double *out, KspScal *__restrict__ s, double *__restrict__ hist, int nhist)
 {
   if (mode == 1 || mode == 3) {
@@ -854,88 +819,6 @@ __global__ void __launch_bounds__(256) k_cg_init(GridP g, const double *__restri
 // r -= alpha q ; partial sums of the new r.  24 B/cell.  Same 128 x (4*RY) x zc tiling as k_cg_A (no integer division in
 // the loop); loads are unconditional on clamped, always-valid addresses so that the compiler can count them (a load
 // inside a divergent branch costs an s_waitcnt vmcnt(0)); only the stores and the sums are masked.
-#ifdef FL_KBENCH_VARIANTS  // variant 2 of the CG pair: the r-update that reads a stored q
-template <int RY, bool JAC, int NT>
-__global__ void __launch_bounds__(256) k_cg_B(GridP g, const double *__restrict__ q, double *__restrict__ r, KspScal *__restrict__ s, double *__restrict__ partial, int stride, int nchunk, int zc, int tiles_x, FinCtx fin)
-{
-  __shared__ double red[5 * 4];
-  __shared__ int    flag;
-  if (s->reason != 0) return;
-  const double alpha = s->alpha;
-  const int    b = blockIdx.x, chunk = b % nchunk, tile = b / nchunk;
-  const int    i0 = (tile % tiles_x) * 128, j0 = (tile / tiles_x) * (4 * RY);
-  const int    k0 = chunk * zc, k1 = min(k0 + zc, g.nz);
-  const int    lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int    i = i0 + 2 * lane, il = min(i, g.nx & ~1);
-  const bool   own0 = i < g.nx, own1 = i + 1 < g.nx;
-  const double xc0 = g.sc[0][min(i, g.nx)], xc1 = g.sc[0][min(i + 1, g.nx)];
-  int64_t      ro[RY];
-  bool         rown[RY];
-  double       yc[RY];
-#pragma unroll
-  for (int m = 0; m < RY; ++m) {
-    const int j = j0 + w * RY + m;
-    rown[m]     = j < g.ny;
-    ro[m]       = g.off0 + (int64_t)min(j, g.ny) * g.sx;  // wave-uniform; the lane adds il
-    yc[m]       = g.sc[1][min(j, g.ny)];
-  }
-  double acc[5] = {0., 0., 0., 0., 0.};
-  struct Raw {
-    double2 q[RY], r[RY];
-    double  zc;
-  };
-  // loads of plane k (clamped into the chunk: the trip past the end re-reads a cached plane instead of branching)
-  auto load = [&](int k, Raw &R) {
-    const int     kc = min(k, k1 - 1);
-    const int64_t pl = (int64_t)kc * g.sxy;
-#pragma unroll
-    for (int m = 0; m < RY; ++m) {
-      R.q[m] = ld2<NT>(q + ro[m] + pl + il);
-      R.r[m] = ld2<NT>(r + ro[m] + pl + il);
-    }
-    R.zc = g.sc[2][kc];
-  };
-  // one plane: prefetch k+1 into N, work on C.  Called with (A,B) then (B,A): the two register sets ping-pong, so no
-  // register copy ever has to wait for a load in flight.
-  auto step = [&](int k, const Raw &C, Raw &N) {
-    load(k + 1, N);
-    const int64_t pc = (int64_t)k * g.sxy;
-#pragma unroll
-    for (int m = 0; m < RY; ++m) {
-      double2 rn;
-      rn.x = fma(-alpha, C.q[m].x, C.r[m].x);  // the same rounding as k_pack_faces_rq
-      rn.y = fma(-alpha, C.q[m].y, C.r[m].y);
-      const double dyz = yc[m] + C.zc;
-      const double z0 = JAC ? rn.x / (xc0 + dyz) : rn.x;
-      const double z1 = JAC ? rn.y / (xc1 + dyz) : rn.y;
-      if (rown[m]) {
-        if (own1) st2<NT>(r + ro[m] + pc + il, rn);
-        else if (own0) r[ro[m] + pc + il] = rn.x;
-      }
-      const double m0 = (rown[m] && own0) ? 1. : 0., m1 = (rown[m] && own1) ? 1. : 0.;
-      const double r0 = m0 * rn.x, r1 = m1 * rn.y, zz0 = m0 * z0, zz1 = m1 * z1;
-      acc[0] += r0 * zz0 + r1 * zz1;
-      acc[1] += zz0 * zz0 + zz1 * zz1;
-      acc[2] += zz0 + zz1;
-      acc[3] += r0 + r1;
-      acc[4] += r0 * r0 + r1 * r1;
-    }
-  };
-  if (k0 < k1) {
-    Raw A, B;
-    load(k0, A);
-    for (int k = k0; k < k1; k += 2) {
-      step(k, A, B);
-      if (k + 1 < k1) step(k + 1, B, A);
-    }
-  }
-  block_sum<5>(acc, red);
-  if (fin.enabled) fused_fin<5, 256>(2, acc, partial, stride, fin, s, red, &flag);
-  else if (threadIdx.x == 0)
-#pragma unroll
-    for (int a = 0; a < 5; ++a) partial[(int64_t)a * stride + blockIdx.x] = acc[a];
-}
-#endif  // FL_KBENCH_VARIANTS
 
 // the x-updates still owed when the iteration stops, fused with the copy into the caller's (unpadded) array:
 //   xout = x + a_(cur-n+1) p_(cur-n+1) + ... + a_cur p_cur   (n = pending_x ring slots, oldest first, one fma each: the order k_cg_Bq
@@ -987,17 +870,16 @@ __global__ void __launch_bounds__(256) k_cg_finish(GridP g, DirRing P, const dou
 
 // ------------------------------------------------------------------------------------------------ CG: the fused stencil kernel
 
-// RY rows per wave, NW waves per block (tile 128 x NW*RY), PF prefetch mode, NT: 0 plain, 1 non-temporal stores,
-// 2 non-temporal stores and tile loads (halo loads stay plain: they are meant to hit in L2)
-// SQ: store q (k_cg_B reads it back) and apply the x-update deferred from the iteration before; !SQ: neither -- q is formed again and
-// x is updated by k_cg_Bq, so this kernel reads r, p and writes p' (24 B/cell).
-template <int RY, int NW, bool JAC, int PF, int NT, bool SQ>
+// RY rows per wave, NW waves per block (tile 128 x NW*RY).  Tile loads and stores are non-temporal (halo loads stay plain: they are meant to
+// hit in L2).  q is not stored and x not touched -- q is formed again and x updated by k_cg_Bq -- so this kernel reads r, p and writes p'
+// (24 B/cell); q goes to memory on the block's boundary layers only, where the plan asks for it (PlanA::qb).
+template <int RY, int NW, bool JAC>
 __device__ __forceinline__ void cg_A_body(const GridP &g, const double *__restrict__ r, const double *__restrict__ pold, double *__restrict__ pnew, double *__restrict__ q, double *__restrict__ x, KspScal *__restrict__ s,
                                                       double *__restrict__ partial, int nchunk, int zc, int tiles_x, int tiles, int remap, FinCtx fin)
 {
   using T               = TileA<RY, NW>;
   constexpr int TX = T::TX, TY = T::TY, LX = T::LX, LY = T::LY;
-  constexpr int NTL = NT >= 2, NTS = NT >= 1;
+  constexpr int NTL = 1, NTS = 1;  // the non-temporal hint on tile loads / stores
   // three staged p' planes: kk (being written), kk-1 (stencil centre + in-plane neighbours), kk-2 (z-low neighbour).
   // Keeping the two older planes in LDS instead of registers frees 32 VGPRs for the load prefetch.
   __shared__ __attribute__((aligned(16))) double lds[3][LY][LX];
@@ -1007,9 +889,8 @@ __device__ __forceinline__ void cg_A_body(const GridP &g, const double *__restri
 
   const double  beta       = s->beta;
   const double  zs         = s->zshift;
-  const double  alpha_prev = s->alpha;  // 0 on the first iteration (and p_old = 0): the deferred x-update is a no-op then
 
-  const bool qbnd = !SQ && (remap & 2) != 0;  // store q on the block's boundary layers only (PlanA::qb)
+  const bool qbnd = (remap & 2) != 0;  // store q on the block's boundary layers only (PlanA::qb)
   const int  b    = (remap & 1) ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
   const int chunk = b / tiles, tile = b % tiles;  // chunk-major: consecutive logical blocks are neighbouring tiles
   const int i0 = (tile % tiles_x) * TX, j0 = (tile / tiles_x) * TY;
@@ -1068,7 +949,7 @@ __device__ __forceinline__ void cg_A_body(const GridP &g, const double *__restri
 
   // raw inputs of one plane, fetched one trip ahead
   struct Raw {
-    double2 r[RY], p[RY], x[RY];
+    double2 r[RY], p[RY];
     double  hrA, hpA, hrB, hpB;
     double  zl, zc, zh;  // z-row of that plane: prefetched with it so that no load sits between prefetch and use
   };
@@ -1081,12 +962,6 @@ __device__ __forceinline__ void cg_A_body(const GridP &g, const double *__restri
       R.r[m] = ld2<NTL>(r + RO(m) + pl);
       R.p[m] = ld2<NTL>(pold + RO(m) + pl);
     }
-    if (SQ) {
-      // x only exists on owned planes: the two extra trips re-read a cached plane instead of branching
-      const int64_t px = (int64_t)min(max(kn_, k0), k1 - 1) * g.sxy;
-#pragma unroll
-      for (int m = 0; m < RY; ++m) R.x[m] = ld2<NTL>(x + RO(m) + px);
-    }
     R.hrA = r[tbase + pl + hAo];
     R.hpA = pold[tbase + pl + hAo];
     R.hrB = r[tbase + pl + hBo];
@@ -1098,25 +973,8 @@ __device__ __forceinline__ void cg_A_body(const GridP &g, const double *__restri
 
   // one plane: prefetch kk+1 into N, work on C.  Called alternately with (A,B) and (B,A): the two register sets
   // ping-pong, so no register copy ever has to wait for a load in flight.
-  // PF == 1: called alternately with (A,B) / (B,A), prefetch at the top.  PF == 0: C and N are the same set; the
-  // next plane is fetched as soon as p' and the x-update have consumed the current one (fewer VGPRs, shorter flight).
-  // deferred x-update of plane kk:  x += alpha_prev * p_old
-  auto xupdate = [&](int kk, int64_t pl, bool pown, const Raw &C, const double2 *xv) {
-    if (!SQ || !pown) return;
-#pragma unroll
-    for (int m = 0; m < RY; ++m) {
-      double2 xn;
-      xn.x = xv[m].x + alpha_prev * C.p[m].x;
-      xn.y = xv[m].y + alpha_prev * C.p[m].y;
-      if (rown[m]) {
-        if (own1) st2<NTS>(x + RO(m) + pl, xn);
-        else if (own0) x[RO(m) + pl] = xn.x;
-      }
-    }
-  };
-
   auto step = [&](int kk, Raw &C, Raw &N) {
-    if (PF == 1) load(kk + 1, N);
+    load(kk + 1, N);
     const double nzl = C.zl, nzc = C.zc, nzh = C.zh;
 
     const bool    pown = kk >= k0 && kk < k1;    // plane owned by this chunk: its p', x are stored here
@@ -1148,10 +1006,6 @@ __device__ __forceinline__ void cg_A_body(const GridP &g, const double *__restri
       if (hAgh) pnew[tbase + pl + hAo] = hnA;
       if (hBgh) pnew[tbase + pl + hBo] = hnB;
     }
-    if (PF == 0) {
-      xupdate(kk, pl, pown, C, C.x);
-      load(kk + 1, N);  // N aliases C: every value of the old plane has been consumed
-    }
 
     // q of plane kc = kk-1: centre, in-plane neighbours from lds[kc%3] (staged one trip ago), z-low from lds[(kc-1)%3] ------
     const int kc = kk - 1;
@@ -1172,13 +1026,8 @@ __device__ __forceinline__ void cg_A_body(const GridP &g, const double *__restri
         qq.x = st7(xc0 + dyc, cen.x, xl0, west, xh0, cen.y, yl[m], south.x, yh[m], north.x, zlc, below.x, zhc, pnext[m].x);
         qq.y = st7(xc1 + dyc, cen.y, xl1, cen.x, xh1, east, yl[m], south.y, yh[m], north.y, zlc, below.y, zhc, pnext[m].y);
         if (rown[m]) {
-          if (own1) {
-            if (SQ) st2<NTS>(q + RO(m) + pc, qq);
-            dot += cen.x * qq.x + cen.y * qq.y;
-          } else if (own0) {
-            if (SQ) q[RO(m) + pc] = qq.x;
-            dot += cen.x * qq.x;
-          }
+          if (own1) dot += cen.x * qq.x + cen.y * qq.y;
+          else if (own0) dot += cen.x * qq.x;
           if (qbnd) {
             // the first / last plane and row of the block entirely, of the other rows the first and the last cell
             const int j = jb + m;
@@ -1194,8 +1043,6 @@ __device__ __forceinline__ void cg_A_body(const GridP &g, const double *__restri
       }
     }
 
-    if (PF == 1) xupdate(kk, pl, pown, C, C.x);
-
     // stage plane kk for the next trip ------------------------------------------------------------------------------------
 #pragma unroll
     for (int m = 0; m < RY; ++m) *reinterpret_cast<double2 *>(&lds[buf][w * RY + m + 1][2 * lane + 2]) = pnext[m];
@@ -1207,17 +1054,11 @@ __device__ __forceinline__ void cg_A_body(const GridP &g, const double *__restri
     zhc = nzh;
   };
 
-  if (PF == 1) {
-    Raw A, B;
-    load(k0 - 1, A);
-    for (int kk = k0 - 1; kk <= k1; kk += 2) {
-      step(kk, A, B);
-      if (kk + 1 <= k1) step(kk + 1, B, A);
-    }
-  } else {
-    Raw A;
-    load(k0 - 1, A);
-    for (int kk = k0 - 1; kk <= k1; ++kk) step(kk, A, A);
+  Raw A, B;
+  load(k0 - 1, A);
+  for (int kk = k0 - 1; kk <= k1; kk += 2) {
+    step(kk, A, B);
+    if (kk + 1 <= k1) step(kk + 1, B, A);
   }
 
 #undef RO
@@ -1229,49 +1070,49 @@ __device__ __forceinline__ void cg_A_body(const GridP &g, const double *__restri
 #pragma unroll
     for (int a = 0; a < NW; ++a) tot[0] += red[a];
   }
-  if (fin.enabled) fused_fin<1, 64 * NW>(SQ ? 1 : 3, tot, partial, 0, fin, s, red, &flag);
+  if (fin.enabled) fused_fin<1, 64 * NW>(3, tot, partial, 0, fin, s, red, &flag);
   else if (tid == 0) partial[blockIdx.x] = tot[0];
 }
 
 // The kernels pick the two ring slots and hand them to the body as __restrict__ parameters: p' stores that might alias the p loads
 // would pin every prefetch behind them (k_cg_A 0.59 -> 0.62 ms at 512^3 when the body took them from the ring itself).
 #define FL_CG_A_ARGS GridP g, const double *__restrict__ r, DirRing P, double *__restrict__ q, double *__restrict__ x, KspScal *__restrict__ s, double *__restrict__ partial, int nchunk, int zc, int tiles_x, int tiles, int remap, FinCtx fin
-template <int RY, int NW, bool JAC, int PF, int NT, bool SQ>
-__global__ void __launch_bounds__(64 * NW, FL_CGA_WPE) k_cg_A(FL_CG_A_ARGS)
+template <int RY, int NW, bool JAC>
+__global__ void __launch_bounds__(64 * NW, CG_WPE) k_cg_A(FL_CG_A_ARGS)
 {
   const int cur = s->cur;  // p_old = ring slot cur; p' goes to the next slot, the oldest direction (x holds its update)
-  cg_A_body<RY, NW, JAC, PF, NT, SQ>(g, r, ring_at(P, cur), ring_at(P, cur + 1 == ring_depth(s) ? 0 : cur + 1), q, x, s, partial, nchunk, zc, tiles_x, tiles, remap, fin);
+  cg_A_body<RY, NW, JAC>(g, r, ring_at(P, cur), ring_at(P, cur + 1 == ring_depth(s) ? 0 : cur + 1), q, x, s, partial, nchunk, zc, tiles_x, tiles, remap, fin);
 }
 // The same code under another name: launched only by fl_poisson_tune_placement, so that profiles keep the probe
 // launches (half of them on deliberately rejected placements) apart from the solver's own launches.
-template <int RY, int NW, bool JAC, int PF, int NT, bool SQ>
+template <int RY, int NW, bool JAC>
 __global__ void __launch_bounds__(64 * NW, 2) k_cg_A_probe(FL_CG_A_ARGS)
 {
   const int cur = s->cur;  // p_old = ring slot cur; p' goes to the next slot, the oldest direction (x holds its update)
-  cg_A_body<RY, NW, JAC, PF, NT, SQ>(g, r, ring_at(P, cur), ring_at(P, cur + 1 == ring_depth(s) ? 0 : cur + 1), q, x, s, partial, nchunk, zc, tiles_x, tiles, remap, fin);
+  cg_A_body<RY, NW, JAC>(g, r, ring_at(P, cur), ring_at(P, cur + 1 == ring_depth(s) ? 0 : cur + 1), q, x, s, partial, nchunk, zc, tiles_x, tiles, remap, fin);
 }
 #undef FL_CG_A_ARGS
 
-// r -= alpha q with q = S p' FORMED AGAIN from the direction k_cg_A has just written, instead of being read back: k_cg_A<SQ = false>
-// then never writes q.  Per cell this kernel reads p' (plus the tile's one-cell ring) and r and writes r -- 24 B + ring -- where the
-// q store of k_cg_A and the q load of k_cg_B moved 16 B: an iteration moves 64 B/cell instead of 72.  Same tile walk as k_cg_A
+// r -= alpha q with q = S p' FORMED AGAIN from the direction k_cg_A has just written, instead of being read back: k_cg_A never writes
+// q.  Per cell this kernel reads p' (plus the tile's one-cell ring) and r and writes r -- 24 B + ring -- where a q store in k_cg_A and
+// a q load here would move 16 B: an iteration moves 64 B/cell instead of 72.  Same tile walk as k_cg_A
 // (128 x NW*RY tile marching through a z chunk, three p' planes in LDS, raw planes fetched one trip ahead into a second register
 // set, unconditional loads on clamped addresses, masked stores); q comes out of st7 exactly as in k_cg_A.  The ghost layer of p'
-// is complete: k_cg_A stores p' on every star-ghost cell it forms (rows / columns / planes -1 and n).  Sums as in k_cg_B.
+// is complete: k_cg_A stores p' on every star-ghost cell it forms (rows / columns / planes -1 and n).  Five partial sums: what the PETSc-style convergence test needs.
 // The x-update lives here too (XU updates): the direction is in registers anyway.  With a ring of K direction buffers (DirRing,
 // KspScal::xdepth) x is read and written on every K-th iteration only: XU == K there -- x += a_(i-K+1) p_(i-K+1) + ... + a_(i-1) p_(i-1)
 // + alpha p', the K - 1 older directions from their ring slots, which k_cg_A overwrites only from the NEXT iteration on -- and XU == 0
 // on the others: 8 (K - 1) + 16 B/cell per K iterations instead of 16 per iteration.  XZ: the first such launch of a solve, x = 0 is not
 // read (the padded x is not zeroed by k_cg_init then).  XU == 1: x += alpha p' every iteration (cg_xbatch = 0, A/B runs).
 // The fma of XU > 1 are the separate updates in iteration order: same x bit for bit.
-template <int RY, int NW, bool JAC, int NT, int XU, bool XZ>
+template <int RY, int NW, bool JAC, int XU, bool XZ>
 __device__ __forceinline__ void cg_Bq_body(const GridP &g, const DirRing &P, double *__restrict__ r, double *__restrict__ x, KspScal *__restrict__ s,
                                            double *__restrict__ partial, int stride, int nchunk, int zc, int tiles_x, int tiles, int remap, FinCtx fin)
 {
   constexpr int NO = XU > 1 ? XU - 1 : 1;  // older directions read by an x-flush (array extent)
   using T               = TileA<RY, NW>;
   constexpr int TX = T::TX, TY = T::TY, LX = T::LX, LY = T::LY;
-  constexpr int NTL = NT >= 2, NTS = NT >= 1;
+  constexpr int NTL = 1, NTS = 1;  // the non-temporal hint on tile loads / stores
   __shared__ __attribute__((aligned(16))) double lds[3][LY][LX];
   __shared__ double                              red[5 * NW];
   __shared__ int                                 flag;
@@ -1445,63 +1286,22 @@ __device__ __forceinline__ void cg_Bq_body(const GridP &g, const DirRing &P, dou
     for (int a = 0; a < 5; ++a) partial[(int64_t)a * stride + blockIdx.x] = tot[a];
 }
 #define FL_CG_BQ_ARGS GridP g, DirRing P, double *__restrict__ r, double *__restrict__ x, KspScal *__restrict__ s, double *__restrict__ partial, int stride, int nchunk, int zc, int tiles_x, int tiles, int remap, FinCtx fin
-template <int RY, int NW, bool JAC, int NT, int XU, bool XZ>
-__global__ void __launch_bounds__(64 * NW, FL_CGB_WPE) k_cg_Bq(FL_CG_BQ_ARGS)
+template <int RY, int NW, bool JAC, int XU, bool XZ>
+__global__ void __launch_bounds__(64 * NW, CG_WPE) k_cg_Bq(FL_CG_BQ_ARGS)
 {
-  cg_Bq_body<RY, NW, JAC, NT, XU, XZ>(g, P, r, x, s, partial, stride, nchunk, zc, tiles_x, tiles, remap, fin);
+  cg_Bq_body<RY, NW, JAC, XU, XZ>(g, P, r, x, s, partial, stride, nchunk, zc, tiles_x, tiles, remap, fin);
 }
 // the placement probe's launches under their own name (see k_cg_A_probe)
-template <int RY, int NW, bool JAC, int NT, int XU, bool XZ>
+template <int RY, int NW, bool JAC, int XU, bool XZ>
 __global__ void __launch_bounds__(64 * NW, 2) k_cg_Bq_probe(FL_CG_BQ_ARGS)
 {
-  cg_Bq_body<RY, NW, JAC, NT, XU, XZ>(g, P, r, x, s, partial, stride, nchunk, zc, tiles_x, tiles, remap, fin);
+  cg_Bq_body<RY, NW, JAC, XU, XZ>(g, P, r, x, s, partial, stride, nchunk, zc, tiles_x, tiles, remap, fin);
 }
 #undef FL_CG_BQ_ARGS
 
 // ------------------------------------------------------------------------------------------------ unfused CG pieces (variant 1)
 
 // p = (r/diag - mean) + beta p on the owned cells
-#ifdef FL_KBENCH_VARIANTS  // variant 1 of the CG solver: one kernel per BLAS-1 / SpMV step
-template <bool JAC>
-__global__ void k_cg_pupdate(GridP g, const double *__restrict__ r, double *__restrict__ P0, double *__restrict__ P1, const KspScal *__restrict__ s)
-{
-  if (s->reason != 0) return;
-  const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
-  if (i >= g.nx || j >= g.ny) return;
-  const double *pold = s->cur ? P1 : P0;
-  double       *pnew = s->cur ? P0 : P1;
-  const int64_t o    = pidx(g, i, j, k);
-  const double  z    = JAC ? r[o] / (g.sc[0][i] + g.sc[1][j] + g.sc[2][k]) : r[o];
-  pnew[o]            = (z - s->zshift) + s->beta * pold[o];
-}
-
-// q = S p' (p' = the buffer k_cg_pupdate wrote), partial p'.q, deferred x update as in k_cg_A
-__global__ void __launch_bounds__(256) k_cg_apply_dot(GridP g, const double *__restrict__ P0, const double *__restrict__ P1, double *__restrict__ q, double *__restrict__ x, const KspScal *__restrict__ s, double *__restrict__ partial)
-{
-  __shared__ double red[4];
-  if (s->reason != 0) return;
-  const int     i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
-  const double *pold = s->cur ? P1 : P0;
-  const double *pnew = s->cur ? P0 : P1;
-  double        acc[1] = {0.};
-  if (i < g.nx && j < g.ny) {
-    const int64_t o = pidx(g, i, j, k);
-    const double  v = stencil7(g, pnew, i, j, k);
-    q[o]            = v;
-    acc[0]          = pnew[o] * v;
-    if (s->pending_x) x[o] += s->alpha * pold[o];
-  }
-  // blockDim = (64,4): linear thread id matches block_sum's expectations
-  double v1[1] = {acc[0]};
-  {
-    const int lin = threadIdx.y * 64 + threadIdx.x;
-    double    t   = wave_sum(v1[0]);
-    if ((lin & 63) == 0) red[lin >> 6] = t;
-    __syncthreads();
-    if (lin == 0) partial[((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-  }
-}
-#endif  // FL_KBENCH_VARIANTS
 
 // ------------------------------------------------------------------------------------------------ bandwidth reference
 // NR input streams, NW output streams, 16 B per lane per access, grid-stride: the realistic HBM ceiling for a kernel with
@@ -1656,13 +1456,6 @@ void launch_face_plane0(hipStream_t st, const GridP &g, const double *V, double 
   const int na = axis == 0 ? g.ny : g.nx, nb = axis == 2 ? g.ny : g.nz;
   hipLaunchKernelGGL(k_face_plane0, grid3(na, nb, 1), blk3(), 0, st, g, V, buf, axis);
 }
-void launch_project_faces(hipStream_t st, const GridP &g, const double *p, double *V, int axis)
-{
-#ifdef FL_KBENCH_VARIANTS
-  const int lx = axis == 0 ? g.fx : g.nx, ly = axis == 1 ? g.fy : g.ny, lz = axis == 2 ? g.fz : g.nz;
-  if (lz > 0) hipLaunchKernelGGL(k_project_faces, grid3(lx, ly, lz), blk3(), 0, st, g, p, V, axis);
-#endif
-}
 void launch_project_all(hipStream_t st, const GridP &g, const double *p, double *const v[3], double *const V[3])
 {
   ProjOut o;
@@ -1687,6 +1480,19 @@ bool project_six_usable(const GridP &g, const double *p_unpadded, double *const 
     if (!v[d] || !V[d] || (reinterpret_cast<uintptr_t>(v[d]) & 15) || (d > 0 && (reinterpret_cast<uintptr_t>(V[d]) & 15))) return false;
   return !p_unpadded || (reinterpret_cast<uintptr_t>(p_unpadded) & 15) == 0;
 }
+// 1024 blocks of four waves per XCD slab of rows (8 slabs; one slab where there are fewer than 8 rows).  512^3 (profiles/r04_project.txt):
+// 1024 - 2048 blocks per XCD 2.69 ms, 256: 2.97, 16384 (a row per wave): 2.87; without the slabs 2.76 - 2.86; without the non-temporal hint
+// 2.78; two rows per pass (244 VGPRs) 2.86; capped at 128 VGPRs 2.85
+ProjectSixPlan project_six_plan(const GridP &g)
+{
+  ProjectSixPlan p;
+  p.nseg  = (g.nx + 127) / 128;
+  p.nxcd  = g.ny < 8 ? 1 : 8;
+  p.items = (int64_t)p.nseg * ((g.ny + p.nxcd - 1) / p.nxcd) * g.nz;
+  p.nbx   = std::max<int64_t>(1, std::min<int64_t>((p.items + 3) / 4, (int64_t)1024 * (8 / p.nxcd)));
+  p.nbx   = (p.nbx + p.nseg - 1) / p.nseg * p.nseg;
+  return p;
+}
 // direct: p is the caller's unpadded array, per = bit d set where axis d is periodic (single rank); else p is padded with its ghost layers filled
 void launch_project_six(hipStream_t st, const GridP &g, const double *p, bool direct, int per, double *const v[3], double *const V[3])
 {
@@ -1695,32 +1501,10 @@ void launch_project_six(hipStream_t st, const GridP &g, const double *p, bool di
     o.v[d] = v[d];
     o.V[d] = V[d];
   }
-  // experiments (tools/experiments/r04_project.sh): FLUCA_PROJECT_VAR="nt,nxcd,blocks_per_xcd".  512^3 (profiles/r04_project.txt): 1024 - 2048 blocks
-  // per XCD 2.69 ms, 256: 2.97, 16384 (a row per wave): 2.87; without the slabs (nxcd 1) 2.76 - 2.86; without the hint 2.78; two rows per pass
-  // (244 VGPRs) 2.86; capped at 128 VGPRs 2.85
-  struct Var { int nt = 1, nxcd = 8, nbx = 1024; };
-  Var var;
-  if (const char *e = variant_env("FLUCA_PROJECT_VAR")) std::sscanf(e, "%d,%d,%d", &var.nt, &var.nxcd, &var.nbx);
-  const int nseg = (g.nx + 127) / 128;
-  const int nxcd = (var.nxcd == 1 || g.ny < 8) ? 1 : 8;
-  // blocks of four waves per XCD: a multiple of nseg (a wave keeps its segment), no more than the rows of a slab need
-  const int64_t items = (int64_t)nseg * ((g.ny + nxcd - 1) / nxcd) * g.nz;
-  int64_t       nbx = std::max<int64_t>(1, std::min<int64_t>((items + 3) / 4, (int64_t)std::max(var.nbx, 1) * (8 / nxcd)));
-  nbx = (nbx + nseg - 1) / nseg * nseg;
-  const dim3 gr((unsigned)(nbx * nxcd)), bl(256);
-  if (direct) {
-    if (var.nt) hipLaunchKernelGGL((k_project_six<true, 1, 1>), gr, bl, 0, st, g, p, o, per, nxcd);
-    else hipLaunchKernelGGL((k_project_six<true, 0, 1>), gr, bl, 0, st, g, p, o, per, nxcd);
-  } else {
-    if (var.nt) hipLaunchKernelGGL((k_project_six<false, 1, 1>), gr, bl, 0, st, g, p, o, per, nxcd);
-    else hipLaunchKernelGGL((k_project_six<false, 0, 1>), gr, bl, 0, st, g, p, o, per, nxcd);
-  }
-}
-void launch_project_cells(hipStream_t st, const GridP &g, const double *p, double *v, int axis)
-{
-#ifdef FL_KBENCH_VARIANTS
-  hipLaunchKernelGGL(k_project_cells, grid3(g.nx, g.ny, g.nz), blk3(), 0, st, g, p, v, axis);
-#endif
+  const ProjectSixPlan pl = project_six_plan(g);
+  const dim3           gr((unsigned)(pl.nbx * pl.nxcd)), bl(256);
+  if (direct) hipLaunchKernelGGL((k_project_six<true, 1, 1>), gr, bl, 0, st, g, p, o, per, pl.nxcd);
+  else hipLaunchKernelGGL((k_project_six<false, 1, 1>), gr, bl, 0, st, g, p, o, per, pl.nxcd);
 }
 void launch_gst_bc(hipStream_t st, const GridP &g, const double *pb, double *V, int axis, int side, double coeff, int add)
 {
@@ -1763,55 +1547,40 @@ void launch_cg_finish(hipStream_t st, const GridP &g, const DirRing &P, const do
   hipLaunchKernelGGL(k_cg_finish, dim3(nblocks), dim3(256), 0, st, g, P, x, xout, s, unpadded_pairs(g, xout));
 }
 
-// tiling of k_cg_A: returns the number of blocks
-struct PlanA {
-  int ry, nw, tiles_x, tiles_y, nchunk, zc, nblocks, pf, nt, remap, probe;
-  int sq;  // 1: k_cg_A stores q (k_cg_B reads it back); 0: q is formed again by k_cg_Bq (the default of the solver)
-  int qb;  // sq == 0 only: k_cg_A still stores q on the six boundary layers of the block (the overlapped halo exchange packs r - alpha q there)
-};
-// tiling of k_cg_A / k_cg_B (K_B always runs 4-wave blocks: it reuses ry, nchunk, zc with nw = 4)
-PlanA plan_tiles(const GridP &g, int ry, int nw, int nchunk_force, int target_blocks, int min_zc = 8)
+// 128 x (nw * ry) tiles; nchunk_force > 0 takes that many z chunks (fewer if some would be empty), else the chunking rule (z_chunk_count)
+PlanA plan_tiles(const GridP &g, int ry, int nw, int nchunk_force, int target_blocks, int min_zc)
 {
   PlanA p;
   p.ry = ry;
   p.nw = nw;
-  p.pf = 0;
-  p.nt = 0;
   p.remap   = 1;
   p.probe   = 0;
-  p.sq      = 0;
   p.qb      = 0;
   p.tiles_x = (g.nx + 127) / 128;
   p.tiles_y = (g.ny + nw * ry - 1) / (nw * ry);
-  const int tiles = p.tiles_x * p.tiles_y;
-  int       nchunk = nchunk_force > 0 ? nchunk_force : std::max(1, (target_blocks + tiles / 2) / tiles);
-  if (nchunk_force <= 0) nchunk = std::min(nchunk, std::max(1, g.nz / min_zc));  // min_zc = 8 keeps the 2-plane chunk prologue <= 25 %
-  nchunk    = std::max(1, std::min(nchunk, g.nz));
-  p.zc      = (g.nz + nchunk - 1) / nchunk;
-  p.nchunk  = (g.nz + p.zc - 1) / p.zc;
+  const int     tiles = p.tiles_x * p.tiles_y;
+  const ZChunks z     = z_chunks(g.nz, nchunk_force > 0 ? std::min(nchunk_force, g.nz) : z_chunk_count(tiles, g.nz, target_blocks, min_zc));
+  p.zc      = z.zc;
+  p.nchunk  = z.nchunk;
   p.nblocks = tiles * p.nchunk;
   return p;
 }
-// Defaults from the tools/kbench.py sweeps on MI355X at 512^3 (profiles/r01_kbench*.txt, three different boxes): 128 x 16
+// Defaults from the kernel sweeps on MI355X at 512^3 (profiles/r01_kbench*.txt, three different machines): 128 x 16
 // tiles of 8 waves x 2 rows, two ping-pong prefetch sets, non-temporal tile loads and stores, XCD-contiguous
 // chunk-major block order.  Grids too small to give every CU a block with that shape (the reference's own 64 x 64 x 32
 // cavity makes 16) are latency-bound, not bandwidth-bound: they get smaller tiles and short z chunks instead, the chunk
-// prologue no longer matters (tools/experiments/small_grid_plan.py: k_cg_A 23.4 -> 6.9 us, k_cg_B 9.6 -> 4.7 us there).
+// prologue no longer matters (k_cg_A 23.4 -> 6.9 us there).
 constexpr int MIN_BLOCKS = 256;  // one per CU
-// Plans from the sweeps of tools/experiments/sweep256.py at 128^3, 256^3 and 512^3 (profiles/r02_plan_sweep.txt): both kernels are
-// fastest with about one block per CU (k_cg_A) or one to two (k_cg_B) and as few z chunks as that allows -- every chunk pays a
-// two-plane prologue in k_cg_A and a ramp in both.  512^3: k_cg_A 128 x 16 tiles x 2 chunks (1094 us; 4 chunks 1106, 128 x 8 tiles
-// 1123), k_cg_B 128 x 16 x 2 chunks (543 us; the 1024 blocks of round 1: 585).  256^3: k_cg_A 128 x 8 x 4 chunks (151 us; the
-// round-1 plan of 128 x 16 x 16 chunks: 164), k_cg_B 128 x 4 x 4 chunks (70 us; round 1: 128 x 16 x 32 chunks, 108).
+// Plans from the sweeps at 128^3, 256^3 and 512^3 (profiles/r02_plan_sweep.txt): the kernel is fastest with about one block per CU and as
+// few z chunks as that allows -- every chunk pays a two-plane prologue and a ramp.  512^3: 128 x 16 tiles x 2 chunks (1094 us; 4 chunks
+// 1106, 128 x 8 tiles 1123).  256^3: 128 x 8 x 4 chunks (151 us; the round-1 plan of 128 x 16 x 16 chunks: 164).
 PlanA plan_cg_A(const GridP &g, int ry_force, int nchunk_force)
 {
-  const int target_env = FL_VARIANT(cga_target, 0);
-  const int target = target_env > 0 ? target_env : 256;
   const int ry = ry_force > 0 ? ry_force : (g.ny >= 8 ? 2 : 1);
   // 128 x 16 tiles (8 waves) when they alone nearly fill the chip, 128 x 8 (4 waves) below that
   const int tiles16 = ((g.nx + 127) / 128) * ((g.ny + 8 * ry - 1) / (8 * ry));
   const int nw      = (ry == 2 && g.ny >= 32 && tiles16 >= 128) ? 8 : 4;
-  PlanA     p       = plan_tiles(g, ry, nw, nchunk_force, target);
+  PlanA     p       = plan_tiles(g, ry, nw, nchunk_force, 256);
   if (ry_force <= 0 && nchunk_force <= 0 && p.nblocks < MIN_BLOCKS) {
     p = plan_tiles(g, ry, 4, 0, 512, 2);
     if (p.nblocks < MIN_BLOCKS && ry == 2) p = plan_tiles(g, 1, 4, 0, 512, 2);
@@ -1819,78 +1588,26 @@ PlanA plan_cg_A(const GridP &g, int ry_force, int nchunk_force)
   // 256^3 .. 512^3 (round 4, profiles/r04_cg256.txt, r04_cg_plans.txt): an 8-wave block holds 147 - 186 VGPRs, so a CU runs ONE of them; the pair is
   // fastest when every CU has exactly one -- as many z chunks of 128 x 16 tiles as fit into 256 blocks, never a second round (384^3: 216 blocks
   // 0.633 ms per iteration against 0.844 with the 288 four-wave blocks of round 2's rule; 256^3: 0.188 - 0.198 against 0.204; 512^3 unchanged)
-  if (ry_force <= 0 && nchunk_force <= 0 && target_env <= 0 && ry == 2 && g.ny >= 32 && (int64_t)g.nx * g.ny * g.nz >= ((int64_t)1 << 24) && tiles16 < 128) {
+  if (ry_force <= 0 && nchunk_force <= 0 && ry == 2 && g.ny >= 32 && (int64_t)g.nx * g.ny * g.nz >= ((int64_t)1 << 24) && tiles16 < 128) {
     const int nchunk = std::max(1, std::min(256 / tiles16, g.nz / 8));
     if (tiles16 * nchunk >= 192) p = plan_tiles(g, 2, 8, nchunk, 0);
   }
-  p.pf         = 1;
-  p.nt         = 2;
-  // experiments (tools/experiments/r04_cg256.sh): FLUCA_CG_PLAN="ry,nw,nchunk" replaces the tiling of k_cg_A / k_cg_Bq on every grid
-  struct Force { int ry = 0, nw = 0, nchunk = 0; };
-  Force force;
-  if (const char *e = variant_env("FLUCA_CG_PLAN")) std::sscanf(e, "%d,%d,%d", &force.ry, &force.nw, &force.nchunk);
-  if (ry_force <= 0 && nchunk_force <= 0 && (force.ry == 1 || force.ry == 2) && (force.nw == 4 || (force.nw == 8 && force.ry == 2)) && g.ny >= 8) {
-    p    = plan_tiles(g, force.ry, force.nw, std::max(force.nchunk, 1), 0);
-    p.pf = 1;
-    p.nt = 2;
-  }
-  return p;
-}
-PlanA plan_cg_B(const GridP &g)
-{
-  const int64_t cells = (int64_t)g.nx * g.ny * g.nz;
-  const bool    big   = cells >= ((int64_t)1 << 26);  // 512^3: few fat blocks; below: one row per wave, two blocks per CU
-  int           ry = big ? (g.ny >= 32 ? 4 : (g.ny >= 8 ? 2 : 1)) : 1;
-  const int     target = big ? 256 : 512;
-  PlanA         p  = plan_tiles(g, ry, 4, 0, target);
-  while (p.nblocks < MIN_BLOCKS) {
-    p = plan_tiles(g, ry, 4, 0, target, 2);
-    if (p.nblocks >= MIN_BLOCKS || ry == 1) break;
-    ry /= 2;
-  }
-  p.nt         = 1;
   return p;
 }
 
-template <int RY, int NW, int PF, int NT, bool SQ>
-static void launch_cg_A_q(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const double *r, const DirRing &P, double *q, double *x, KspScal *s, double *partial, const FinCtx &fin)
+template <int RY, int NW>
+static void launch_cg_A_t(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const double *r, const DirRing &P, double *q, double *x, KspScal *s, double *partial, const FinCtx &fin)
 {
   const int  tiles = p.tiles_x * p.tiles_y;
   const int  rq    = (p.remap ? 1 : 0) | (p.qb ? 2 : 0);  // bit 0: XCD-contiguous block order, bit 1: q on the boundary layers
   const dim3 gr(p.nblocks), bl(64 * NW);
   if (p.probe) {
-    if (jac) hipLaunchKernelGGL((k_cg_A_probe<RY, NW, true, PF, NT, SQ>), gr, bl, 0, st, g, r, P, q, x, s, partial, p.nchunk, p.zc, p.tiles_x, tiles, rq, fin);
-    else hipLaunchKernelGGL((k_cg_A_probe<RY, NW, false, PF, NT, SQ>), gr, bl, 0, st, g, r, P, q, x, s, partial, p.nchunk, p.zc, p.tiles_x, tiles, rq, fin);
+    if (jac) hipLaunchKernelGGL((k_cg_A_probe<RY, NW, true>), gr, bl, 0, st, g, r, P, q, x, s, partial, p.nchunk, p.zc, p.tiles_x, tiles, rq, fin);
+    else hipLaunchKernelGGL((k_cg_A_probe<RY, NW, false>), gr, bl, 0, st, g, r, P, q, x, s, partial, p.nchunk, p.zc, p.tiles_x, tiles, rq, fin);
   } else {
-    if (jac) hipLaunchKernelGGL((k_cg_A<RY, NW, true, PF, NT, SQ>), gr, bl, 0, st, g, r, P, q, x, s, partial, p.nchunk, p.zc, p.tiles_x, tiles, rq, fin);
-    else hipLaunchKernelGGL((k_cg_A<RY, NW, false, PF, NT, SQ>), gr, bl, 0, st, g, r, P, q, x, s, partial, p.nchunk, p.zc, p.tiles_x, tiles, rq, fin);
+    if (jac) hipLaunchKernelGGL((k_cg_A<RY, NW, true>), gr, bl, 0, st, g, r, P, q, x, s, partial, p.nchunk, p.zc, p.tiles_x, tiles, rq, fin);
+    else hipLaunchKernelGGL((k_cg_A<RY, NW, false>), gr, bl, 0, st, g, r, P, q, x, s, partial, p.nchunk, p.zc, p.tiles_x, tiles, rq, fin);
   }
-}
-template <int RY, int NW, int PF, int NT>
-static void launch_cg_A_t(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const double *r, const DirRing &P, double *q, double *x, KspScal *s, double *partial, const FinCtx &fin)
-{
-#ifdef FL_KBENCH_VARIANTS
-  if (p.sq) {  // variant 2: q stored
-    launch_cg_A_q<RY, NW, PF, NT, true>(st, g, jac, p, r, P, q, x, s, partial, fin);
-    return;
-  }
-#endif
-  launch_cg_A_q<RY, NW, PF, NT, false>(st, g, jac, p, r, P, q, x, s, partial, fin);
-}
-template <int RY, int NW>
-static void launch_cg_A_v(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const double *r, const DirRing &P, double *q, double *x, KspScal *s, double *partial, const FinCtx &fin)
-{
-#ifdef FL_KBENCH_VARIANTS  // the whole sweep space of tools/kbench.py (build with -DFL_KBENCH_VARIANTS)
-  switch (p.pf * 10 + p.nt) {
-  case 0: launch_cg_A_t<RY, NW, 0, 0>(st, g, jac, p, r, P, q, x, s, partial, fin); return;
-  case 1: launch_cg_A_t<RY, NW, 0, 1>(st, g, jac, p, r, P, q, x, s, partial, fin); return;
-  case 2: launch_cg_A_t<RY, NW, 0, 2>(st, g, jac, p, r, P, q, x, s, partial, fin); return;
-  case 10: launch_cg_A_t<RY, NW, 1, 0>(st, g, jac, p, r, P, q, x, s, partial, fin); return;
-  case 11: launch_cg_A_t<RY, NW, 1, 1>(st, g, jac, p, r, P, q, x, s, partial, fin); return;
-  default: break;
-  }
-#endif
-  launch_cg_A_t<RY, NW, 1, 2>(st, g, jac, p, r, P, q, x, s, partial, fin);  // the shipped variant
 }
 void launch_cg_A(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const double *r, const DirRing &P, double *q, double *x, KspScal *s, double *partial, unsigned *counter, double *hist, int nhist, double *sums)
 {
@@ -1901,46 +1618,12 @@ void launch_cg_A(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const
   fin.nhist   = nhist;
   fin.enabled = counter != nullptr;
   switch (p.ry * 10 + p.nw) {
-#ifdef FL_KBENCH_VARIANTS
-  case 48: launch_cg_A_v<4, 8>(st, g, jac, p, r, P, q, x, s, partial, fin); break;
-  case 44: launch_cg_A_v<4, 4>(st, g, jac, p, r, P, q, x, s, partial, fin); break;
-#endif
-  case 28: launch_cg_A_v<2, 8>(st, g, jac, p, r, P, q, x, s, partial, fin); break;
-  case 24: launch_cg_A_v<2, 4>(st, g, jac, p, r, P, q, x, s, partial, fin); break;
-  default: launch_cg_A_v<1, 4>(st, g, jac, p, r, P, q, x, s, partial, fin); break;
+  case 28: launch_cg_A_t<2, 8>(st, g, jac, p, r, P, q, x, s, partial, fin); break;
+  case 24: launch_cg_A_t<2, 4>(st, g, jac, p, r, P, q, x, s, partial, fin); break;
+  default: launch_cg_A_t<1, 4>(st, g, jac, p, r, P, q, x, s, partial, fin); break;
   }
 }
 
-#ifdef FL_KBENCH_VARIANTS  // variant 2 of the CG pair (q stored, k_cg_B reads it back)
-template <int RY>
-static void launch_cg_B_ry(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const double *q, double *r, KspScal *s, double *partial, int stride, const FinCtx &fin)
-{
-  const dim3 gr(p.nblocks), bl(256);
-  if (p.nt) {
-    if (jac) hipLaunchKernelGGL((k_cg_B<RY, true, 1>), gr, bl, 0, st, g, q, r, s, partial, stride, p.nchunk, p.zc, p.tiles_x, fin);
-    else hipLaunchKernelGGL((k_cg_B<RY, false, 1>), gr, bl, 0, st, g, q, r, s, partial, stride, p.nchunk, p.zc, p.tiles_x, fin);
-  } else {
-    if (jac) hipLaunchKernelGGL((k_cg_B<RY, true, 0>), gr, bl, 0, st, g, q, r, s, partial, stride, p.nchunk, p.zc, p.tiles_x, fin);
-    else hipLaunchKernelGGL((k_cg_B<RY, false, 0>), gr, bl, 0, st, g, q, r, s, partial, stride, p.nchunk, p.zc, p.tiles_x, fin);
-  }
-}
-#endif  // FL_KBENCH_VARIANTS
-void launch_cg_B(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const double *q, double *r, KspScal *s, double *partial, int stride, unsigned *counter, double *hist, int nhist, double *sums)
-{
-#ifdef FL_KBENCH_VARIANTS
-  FinCtx fin;
-  fin.sums    = sums;
-  fin.counter = counter;
-  fin.hist    = hist;
-  fin.nhist   = nhist;
-  fin.enabled = counter != nullptr;
-  switch (p.ry) {
-  case 4: launch_cg_B_ry<4>(st, g, jac, p, q, r, s, partial, stride, fin); break;
-  case 2: launch_cg_B_ry<2>(st, g, jac, p, q, r, s, partial, stride, fin); break;
-  default: launch_cg_B_ry<1>(st, g, jac, p, q, r, s, partial, stride, fin); break;
-  }
-#endif
-}
 
 // k_cg_Bq on the tiling of k_cg_A (plan_cg_A).  xu: x-updates applied (0 none, 1 x += alpha p', K the K owed on every K-th iteration of a
 // ring of K direction buffers, K = 2, 3, 4 or 8); xz: the first of those launches in a solve (x = 0 is not read)
@@ -1949,9 +1632,9 @@ static void launch_cg_Bq_x(hipStream_t st, const GridP &g, bool jac, const PlanA
 {
   const int  tiles = p.tiles_x * p.tiles_y;
   const dim3 gr(p.nblocks), bl(64 * NW);
-  if (p.probe) hipLaunchKernelGGL((k_cg_Bq_probe<RY, NW, true, 2, XU, XZ>), gr, bl, 0, st, g, P, r, x, s, partial, stride, p.nchunk, p.zc, p.tiles_x, tiles, p.remap, fin);
-  else if (jac) hipLaunchKernelGGL((k_cg_Bq<RY, NW, true, 2, XU, XZ>), gr, bl, 0, st, g, P, r, x, s, partial, stride, p.nchunk, p.zc, p.tiles_x, tiles, p.remap, fin);
-  else hipLaunchKernelGGL((k_cg_Bq<RY, NW, false, 2, XU, XZ>), gr, bl, 0, st, g, P, r, x, s, partial, stride, p.nchunk, p.zc, p.tiles_x, tiles, p.remap, fin);
+  if (p.probe) hipLaunchKernelGGL((k_cg_Bq_probe<RY, NW, true, XU, XZ>), gr, bl, 0, st, g, P, r, x, s, partial, stride, p.nchunk, p.zc, p.tiles_x, tiles, p.remap, fin);
+  else if (jac) hipLaunchKernelGGL((k_cg_Bq<RY, NW, true, XU, XZ>), gr, bl, 0, st, g, P, r, x, s, partial, stride, p.nchunk, p.zc, p.tiles_x, tiles, p.remap, fin);
+  else hipLaunchKernelGGL((k_cg_Bq<RY, NW, false, XU, XZ>), gr, bl, 0, st, g, P, r, x, s, partial, stride, p.nchunk, p.zc, p.tiles_x, tiles, p.remap, fin);
 }
 template <int RY, int NW, int XU>
 static void launch_cg_Bq_z(hipStream_t st, const GridP &g, bool jac, const PlanA &p, bool xz, const DirRing &P, double *r, double *x, KspScal *s, double *partial, int stride, const FinCtx &fin)
@@ -2024,21 +1707,6 @@ void launch_stream_par(hipStream_t st, int nr, int nw, int u, int nt, int nblock
   if (nr == 1 && nw == 1) stream_par_t<1, 1>(st, u, nt, nblocks, n2, A, B, C, O0, O1, O2);
   else if (nr == 2 && nw == 1) stream_par_t<2, 1>(st, u, nt, nblocks, n2, A, B, C, O0, O1, O2);
   else stream_par_t<3, 3>(st, u, nt, nblocks, n2, A, B, C, O0, O1, O2);
-}
-
-void launch_cg_pupdate(hipStream_t st, const GridP &g, bool jac, const double *r, double *P0, double *P1, const KspScal *s)
-{
-#ifdef FL_KBENCH_VARIANTS
-  if (jac) hipLaunchKernelGGL(k_cg_pupdate<true>, grid3(g.nx, g.ny, g.nz), blk3(), 0, st, g, r, P0, P1, s);
-  else hipLaunchKernelGGL(k_cg_pupdate<false>, grid3(g.nx, g.ny, g.nz), blk3(), 0, st, g, r, P0, P1, s);
-#endif
-}
-int  apply_dot_blocks(const GridP &g) { return ((g.nx + 63) / 64) * ((g.ny + 3) / 4) * g.nz; }
-void launch_cg_apply_dot(hipStream_t st, const GridP &g, const double *P0, const double *P1, double *q, double *x, const KspScal *s, double *partial)
-{
-#ifdef FL_KBENCH_VARIANTS
-  hipLaunchKernelGGL(k_cg_apply_dot, grid3(g.nx, g.ny, g.nz), blk3(), 0, st, g, P0, P1, q, x, s, partial);
-#endif
 }
 
 }  // namespace fl

@@ -23,7 +23,7 @@ __device__ __forceinline__ double uniform(double v)
 }
 
 // ------------------------------------------------------------------------------------------------ tile walker
-// 128 x 4*RY x zc tiles like k_cg_B: lane = pair of x-adjacent cells, wave = RY rows, march in z.
+// 128 x 4*RY x zc tiles like k_cg_Bq: lane = pair of x-adjacent cells, wave = RY rows, march in z.
 
 struct Tile {
   int  i, il, k0, k1, lane, w, j0w, i0;
@@ -544,11 +544,9 @@ __device__ __forceinline__ void st_body(const GridP &g, const double *__restrict
     partial[(int64_t)tid * stride + blockIdx.x] = t;
   }
 }
-#ifndef FL_ST11_WPE
-#define FL_ST11_WPE 4  // the restricted residual fits 128 VGPRs without spilling: two 512-thread blocks per CU (2: one block, 142 VGPRs)
-#endif
+constexpr int ST11_WPE = 4;  // the restricted residual fits 128 VGPRs without spilling: two 512-thread blocks per CU (2: one block, 142 VGPRs)
 template <int RY, int NW, bool JAC, int MODE>
-__global__ void __launch_bounds__(64 * NW, (MODE == 11 && NW == 8) ? FL_ST11_WPE : 2) k_bcgs_st(GridP g, const double *__restrict__ stg, const double *e0, const double *e1, const double *e2, double *w0, double *w1, const KspScal *__restrict__ s,
+__global__ void __launch_bounds__(64 * NW, (MODE == 11 && NW == 8) ? ST11_WPE : 2) k_bcgs_st(GridP g, const double *__restrict__ stg, const double *e0, const double *e1, const double *e2, double *w0, double *w1, const KspScal *__restrict__ s,
                                                         double *__restrict__ partial, int stride, int nchunk, int zc, int tiles_x, int tiles, int remap, StAux ax)
 {
   st_body<RY, NW, JAC, MODE>(g, stg, e0, e1, e2, w0, w1, s, partial, stride, nchunk, zc, tiles_x, tiles, remap, ax);
@@ -959,11 +957,10 @@ TP tile_plan(const GridP &g)
   TP t;
   t.ry = g.ny >= 16 ? 2 : 1;
   t.tiles_x = (g.nx + 127) / 128;
-  const int tiles_y = (g.ny + 4 * t.ry - 1) / (4 * t.ry), tiles = t.tiles_x * tiles_y;
-  int       nchunk = std::max(1, (1024 + tiles / 2) / tiles);
-  nchunk   = std::max(1, std::min(std::min(nchunk, std::max(1, g.nz / 8)), g.nz));
-  t.zc     = (g.nz + nchunk - 1) / nchunk;
-  t.nchunk = (g.nz + t.zc - 1) / t.zc;
+  const int     tiles_y = (g.ny + 4 * t.ry - 1) / (4 * t.ry), tiles = t.tiles_x * tiles_y;
+  const ZChunks z       = z_chunks(g.nz, z_chunk_count(tiles, g.nz, 1024));
+  t.zc      = z.zc;
+  t.nchunk  = z.nchunk;
   t.nblocks = tiles * t.nchunk;
   return t;
 }
@@ -1016,22 +1013,18 @@ void cheb_st_t(fl_poisson *h, const PlanA &p, bool jac, double *X0, double *X1, 
   if (jac) hipLaunchKernelGGL((k_cheb_st<RY, NW, true>), gr, bl, 0, h->stream, h->g, X0, X1, X0, X1, B, D0, D1, h->scal, h->partial, h->partial_stride, p.nchunk, p.zc, p.tiles_x, tiles, p.remap);
   else hipLaunchKernelGGL((k_cheb_st<RY, NW, false>), gr, bl, 0, h->stream, h->g, X0, X1, X0, X1, B, D0, D1, h->scal, h->partial, h->partial_stride, p.nchunk, p.zc, p.tiles_x, tiles, p.remap);
 }
-// variant switch "cheb_staged": 1 (shipped) the one-step kernel on the LDS-staged walk (k_cheb_st), 0 round 1's k_cheb (kbench build only; the product keeps
-// k_cheb for the one case the staged walk does not cover: more blocks than partial-sum slots)
-static inline int cheb_staged_mode() { return FL_VARIANT(cheb_staged, 1); }
-// one Chebyshev step; returns the number of blocks whose partial sums the scalar kernel has to add up
+// one Chebyshev step on the LDS-staged walk (k_cheb_st), or k_cheb in the one case that walk does not cover: more blocks than partial-sum
+// slots; returns the number of blocks whose partial sums the scalar kernel has to add up
 int launch_cheb(fl_poisson *h, const TP &tp, bool jac, double *X0, double *X1, const double *B, double *D0, double *D1)
 {
-  if (cheb_staged_mode() != 0) {
-    const PlanA pa = plan_cg_A(h->g, 0, 0);
-    if (pa.nblocks <= h->partial_stride) {
-      switch (pa.ry * 10 + pa.nw) {
-      case 28: cheb_st_t<2, 8>(h, pa, jac, X0, X1, B, D0, D1); break;
-      case 24: cheb_st_t<2, 4>(h, pa, jac, X0, X1, B, D0, D1); break;
-      default: cheb_st_t<1, 4>(h, pa, jac, X0, X1, B, D0, D1); break;
-      }
-      return pa.nblocks;
+  const PlanA pa = plan_cg_A(h->g, 0, 0);
+  if (pa.nblocks <= h->partial_stride) {
+    switch (pa.ry * 10 + pa.nw) {
+    case 28: cheb_st_t<2, 8>(h, pa, jac, X0, X1, B, D0, D1); break;
+    case 24: cheb_st_t<2, 4>(h, pa, jac, X0, X1, B, D0, D1); break;
+    default: cheb_st_t<1, 4>(h, pa, jac, X0, X1, B, D0, D1); break;
     }
+    return pa.nblocks;
   }
   if (jac) {
     if (tp.ry == 2) cheb_t<2, true>(h, tp, X0, X1, B, D0, D1);
@@ -1155,12 +1148,7 @@ void launch_bcgs_st(fl_poisson *h, const PlanA &p, bool jac, const double *stg, 
 int fl_residual_padded(fl_poisson *h, double *xpad, const double *bpad, double *rpad)
 {
   FL_CHK(fl_fill_ghosts(h, xpad));
-  if (cheb_staged_mode() != 0) {
-    launch_bcgs_st<8>(h, plan_cg_A(h->g, 0, 0), false, xpad, bpad, nullptr, nullptr, rpad, nullptr);  // LDS-staged walk
-    return 0;
-  }
-  const TP tp = tile_plan(h->g);
-  launch_apply_pc(h, tp, false, xpad, rpad, bpad, nullptr, nullptr, 3);
+  launch_bcgs_st<8>(h, plan_cg_A(h->g, 0, 0), false, xpad, bpad, nullptr, nullptr, rpad, nullptr);  // LDS-staged walk
   return 0;
 }
 
@@ -1179,9 +1167,8 @@ bool fl_residual_restrict_fusable(const GridP &g)
 // the residual and the restriction).
 int fl_residual_restrict_padded(fl_poisson *h, double *xpad, const double *bpad, const double *wx, const double *wy, const double *wz, fl_poisson *hc, double *cpad)
 {
-  const int on = FL_VARIANT(mg_fused_restrict, 1);  // 0: residual and restriction as two passes (A/B runs)
   const GridP &g = h->g, &gc = hc->g;
-  if (!on || cheb_staged_mode() == 0 || !fl_residual_restrict_fusable(g)) return 1;
+  if (!fl_residual_restrict_fusable(g)) return 1;
   if (gc.nx * 2 != g.nx || gc.ny * 2 != g.ny || gc.nz * 2 != g.nz) return 1;
   const PlanA p = plan_cg_A(g, 0, 0);
   FL_CHK(fl_fill_ghosts(h, xpad));
@@ -1198,15 +1185,10 @@ int fl_residual_restrict_padded(fl_poisson *h, double *xpad, const double *bpad,
 int fl_apply_padded_dot(fl_poisson *h, double *xpad, double *ypad, double *xy)
 {
   FL_CHK(fl_fill_ghosts(h, xpad));
-  const TP    tp = tile_plan(h->g);
   const PlanA pa = plan_cg_A(h->g, 0, 0);
-  FL_CHK(fl_ensure_partials(h, std::max(tp.nblocks, pa.nblocks)));
-  int nbl = tp.nblocks;
-  if (cheb_staged_mode() != 0) {
-    launch_bcgs_st<7>(h, pa, false, xpad, nullptr, nullptr, nullptr, ypad, nullptr);  // LDS-staged walk
-    nbl = pa.nblocks;
-  } else launch_apply_pc(h, tp, false, xpad, ypad, nullptr, nullptr, h->partial, 0);
-  launch_reduce(h->stream, h->partial, nbl, h->partial_stride, 4, h->sums);
+  FL_CHK(fl_ensure_partials(h, pa.nblocks));
+  launch_bcgs_st<7>(h, pa, false, xpad, nullptr, nullptr, nullptr, ypad, nullptr);  // LDS-staged walk
+  launch_reduce(h->stream, h->partial, pa.nblocks, h->partial_stride, 4, h->sums);
   if (h->multi) FL_CHK(h->comm.allreduce(h->stream, h->sums, NSLOT));
   if (!xy) return 0;  // the caller takes x.y from h->sums[2] on the device (no host wait)
   FL_HIP(hipMemcpyAsync(xy, h->sums + 2, sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1242,10 +1224,8 @@ int fl_cheb_smooth_padded(fl_poisson *h, int nu, bool jac, bool guess_zero, bool
   o.norm_type        = FL_NORM_NONE;
   o.maxit            = nu;
   o.remove_nullspace = 0;
-  // PETSc's -mg_levels_ksp_chebyshev_esteig 0,0.1,0,1.1 applied to the bound (experiments: FLUCA_MG_CHEB_LO / _HI, fractions of the bound)
-  const char  *elo = variant_env("FLUCA_MG_CHEB_LO"), *ehi = variant_env("FLUCA_MG_CHEB_HI");
-  const double flo = elo ? std::atof(elo) : 0.1, fhi = ehi ? std::atof(ehi) : 1.1;
-  const double lam = fl_gershgorin_bound(h, jac), emin = flo * lam, emax = fhi * lam;
+  // PETSc's -mg_levels_ksp_chebyshev_esteig 0,0.1,0,1.1 applied to the bound
+  const double lam = fl_gershgorin_bound(h, jac), emin = 0.1 * lam, emax = 1.1 * lam;
   init_scal(h, &o);
   KspScal S0 = *h->scal_host;
   S0.scale     = 2. / (emax + emin);
@@ -1414,68 +1394,15 @@ int fl_cheb_smooth_padded(fl_poisson *h, int nu, bool jac, bool guess_zero, bool
 
 int fl_solve_bcgs(fl_poisson *h, const double *b, double *x, const fl_ksp_opts *o, fl_ksp_stats *st)
 {
-  // variant 0 (default): V0 = M S P and T0 = M S S0 are formed wherever they are needed and never stored (k_bcgs_st, 120 B/cell/iteration);
-  // any other value: the stored products of round 1 (k_apply_pc + k_bcgs_pw, 152 B/cell)
-  const int variant_forced = FL_VARIANT(bcgs_variant, -1);
-  const int variant = (o->variant == 0 && variant_forced >= 0) ? variant_forced : o->variant;
-  if (variant == 0) {
-    const GridP &g   = h->g;
-    const bool   jac = o->pc == FL_PC_JACOBI;
-    // vectors: r=R, P0=RP, P1/q=P (two buffers: a tile reads its neighbours' old P while they write the new one), xp=X, w0=S0
-    for (double **v : {&h->r, &h->P0, &h->P1, &h->q, &h->xp, &h->w0}) FL_CHK(fl_ensure_vec(h, v));
-    const TP    tp = tile_plan(g);
-    const PlanA pa = plan_cg_A(g, 0, 0);
-    FL_CHK(fl_ensure_partials(h, std::max(tp.nblocks, pa.nblocks)));
-    const int nhist = o->maxit + 1;
-    FL_CHK(fl_ensure_hist(h, nhist));
-    hipStream_t s = h->stream;
-    init_scal(h, o);
-    FL_HIP(hipEventRecord(h->ev0, s));
-    FL_HIP(hipMemcpyAsync(h->scal, h->scal_host, sizeof(KspScal), hipMemcpyHostToDevice, s));
-    for (double *v : {h->P1, h->q, h->xp}) FL_CHK(fl_zero_vec(h, v));
-    double *R = h->r, *RP = h->P0, *P = h->P1, *Pn = h->q, *X = h->xp, *S0 = h->w0;
-    auto    fin = [&](int mode) {
-      return [=](const double *partial, int nb, int stride, const double *sums) { hipLaunchKernelGGL(k_bcgs_fin, dim3(1), dim3(256), 0, s, mode, partial, nb, stride, sums, h->scal, h->hist, nhist); };
-    };
-    launch_pw<3>(h, tp, jac, b, nullptr, nullptr, nullptr, R, nullptr);
-    FL_CHK(fin_step(h, tp.nblocks, 3, fin(0)));
-    launch_pw<4>(h, tp, jac, nullptr, nullptr, nullptr, nullptr, R, RP);
-    const bool ghosts = fl_any_ghost_exchange(h);
-    const int  every  = o->check_every > 0 ? o->check_every : 16;
-    int        it = 0;
-    bool       done = false;
-    while (!done) {
-      const int stop = std::min(o->maxit, it + every);
-      for (; it < stop; ++it) {
-        // P' = R - omega_old beta (M S P - vshift) + beta P   (the old P's ghosts are still those filled for the iteration before)
-        launch_bcgs_st<5>(h, pa, jac, P, R, nullptr, nullptr, Pn, nullptr);
-        std::swap(P, Pn);
-        if (ghosts) FL_CHK(fl_fill_ghosts(h, P));
-        launch_bcgs_st<1>(h, pa, jac, P, RP, nullptr, nullptr, nullptr, nullptr);
-        FL_CHK(fin_step(h, pa.nblocks, 4, fin(1)));
-        launch_bcgs_st<2>(h, pa, jac, P, R, nullptr, nullptr, S0, nullptr);
-        FL_CHK(fin_step(h, pa.nblocks, 3, fin(2)));
-        if (ghosts) FL_CHK(fl_fill_ghosts(h, S0));
-        launch_bcgs_st<3>(h, pa, jac, S0, nullptr, nullptr, nullptr, nullptr, nullptr);
-        FL_CHK(fin_step(h, pa.nblocks, 4, fin(3)));
-        launch_bcgs_st<4>(h, pa, jac, S0, P, X, RP, X, R);
-        FL_CHK(fin_step(h, pa.nblocks, 3, fin(4)));
-      }
-      FL_CHK(fl_poll_scal(h));
-      if (h->scal_host->reason != 0 || it >= o->maxit) done = true;
-    }
-    launch_unpad_copy(s, g, X, x, nullptr);
-    return finish_stats(h, o, st);
-  }
-#ifndef FL_KBENCH_VARIANTS
-  return FL_ERR_SUP;  // the stored-product form of round 1 lives in the kbench build only (include/fluca_hip.h, fl_ksp_opts.variant)
-#else
+  // V0 = M S P and T0 = M S S0 are formed wherever they are needed and never stored (k_bcgs_st, 120 B/cell/iteration)
+  if (o->variant != 0) return FL_ERR_SUP;  // the stored-product form left the library (include/fluca_hip.h, fl_ksp_opts.variant)
   const GridP &g   = h->g;
   const bool   jac = o->pc == FL_PC_JACOBI;
-  // vectors: r=R, P0=RP, P1=P, q=V0, xp=X, w0=S0, w1=T0
-  for (double **v : {&h->r, &h->P0, &h->P1, &h->q, &h->xp, &h->w0, &h->w1}) FL_CHK(fl_ensure_vec(h, v));
-  const TP tp = tile_plan(g);
-  FL_CHK(fl_ensure_partials(h, tp.nblocks));
+  // vectors: r=R, P0=RP, P1/q=P (two buffers: a tile reads its neighbours' old P while they write the new one), xp=X, w0=S0
+  for (double **v : {&h->r, &h->P0, &h->P1, &h->q, &h->xp, &h->w0}) FL_CHK(fl_ensure_vec(h, v));
+  const TP    tp = tile_plan(g);
+  const PlanA pa = plan_cg_A(g, 0, 0);
+  FL_CHK(fl_ensure_partials(h, std::max(tp.nblocks, pa.nblocks)));
   const int nhist = o->maxit + 1;
   FL_CHK(fl_ensure_hist(h, nhist));
   hipStream_t s = h->stream;
@@ -1483,7 +1410,7 @@ int fl_solve_bcgs(fl_poisson *h, const double *b, double *x, const fl_ksp_opts *
   FL_HIP(hipEventRecord(h->ev0, s));
   FL_HIP(hipMemcpyAsync(h->scal, h->scal_host, sizeof(KspScal), hipMemcpyHostToDevice, s));
   for (double *v : {h->P1, h->q, h->xp}) FL_CHK(fl_zero_vec(h, v));
-  double *R = h->r, *RP = h->P0, *P = h->P1, *V0 = h->q, *X = h->xp, *S0 = h->w0, *T0 = h->w1;
+  double *R = h->r, *RP = h->P0, *P = h->P1, *Pn = h->q, *X = h->xp, *S0 = h->w0;
   auto    fin = [&](int mode) {
     return [=](const double *partial, int nb, int stride, const double *sums) { hipLaunchKernelGGL(k_bcgs_fin, dim3(1), dim3(256), 0, s, mode, partial, nb, stride, sums, h->scal, h->hist, nhist); };
   };
@@ -1497,24 +1424,25 @@ int fl_solve_bcgs(fl_poisson *h, const double *b, double *x, const fl_ksp_opts *
   while (!done) {
     const int stop = std::min(o->maxit, it + every);
     for (; it < stop; ++it) {
-      launch_pw<0>(h, tp, jac, R, V0, nullptr, nullptr, P, nullptr);
+      // P' = R - omega_old beta (M S P - vshift) + beta P   (the old P's ghosts are still those filled for the iteration before)
+      launch_bcgs_st<5>(h, pa, jac, P, R, nullptr, nullptr, Pn, nullptr);
+      std::swap(P, Pn);
       if (ghosts) FL_CHK(fl_fill_ghosts(h, P));
-      launch_apply_pc(h, tp, jac, P, V0, RP, h->scal, h->partial, 0);
-      FL_CHK(fin_step(h, tp.nblocks, 4, fin(1)));
-      launch_pw<1>(h, tp, jac, R, V0, nullptr, nullptr, S0, nullptr);
-      FL_CHK(fin_step(h, tp.nblocks, 3, fin(2)));
+      launch_bcgs_st<1>(h, pa, jac, P, RP, nullptr, nullptr, nullptr, nullptr);
+      FL_CHK(fin_step(h, pa.nblocks, 4, fin(1)));
+      launch_bcgs_st<2>(h, pa, jac, P, R, nullptr, nullptr, S0, nullptr);
+      FL_CHK(fin_step(h, pa.nblocks, 3, fin(2)));
       if (ghosts) FL_CHK(fl_fill_ghosts(h, S0));
-      launch_apply_pc(h, tp, jac, S0, T0, nullptr, h->scal, h->partial, 0);
-      FL_CHK(fin_step(h, tp.nblocks, 4, fin(3)));
-      launch_pw<2>(h, tp, jac, P, S0, T0, RP, X, R);
-      FL_CHK(fin_step(h, tp.nblocks, 3, fin(4)));
+      launch_bcgs_st<3>(h, pa, jac, S0, nullptr, nullptr, nullptr, nullptr, nullptr);
+      FL_CHK(fin_step(h, pa.nblocks, 4, fin(3)));
+      launch_bcgs_st<4>(h, pa, jac, S0, P, X, RP, X, R);
+      FL_CHK(fin_step(h, pa.nblocks, 3, fin(4)));
     }
     FL_CHK(fl_poll_scal(h));
     if (h->scal_host->reason != 0 || it >= o->maxit) done = true;
   }
   launch_unpad_copy(s, g, X, x, nullptr);
   return finish_stats(h, o, st);
-#endif
 }
 
 // KSPCG with -ksp_cg_single_reduction (fl_ksp_opts.cg_single_reduction): one reduction point, hence one all-reduce and one scalar

@@ -113,46 +113,13 @@ struct MgLin {
   const int    *pn[3];
   const double *pw[3];
 };
-__global__ void __launch_bounds__(256) k_mg_prolong_lin_add(GridP gf, GridP gc, int rx, int ry, int rz, MgLin t, const double *__restrict__ coarse, double *__restrict__ fine)
-{
-  // branch-free: where a cell has no neighbour to interpolate with its offset is 0 and its weight 0, so the "neighbour" read is the
-  // parent itself.  The two cells of a pair share their four (J, K) lines of the coarse grid.
-  const Owned o = owned_of(gf);
-  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < o.npairs; q += (int64_t)gridDim.x * blockDim.x) {
-    const int     ip = (int)(q % o.npair_row);
-    const int64_t row = q / o.npair_row;
-    const int     j = (int)(row % gf.ny), k = (int)(row / gf.ny), i = 2 * ip;
-    const bool    two = i + 1 < gf.nx;
-    const int     i1 = two ? i + 1 : i;
-    const int64_t fo = gf.off0 + (int64_t)k * gf.sxy + (int64_t)j * gf.sx + i;
-    const int64_t cjk = gc.off0 + (int64_t)(k / rz) * gc.sxy + (int64_t)(j / ry) * gc.sx;
-    const double  wy = t.pw[1][j], wz = t.pw[2][k];
-    const int64_t oy = (int64_t)t.pn[1][j] * gc.sx, oz = (int64_t)t.pn[2][k] * gc.sxy;
-    const int64_t c0 = cjk + i / rx, c1 = cjk + i1 / rx;
-    const int     ox0 = t.pn[0][i], ox1 = t.pn[0][i1];
-    const double  wx0 = t.pw[0][i], wx1 = t.pw[0][i1];
-    double        v0[4], v1[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const int64_t sh = ((a & 1) ? oy : 0) + ((a & 2) ? oz : 0);
-      const double  p0 = coarse[c0 + sh], p1 = coarse[c1 + sh];
-      v0[a] = fma(wx0, coarse[c0 + sh + ox0] - p0, p0);
-      v1[a] = fma(wx1, coarse[c1 + sh + ox1] - p1, p1);
-    }
-    const double a0 = fma(wy, v0[1] - v0[0], v0[0]), b0 = fma(wy, v0[3] - v0[2], v0[2]);
-    const double a1 = fma(wy, v1[1] - v1[0], v1[0]), b1 = fma(wy, v1[3] - v1[2], v1[2]);
-    double2      f = ldp(fine, fo, two);
-    f.x += fma(wz, b0 - a0, a0);
-    if (two) f.y += fma(wz, b1 - a1, a1);
-    stp(fine, fo, two, f);
-  }
-}
 
-// The same arithmetic on a tile walk: block = 4 rows x 128 cells (a lane owns a pair) marching through ZC planes, so that row and plane
-// numbers are wave-uniform (their table entries arrive by scalar loads, no 64-bit division per pair as in the grid-stride form above) and
-// the coarse lines of two consecutive planes / rows are the same lines (L1 / L2 hits).  R2: every axis is coarsened by two (shifts).
+// Branch-free: where a cell has no neighbour to interpolate with its offset is 0 and its weight 0, so the "neighbour" read is the parent
+// itself.  The two cells of a pair share their four (J, K) lines of the coarse grid.  A tile walk: block = 4 rows x 128 cells (a lane owns a
+// pair) marching through ZC planes, so that row and plane numbers are wave-uniform (their table entries arrive by scalar loads, no 64-bit
+// division per pair) and the coarse lines of two consecutive planes / rows are the same lines (L1 / L2 hits).  For levels that are not halved
+// on every axis; those that are take k_mg_prolong_lin_cc below.
 // 512^3: 1.1 ms -> see profiles/r03_mg_bench.txt (the fine level moves 17 B/cell: 0.38 ms at 6 TB/s).
-template <bool R2>
 __global__ void __launch_bounds__(256) k_mg_prolong_lin_tile(GridP gf, GridP gc, int rx, int ry, int rz, MgLin t, const double *__restrict__ coarse, double *__restrict__ fine, int zc)
 {
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -161,7 +128,7 @@ __global__ void __launch_bounds__(256) k_mg_prolong_lin_tile(GridP gf, GridP gc,
   const int     k0 = (int)blockIdx.z * zc, k1 = min(k0 + zc, gf.nz);
   const bool    two = i + 1 < gf.nx;
   const int     i1 = two ? i + 1 : i;
-  const int     I0 = R2 ? i >> 1 : i / rx, I1 = R2 ? i1 >> 1 : i1 / rx, J = R2 ? j >> 1 : j / ry;
+  const int     I0 = i / rx, I1 = i1 / rx, J = j / ry;
   const int     ox0 = t.pn[0][i], ox1 = t.pn[0][i1];
   const double  wx0 = t.pw[0][i], wx1 = t.pw[0][i1];
   const double  wy = t.pw[1][j];
@@ -169,7 +136,7 @@ __global__ void __launch_bounds__(256) k_mg_prolong_lin_tile(GridP gf, GridP gc,
   const double *cj = coarse + gc.off0 + (int64_t)J * gc.sx;
   double       *fj = fine + gf.off0 + (int64_t)j * gf.sx + i;
   for (int k = k0; k < k1; ++k) {
-    const int     K = R2 ? k >> 1 : k / rz;
+    const int     K = k / rz;
     const double  wz = t.pw[2][k];
     const int64_t oz = (int64_t)t.pn[2][k] * gc.sxy;
     const double *ck = cj + (int64_t)K * gc.sxy;
@@ -245,7 +212,7 @@ __global__ void __launch_bounds__(256) k_mg_prolong_lin_cc(GridP gf, GridP gc, M
         double2 add;
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
-          // the four lines of k_mg_prolong_lin_add: (0,0), (oy,0), (0,oz), (oy,oz)
+          // the four lines of k_mg_prolong_lin_tile: (0,0), (oy,0), (0,oz), (oy,oz)
           const double v0 = Xc[1][a], v1 = oy[b] < 0 ? Xc[0][a] : (oy[b] > 0 ? Xc[2][a] : Xc[1][a]);
           const double z0 = oz < 0 ? Xm[1][a] : (oz > 0 ? Xp[1][a] : Xc[1][a]);
           const double z1 = oz < 0 ? (oy[b] < 0 ? Xm[0][a] : (oy[b] > 0 ? Xm[2][a] : Xm[1][a]))
@@ -690,7 +657,6 @@ int mg_build_levels(fl_poisson *h, fl_mg *mg, int max_levels)
   for (size_t l = 0; l < mg->lv.size(); ++l) {
     MgLevel    &L = mg->lv[l];
     fl_poisson *hl = L.h;
-    if (hl->nv_il > 1) return FL_ERR_SUP;  // the experimental row-interleaved vector layout is not wired into the cycle
     for (double **v : {&hl->r, &hl->P0, &hl->q, &hl->xp}) FL_CHK(fl_ensure_vec(hl, v));
     if (l + 1 == mg->lv.size()) {
       FL_CHK(alloc_cells(hl, &L.x));
@@ -727,7 +693,7 @@ int vcycle(fl_mg *mg, size_t l, const fl_ksp_opts *o, bool *sums = nullptr, cons
     so.rtol  = 1e-2;
     so.maxit = 200;
     if (subq) hipLaunchKernelGGL(k_mg_pwd<5>, dim3(nblk_pairs(h->g)), dim3(256), 0, h->stream, h->g, (const MgScal *)mg->scal, (const double *)nullptr, subq, (double *)nullptr, h->r);
-    if (!h->multi && h->ncell <= MG_COARSE_MAX && h->nv_il == 1 && fl_mg_coarse_mode() != 0) {
+    if (!h->multi && h->ncell <= MG_COARSE_MAX && fl_mg_coarse_mode() != 0) {
       // one workgroup, no host poll, straight from the padded right-hand side into the padded answer
       const int per = (h->ax[0].periodic ? 1 : 0) | (h->ax[1].periodic ? 2 : 0) | (h->ax[2].periodic ? 4 : 0);
       hipLaunchKernelGGL(k_mg_coarse_cg, dim3(1), dim3(256), 0, h->stream, h->g, per, so.remove_nullspace, so.rtol, so.atol, so.dtol, so.maxit, (const double *)h->r, h->xp);
@@ -765,17 +731,15 @@ int vcycle(fl_mg *mg, size_t l, const fl_ksp_opts *o, bool *sums = nullptr, cons
       t.pn[d] = L.pn[d];
       t.pw[d] = L.pw[d];
     }
-    const int tiled = FL_VARIANT(mg_prolong_tile, 2);  // 2 (shipped): parent-centred where every axis is halved, else 1: the tile walk; 0: the grid-stride kernel
-    if (tiled >= 2 && L.r[0] == 2 && L.r[1] == 2 && L.r[2] == 2) {
+    if (L.r[0] == 2 && L.r[1] == 2 && L.r[2] == 2) {
       const int  kc = 4;
       const GridP &gcs = C.h->g;
       hipLaunchKernelGGL(k_mg_prolong_lin_cc, dim3((gcs.nx + 61) / 62, (gcs.ny + 3) / 4, (gcs.nz + kc - 1) / kc), dim3(256), 0, h->stream, h->g, gcs, t, (const double *)C.h->xp, h->xp, kc);
-    } else if (tiled) {
+    } else {
       const int  zc = 8;
       const dim3 grid((h->g.nx + 127) / 128, (h->g.ny + 3) / 4, (h->g.nz + zc - 1) / zc);
-      if (L.r[0] == 2 && L.r[1] == 2 && L.r[2] == 2) hipLaunchKernelGGL((k_mg_prolong_lin_tile<true>), grid, dim3(256), 0, h->stream, h->g, C.h->g, L.r[0], L.r[1], L.r[2], t, (const double *)C.h->xp, h->xp, zc);
-      else hipLaunchKernelGGL((k_mg_prolong_lin_tile<false>), grid, dim3(256), 0, h->stream, h->g, C.h->g, L.r[0], L.r[1], L.r[2], t, (const double *)C.h->xp, h->xp, zc);
-    } else hipLaunchKernelGGL(k_mg_prolong_lin_add, dim3(nblk_pairs(h->g)), dim3(256), 0, h->stream, h->g, C.h->g, L.r[0], L.r[1], L.r[2], t, (const double *)C.h->xp, h->xp);
+      hipLaunchKernelGGL(k_mg_prolong_lin_tile, grid, dim3(256), 0, h->stream, h->g, C.h->g, L.r[0], L.r[1], L.r[2], t, (const double *)C.h->xp, h->xp, zc);
+    }
   } else hipLaunchKernelGGL(k_mg_prolong_add, dim3(nblk_pairs(h->g)), dim3(256), 0, h->stream, h->g, C.h->g, L.r[0], L.r[1], L.r[2], C.h->xp, h->xp);  // x += P e_c
   bool got = want;
   const int nu_post = knob(K_mg_post_smooth) > 0 ? knob(K_mg_post_smooth) : nu;
@@ -852,7 +816,6 @@ int fl_solve_cg_mg(fl_poisson *h, const double *b, double *x, const fl_ksp_opts 
   int     bad_pq = 0;
   std::vector<double> hist;
   // z' = z - m 1 with m = mean(z):  z'.z' = z.z - N m^2,  r.z' = r.z - m sum r   (k_mg_scal<1>)
-  const bool fused_dots = FL_VARIANT(mg_fused_dots, 1) != 0;  // 0: always the separate k_mg_dots pass (A/B runs)
   MgScal *S = mg->scal;
   {
     MgScal init;
@@ -873,7 +836,7 @@ int fl_solve_cg_mg(fl_poisson *h, const double *b, double *x, const fl_ksp_opts 
   const double *subq = nullptr;  // r -= alpha * subq is owed (taken care of inside the next cycle, alpha from the device)
   // [r -= alpha q ;] z = M^-1 r, the five sums, the scalars that follow from them, and their copy on the way to the host (slot `it & 1`)
   auto cycle_and_sums = [&](int it, bool first) -> int {
-    bool got = fused_dots;
+    bool got = true;
     FL_CHK(vcycle(mg, 0, o, &got, subq));
     if (!got) FL_CHK(dots_dev(h->xp, h->r));  // (else the cycle's last smoothing sweep formed the sums on its way)
     const int a = it & 1;

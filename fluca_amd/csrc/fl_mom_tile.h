@@ -4,7 +4,7 @@
 //   ComputeConvectionOperator_Private          cnlinearcart3d.c:873-1294     (C v)_c = 1/2 d/dx_d (v_c V0_d + v0interp_c v_d)
 //   NSFormJacobian_CNLinear_Cart3d_Internal    cnlinearcart3d.c:2930-2941    A = I + dt C - (mu dt / 2 rho) L
 //
-// The same arithmetic per cell as k_mom_apply (mom_axis), in the shape of k_cg_A:
+// In the shape of k_cg_A:
 //  * a wave owns one row of 128 cells, a lane two x-adjacent cells: every stream (3 velocity components, 12 face fields, 3 outputs)
 //    moves with 16-byte accesses, one 1 KiB wave-instruction per row and plane;
 //  * ONE register set per stream: a stream's load for the next plane is issued as soon as the phase that consumes the current
@@ -45,7 +45,7 @@ __device__ __forceinline__ double from_next_lane(double v, double fill)
 }
 
 // ---- the rows of A in coefficient form ------------------------------------------------------------------------------------------
-// Along one axis D the row of component c is (mom_axis, term by term)
+// Along one axis D the row of component c is, term by term,
 //   cC [ vl (Il . u_c) + vh (Ih . u_c) + wl_c (Nl . u_D) + wh_c (Nh . u_D) ] + cL (L . u_c)
 // with vl / vh = V0_D on the low / high face, wl_c / wh_c = v0interp_{c,D} there, Il / Ih the face-interpolation rows of the
 // component's rule (tangential T, or normal N when c == D) and Nl / Nh those of the face-normal component.  V0 is the same for the three

@@ -16,10 +16,6 @@
 #include "fl_handle.h"
 #include "fl_device.h"
 
-#ifndef FL_MOM_WPE
-#define FL_MOM_WPE 2  // waves per SIMD the register allocator must leave room for (see tools/experiments/mom_wpe.sh)
-#endif
-
 namespace fl {
 
 struct MomP {
@@ -37,13 +33,6 @@ struct FaceT {
   const int    *c0[3][3];
 };
 
-__device__ __forceinline__ double uniform_d(double v)
-{
-  // v is wave-uniform: keep it in scalar registers
-  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-
 // 1/d: hardware estimate + two Newton steps (correctly rounded for all but a vanishing fraction of inputs)
 __device__ __forceinline__ double recip(double d)
 {
@@ -52,353 +41,6 @@ __device__ __forceinline__ double recip(double d)
   r        = fma(r, fma(-d, r, 1.), r);
   return r;
 }
-
-// uniform base pointer + per-lane 32-bit byte offset: lets the backend use the scalar-base addressing mode of global_load
-__device__ __forceinline__ double LD(const double *base, unsigned byteoff) { return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(base) + byteoff); }
-__device__ __forceinline__ void   ST(double *base, unsigned byteoff, double v) { *reinterpret_cast<double *>(reinterpret_cast<char *>(base) + byteoff) = v; }
-
-struct MTile {
-  int  ic, jc, i, j, k0, k1;
-  bool own;
-};
-__device__ __forceinline__ MTile mom_tile(const GridP &g, int tiles_x, int nchunk, int zc)
-{
-  MTile     t;
-  const int b = blockIdx.x, chunk = b % nchunk, tile = b / nchunk;
-  t.i   = (tile % tiles_x) * 64 + (threadIdx.x & 63);
-  t.j   = (tile / tiles_x) * 4 + (threadIdx.x >> 6);
-  t.own = t.i < g.nx && t.j < g.ny;
-  t.ic  = min(t.i, g.nx - 1);
-  t.jc  = min(t.j, g.ny - 1);
-  t.k0  = chunk * zc;
-  t.k1  = min(t.k0 + zc, g.nz);
-  return t;
-}
-
-// One axis' share of row (cell, component C) of A.  T(slot) yields the 1-D table number of this cell along axis D
-// (build_axis_momentum).  um/uc/up: component C at the cell and its two neighbours along D; nm/nc/np: the face-normal
-// component D at the same places (the same numbers when C == D).  WALL == false is the fast path for cells that are
-// not next to a wall of this axis: "normal" and "tangential" rules coincide, there is no far column, and the low / high
-// face rows are plain two-point interpolations -- 7 table numbers instead of 20.
-template <int D, int C, bool WALL, bool DG, class TF>
-__device__ __forceinline__ void mom_axis(TF T, double um, double uc, double up, double ufar, double nm, double nc, double np, double vl, double vh, double wl, double wh, double cC, double cL,
-                                         double &yacc, double &dacc)
-{
-  constexpr int r = C == D ? 1 : 0;
-  double        L0, L1, L2, L3 = 0., Tl0 = 0., Tl1 = 0., Tl2 = 0., Th0 = 0., Th1 = 0., Th2 = 0., Nl0, Nl1, Nl2 = 0., Nh0 = 0., Nh1, Nh2;
-  if (WALL) {
-    L0 = T(r * 4 + 0); L1 = T(r * 4 + 1); L2 = T(r * 4 + 2); L3 = T(r * 4 + 3);
-    Nl0 = T(11); Nl1 = T(12); Nl2 = T(13);
-    Nh0 = T(17); Nh1 = T(18); Nh2 = T(19);
-    if (!r) {
-      Tl0 = T(8); Tl1 = T(9); Tl2 = T(10);
-      Th0 = T(14); Th1 = T(15); Th2 = T(16);
-    }
-  } else {
-    L0 = T(0); L1 = T(1); L2 = T(2);
-    Nl0 = T(8); Nl1 = T(9);
-    Nh1 = T(15); Nh2 = T(16);
-    Tl0 = Nl0; Tl1 = Nl1; Th1 = Nh1; Th2 = Nh2;
-  }
-  // face values of the face-normal component ("normal" rule): second term v0interp_C v_D, and the first term when C == D
-  const double Glo = Nl0 * nm + Nl1 * nc + Nl2 * np, Ghi = Nh0 * nm + Nh1 * nc + Nh2 * np;
-  const double Ilo = r ? Glo : Tl0 * um + Tl1 * uc + Tl2 * up, Ihi = r ? Ghi : Th0 * um + Th1 * uc + Th2 * up;
-  const double conv = vl * Ilo + vh * Ihi + wl * Glo + wh * Ghi;
-  double       lap = L0 * um + L1 * uc + L2 * up;
-  if (WALL) lap += L3 * ufar;
-  yacc += cC * conv + cL * lap;
-  if (DG) {
-    double dc = r ? (vl + wl) * Nl1 + (vh + wh) * Nh1 : vl * Tl1 + vh * Th1;
-    dacc += cC * dc + cL * L1;
-  }
-}
-
-constexpr int MOM_RY = 8;            // grid rows per block = waves per block
-[[maybe_unused]] constexpr int MOM_NT = 64 * MOM_RY;  // (the kbench build's k_mom_apply)
-
-// LDS image of one plane of a 64 x MOM_RY tile: what a cell needs from its x/y neighbours.
-struct MomLds {
-  double u[3][MOM_RY + 2][66];   // velocity components incl. a one-cell ring (rows -1..RY, columns -1..64)
-  double fx[4][MOM_RY][66];      // V0x, v0interp_{0,1,2} on x-faces: low face of column 0..64 (64 = high face of the last cell)
-  double fy[4][MOM_RY + 1][64];  // the same on y-faces: low face of row 0..RY
-};
-
-// y = [1/diag] A x   (x padded with valid ghosts; y padded, or unpadded component-major when OUT == 1).
-// OUT == 2 writes diag(A) instead (padded).  DOT: partial slots 0 sum y, 1 y.o (o padded, may be NULL), 2 x.y, 3 y.y.
-//
-// Block = 64 x MOM_RY tile marching through a z chunk, one thread per cell column, all three components.
-//  * Every global address is (wave-uniform base) + (per-lane 32-bit byte offset).
-//  * Every value is fetched from global memory exactly once per tile: the centre column of the 3 velocity components
-//    and the low faces of the 12 face fields (15 streams), plus the one-cell ring of the tile.  x/y neighbours and high
-//    faces are exchanged through LDS (double-buffered, one barrier per plane); z neighbours ride in registers.
-//  * Software pipeline: while plane k is computed, the loads of plane k+1 (faces, ring) and k+2 (velocity, z-faces) are
-//    in flight; they are consumed by the register rotation at the end of the iteration.
-#ifdef FL_KBENCH_VARIANTS  // round 1 / 2's momentum product (A/B runs)
-template <bool DOT, bool JAC, int OUT>
-__global__ void __launch_bounds__(MOM_NT, FL_MOM_WPE) k_mom_apply(GridP g, MomP m, const double *__restrict__ x, double *__restrict__ y, const double *__restrict__ F, int64_t cs, const double *__restrict__ o,
-                                                                const KspScal *__restrict__ s, double *__restrict__ partial, int pstride, int tiles_x, int nchunk, int zc, int order)
-{
-  __shared__ MomLds lds[2];
-  __shared__ double ltabx[MOM_NTAB][64];  // the x-axis table numbers of this tile's 64 columns (general rows of wall tiles)
-  __shared__ double red[4 * MOM_RY];
-  if (s && s->reason != 0) return;
-  constexpr bool DG = JAC || OUT == 2;
-  // order 1: chunk-major and XCD-contiguous like k_cg_A (blocks are dealt round-robin over the 8 XCDs: give each XCD a contiguous range of
-  // neighbouring tiles of one z chunk, so that the ring a tile re-reads was just fetched into the same L2 by its neighbour)
-  int b = blockIdx.x, chunk, tile;
-  if (order == 1) {
-    const int nb = gridDim.x, tiles = nb / nchunk;
-    if ((nb & 7) == 0) b = (b & 7) * (nb >> 3) + (b >> 3);
-    chunk = b / tiles;
-    tile  = b % tiles;
-  } else {
-    chunk = b % nchunk;
-    tile  = b / nchunk;
-  }
-  const int      lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int      i0 = (tile % tiles_x) * 64, j0 = (tile / tiles_x) * MOM_RY, j = j0 + w;
-  const int      i = i0 + lane;
-  const bool     own = i < g.nx && j < g.ny;
-  // loads are clamped to the ghost column / row (valid memory holding the right neighbour of the last cell)
-  const int      il = min(i, g.nx), jl = min(j, g.ny), it = min(i, g.nx - 1), jt = min(j, g.ny - 1);
-  const int      k0 = chunk * zc, k1 = min(k0 + zc, g.nz);
-  const unsigned lo0 = (unsigned)(il - i0) * 8u;
-  // ring: lane 0 fetches column -1 of its row, lane 63 column 64 (clamped), the others nothing
-  const bool     ringlane = lane == 0 || lane == 63;
-  const unsigned loring0 = lane == 0 ? 0u : (unsigned)(min(i0 + 64, g.nx) - i0 + 1) * 8u;  // relative to (row base - 1)
-  const bool     toprow = w == MOM_RY - 1, botrow = w == 0;                                   // wave-uniform
-  const int      jr = botrow ? max(j0 - 1, -1) : min(j0 + MOM_RY, g.ny);                      // the ring row this wave fetches
-  const unsigned far0 = it == 0 ? 32u : 0u;          // relative to (base - 2): column i+2 at the low wall, i-2 elsewhere
-  const bool     xwall = i0 == 0 || i0 + 64 >= g.nx;  // block-uniform: this tile touches an x wall
-  const bool     ywall = jt == 0 || jt == g.ny - 1;   // wave-uniform
-  const int      lx = m.len[0], ly = m.len[1], lz = m.len[2];
-  const double  *tabx = m.tab[0] + it, *taby = m.tab[1] + jt;
-  double         txi[7], tyi[7];  // fast-path numbers of the x and y axes: fixed for the whole chunk
-  {
-    const int sl[7] = {0, 1, 2, 8, 9, 15, 16};
-#pragma unroll
-    for (int a = 0; a < 7; ++a) {
-      txi[a] = tabx[(int64_t)sl[a] * lx];
-      tyi[a] = taby[(int64_t)sl[a] * ly];
-    }
-  }
-  if (xwall) {
-    // wall tiles read the general x rows from LDS: a global load in the compute phase would have to wait for every
-    // prefetch issued before it (vmcnt retires in order)
-    for (int q = w; q < MOM_NTAB; q += MOM_RY) ltabx[q][lane] = tabx[(int64_t)q * lx];
-    __syncthreads();
-  }
-  auto          slot7 = [](int q) { return q < 3 ? q : (q < 10 ? q - 5 : q - 10); };  // 0,1,2,8,9,15,16 -> 0..6
-  const int64_t sx = g.sx, sxy = g.sxy;
-  const int64_t foy = (jt == 0 ? 2 : -2) * sx;
-  const int64_t ncell = (int64_t)g.nx * g.ny * g.nz;
-  const int64_t rb0 = g.off0 + (int64_t)jl * sx + i0;  // wave-uniform offset of this row in plane 0
-  const int64_t rr0 = g.off0 + (int64_t)jr * sx + i0;  // ... of the ring row
-  const double  cC = m.cC, cL = m.cL;
-  double        acc[4] = {0., 0., 0., 0.};
-
-  // registers of the pipeline.  Face fields are indexed f = 0: V0, 1..3: v0interp_{0,1,2}.
-  double uzm[3], uc[3], uzp[3], vzl[4], vzh[4], fxl[4], fyl[4], oc[3] = {0., 0., 0.};
-  auto   fld = [&](int f, int d) { return F + (f == 0 ? d : 3 + (f - 1) * 3 + d) * cs; };
-  {
-    const int64_t rb = rb0 + (int64_t)k0 * sxy, rr = rr0 + (int64_t)k0 * sxy;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double *X = x + c * cs;
-      uzm[c] = LD(X + rb - sxy, lo0);
-      uc[c]  = LD(X + rb, lo0);
-      uzp[c] = LD(X + rb + sxy, lo0);
-      if (ringlane) lds[k0 & 1].u[c][w + 1][lane == 0 ? 0 : 65] = LD(X + rb - 1, loring0);
-      if (botrow) lds[k0 & 1].u[c][0][lane + 1] = LD(X + rr, lo0);
-      if (toprow) lds[k0 & 1].u[c][MOM_RY + 1][lane + 1] = LD(X + rr, lo0);
-      if (DOT && o) oc[c] = LD(o + c * cs + rb, lo0);
-    }
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      vzl[f] = LD(fld(f, 2) + rb, lo0);
-      vzh[f] = LD(fld(f, 2) + rb + sxy, lo0);
-      fxl[f] = LD(fld(f, 0) + rb, lo0);
-      fyl[f] = LD(fld(f, 1) + rb, lo0);
-      if (lane == 63) lds[k0 & 1].fx[f][w][64] = LD(fld(f, 0) + rb - 1, loring0);
-      if (toprow) lds[k0 & 1].fy[f][MOM_RY][lane] = LD(fld(f, 1) + rr, lo0);
-    }
-  }
-  for (int kl = k0; kl < k1; ++kl) {
-    // Opaque copies of the plane index and the lane offsets: without them the loop optimiser turns every load stream
-    // into its own 64-bit per-lane pointer carried around the loop (dozens of VGPRs, no scalar-base addressing).
-    int      k = kl;
-    unsigned lo = lo0, loring = loring0;
-    asm volatile("" : "+s"(k), "+v"(lo), "+v"(loring));
-    MomLds       &L = lds[k & 1];
-    const int64_t rb = rb0 + (int64_t)k * sxy;
-    const bool    zwall = k == 0 || k == g.nz - 1;
-    // ---- 1: publish this thread's part of plane k (its ring went into this buffer at the end of the previous trip)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) L.u[c][w + 1][lane + 1] = uc[c];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      L.fx[f][w][lane] = fxl[f];
-      L.fy[f][w][lane] = fyl[f];
-    }
-    // far column of the one-sided wall rows (rare: uniform branches; straight from global memory, issued before the prefetches so that waiting for them does not drain those)
-    double ufx[3] = {0., 0., 0.}, ufy[3] = {0., 0., 0.}, ufz[3] = {0., 0., 0.};
-    if (xwall) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) ufx[c] = LD(x + c * cs + rb - 2, lo + far0);
-    }
-    if (ywall) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) ufy[c] = LD(x + c * cs + rb + foy, lo);
-    }
-    if (zwall) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) ufz[c] = LD(x + c * cs + rb + (k == 0 ? 2 : -2) * sxy, lo);
-    }
-    // ---- 2: loads of the next plane(s) (plane k+2 is clamped to the high ghost plane: never read past the array)
-    const int64_t rb1 = rb + sxy, rb2 = rb0 + (int64_t)min(k + 2, g.nz) * sxy, rr1 = rr0 + (int64_t)(k + 1) * sxy;
-    double        n_u[3], n_vz[4], n_fxl[4], n_fyl[4], n_oc[3] = {0., 0., 0.}, n_rcol_u[3], n_rcol_fx[4], n_rrow_u[3], n_rrow_fy[4];  // n_r*: ring of plane k+1
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double *X = x + c * cs;
-      n_u[c] = LD(X + rb2, lo);
-      if (DOT && o) n_oc[c] = LD(o + c * cs + rb1, lo);
-    }
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      n_vz[f]  = LD(fld(f, 2) + rb2, lo);
-      n_fxl[f] = LD(fld(f, 0) + rb1, lo);
-      n_fyl[f] = LD(fld(f, 1) + rb1, lo);
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double *X = x + c * cs;
-      n_rcol_u[c] = ringlane ? LD(X + rb1 - 1, loring) : 0.;
-      n_rrow_u[c] = (botrow || toprow) ? LD(X + rr1, lo) : 0.;
-    }
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      n_rcol_fx[f] = lane == 63 ? LD(fld(f, 0) + rb1 - 1, loring) : 0.;
-      n_rrow_fy[f] = toprow ? LD(fld(f, 1) + rr1, lo) : 0.;
-    }
-    __syncthreads();
-    // ---- 3: the three axes
-    double yacc[3] = {0., 0., 0.}, dacc[3] = {0., 0., 0.};
-    {
-      double um[3], up[3], fh[4];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        um[c] = L.u[c][w + 1][lane];
-        up[c] = L.u[c][w + 1][lane + 2];
-      }
-#pragma unroll
-      for (int f = 0; f < 4; ++f) fh[f] = L.fx[f][w][lane + 1];
-      if (xwall) {
-        auto T = [&](int q) { return ltabx[q][lane]; };
-        mom_axis<0, 0, true, DG>(T, um[0], uc[0], up[0], ufx[0], um[0], uc[0], up[0], fxl[0], fh[0], fxl[1], fh[1], cC, cL, yacc[0], dacc[0]);
-        mom_axis<0, 1, true, DG>(T, um[1], uc[1], up[1], ufx[1], um[0], uc[0], up[0], fxl[0], fh[0], fxl[2], fh[2], cC, cL, yacc[1], dacc[1]);
-        mom_axis<0, 2, true, DG>(T, um[2], uc[2], up[2], ufx[2], um[0], uc[0], up[0], fxl[0], fh[0], fxl[3], fh[3], cC, cL, yacc[2], dacc[2]);
-      } else {
-        auto T = [&](int q) { return txi[slot7(q)]; };
-        mom_axis<0, 0, false, DG>(T, um[0], uc[0], up[0], 0., um[0], uc[0], up[0], fxl[0], fh[0], fxl[1], fh[1], cC, cL, yacc[0], dacc[0]);
-        mom_axis<0, 1, false, DG>(T, um[1], uc[1], up[1], 0., um[0], uc[0], up[0], fxl[0], fh[0], fxl[2], fh[2], cC, cL, yacc[1], dacc[1]);
-        mom_axis<0, 2, false, DG>(T, um[2], uc[2], up[2], 0., um[0], uc[0], up[0], fxl[0], fh[0], fxl[3], fh[3], cC, cL, yacc[2], dacc[2]);
-      }
-    }
-    {
-      double um[3], up[3], fh[4];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        um[c] = L.u[c][w][lane + 1];
-        up[c] = L.u[c][w + 2][lane + 1];
-      }
-#pragma unroll
-      for (int f = 0; f < 4; ++f) fh[f] = L.fy[f][w + 1][lane];
-      if (ywall) {
-        auto T = [&](int q) { return taby[(int64_t)q * ly]; };
-        mom_axis<1, 0, true, DG>(T, um[0], uc[0], up[0], ufy[0], um[1], uc[1], up[1], fyl[0], fh[0], fyl[1], fh[1], cC, cL, yacc[0], dacc[0]);
-        mom_axis<1, 1, true, DG>(T, um[1], uc[1], up[1], ufy[1], um[1], uc[1], up[1], fyl[0], fh[0], fyl[2], fh[2], cC, cL, yacc[1], dacc[1]);
-        mom_axis<1, 2, true, DG>(T, um[2], uc[2], up[2], ufy[2], um[1], uc[1], up[1], fyl[0], fh[0], fyl[3], fh[3], cC, cL, yacc[2], dacc[2]);
-      } else {
-        auto T = [&](int q) { return tyi[slot7(q)]; };
-        mom_axis<1, 0, false, DG>(T, um[0], uc[0], up[0], 0., um[1], uc[1], up[1], fyl[0], fh[0], fyl[1], fh[1], cC, cL, yacc[0], dacc[0]);
-        mom_axis<1, 1, false, DG>(T, um[1], uc[1], up[1], 0., um[1], uc[1], up[1], fyl[0], fh[0], fyl[2], fh[2], cC, cL, yacc[1], dacc[1]);
-        mom_axis<1, 2, false, DG>(T, um[2], uc[2], up[2], 0., um[1], uc[1], up[1], fyl[0], fh[0], fyl[3], fh[3], cC, cL, yacc[2], dacc[2]);
-      }
-    }
-    {
-      const double *tabz = m.tab[2] + k;
-      auto          T = [&](int q) { return tabz[(int64_t)q * lz]; };
-      if (zwall) {
-        mom_axis<2, 0, true, DG>(T, uzm[0], uc[0], uzp[0], ufz[0], uzm[2], uc[2], uzp[2], vzl[0], vzh[0], vzl[1], vzh[1], cC, cL, yacc[0], dacc[0]);
-        mom_axis<2, 1, true, DG>(T, uzm[1], uc[1], uzp[1], ufz[1], uzm[2], uc[2], uzp[2], vzl[0], vzh[0], vzl[2], vzh[2], cC, cL, yacc[1], dacc[1]);
-        mom_axis<2, 2, true, DG>(T, uzm[2], uc[2], uzp[2], ufz[2], uzm[2], uc[2], uzp[2], vzl[0], vzh[0], vzl[3], vzh[3], cC, cL, yacc[2], dacc[2]);
-      } else {
-        mom_axis<2, 0, false, DG>(T, uzm[0], uc[0], uzp[0], 0., uzm[2], uc[2], uzp[2], vzl[0], vzh[0], vzl[1], vzh[1], cC, cL, yacc[0], dacc[0]);
-        mom_axis<2, 1, false, DG>(T, uzm[1], uc[1], uzp[1], 0., uzm[2], uc[2], uzp[2], vzl[0], vzh[0], vzl[2], vzh[2], cC, cL, yacc[1], dacc[1]);
-        mom_axis<2, 2, false, DG>(T, uzm[2], uc[2], uzp[2], 0., uzm[2], uc[2], uzp[2], vzl[0], vzh[0], vzl[3], vzh[3], cC, cL, yacc[2], dacc[2]);
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      double yv = m.cI * uc[c] + yacc[c];
-      if (DG) {
-        const double dg = m.cI + dacc[c];
-        if (OUT == 2) yv = dg;
-        else yv = yv * recip(dg);  // PCJacobi: VecReciprocal(diag) once, VecPointwiseMult per apply
-      }
-      if (own) {
-        if (OUT == 1) y[c * ncell + ((int64_t)k * g.ny + j) * g.nx + i] = yv;
-        else ST(y + c * cs + rb, lo, yv);
-        if (DOT) {
-          acc[0] += yv;
-          acc[1] += yv * oc[c];
-          acc[2] += uc[c] * yv;
-          acc[3] += yv * yv;
-        }
-      }
-    }
-    // ---- 4: rotate (this is where the loads of step 2 are waited for)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      uzm[c] = uc[c];
-      uc[c]  = uzp[c];
-      uzp[c] = n_u[c];
-      oc[c]  = n_oc[c];
-    }
-    // the ring of plane k+1 goes straight into the other LDS buffer: nobody reads that one before the next barrier
-    MomLds &Ln = lds[(k + 1) & 1];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      if (ringlane) Ln.u[c][w + 1][lane == 0 ? 0 : 65] = n_rcol_u[c];
-      if (botrow) Ln.u[c][0][lane + 1] = n_rrow_u[c];
-      if (toprow) Ln.u[c][MOM_RY + 1][lane + 1] = n_rrow_u[c];
-    }
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      vzl[f] = vzh[f];
-      vzh[f] = n_vz[f];
-      fxl[f] = n_fxl[f];
-      fyl[f] = n_fyl[f];
-      if (lane == 63) Ln.fx[f][w][64] = n_rcol_fx[f];
-      if (toprow) Ln.fy[f][MOM_RY][lane] = n_rrow_fy[f];
-    }
-  }
-  if (DOT) {
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const double v = wave_sum(acc[a]);
-      if (lane == 0) red[a * MOM_RY + w] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-      double v = 0.;
-#pragma unroll
-      for (int q = 0; q < MOM_RY; ++q) v += red[threadIdx.x * MOM_RY + q];
-      partial[(int64_t)threadIdx.x * pstride + blockIdx.x] = v;
-    }
-  }
-}
-#endif  // FL_KBENCH_VARIANTS
 
 }  // namespace fl
 #include "fl_stencil.h"
@@ -411,131 +53,11 @@ namespace fl {
 // OP 1: S = R - alpha V
 // OP 2: X += alpha P + omega S ; R = S - omega T          slots: 0 R.R  1 R.RP  2 sum R
 // OP 3: R = RP = b / diag (b unpadded, component-major)    slots: 0 sum R  1 R.R        (dg NULL: no preconditioner)
-#ifdef FL_KBENCH_VARIANTS  // round 1's vector updates (A/B runs)
-template <int OP>
-__global__ void __launch_bounds__(256) k_mom_pw(GridP g, int64_t cs, const double *__restrict__ a0, const double *__restrict__ a1, const double *__restrict__ a2, const double *__restrict__ a3, double *__restrict__ w0,
-                                                double *__restrict__ w1, const KspScal *__restrict__ s, double *__restrict__ partial, int pstride, int tiles_x, int nchunk, int zc)
-{
-  __shared__ double red[3 * 4];
-  if (OP != 3 && s->reason != 0) return;
-  const MTile   t = mom_tile(g, tiles_x, nchunk, zc);
-  const double  alpha = s->alpha, omega = s->omega, beta = s->beta, ob = s->omega_old * s->beta;
-  const int64_t ncell = (int64_t)g.nx * g.ny * g.nz;
-  double        acc[3] = {0., 0., 0.};
-  if (t.own)
-    for (int k = t.k0; k < t.k1; ++k) {
-      const int64_t idx = g.off0 + (int64_t)k * g.sxy + (int64_t)t.j * g.sx + t.i;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int64_t q = c * cs + idx;
-        if (OP == 0) {
-          w0[q] = a0[q] - ob * a1[q] + beta * w0[q];
-        } else if (OP == 1) {
-          w0[q] = a0[q] - alpha * a1[q];
-        } else if (OP == 2) {
-          const double S = a1[q];
-          const double rn = S - omega * a2[q];
-          w0[q] += alpha * a0[q] + omega * S;
-          w1[q] = rn;
-          acc[0] += rn * rn;
-          acc[1] += rn * a3[q];
-          acc[2] += rn;
-        } else {
-          const double b = a0[c * ncell + ((int64_t)k * g.ny + t.j) * g.nx + t.i];
-          const double r = a1 ? b / a1[q] : b;
-          w0[q] = r;
-          w1[q] = r;
-          acc[0] += r;
-          acc[1] += r * r;
-        }
-      }
-    }
-  if (OP == 2 || OP == 3) {
-    block_sum<3>(acc, red);
-    if (threadIdx.x == 0)
-#pragma unroll
-      for (int a = 0; a < 3; ++a) partial[(int64_t)a * pstride + blockIdx.x] = acc[a];
-  }
-}
-#endif  // FL_KBENCH_VARIANTS
-
-// The same four updates on 128-cell row segments, two x-adjacent cells per lane (16-byte accesses, non-temporal where a value is not read
-// again before it would be evicted anyway): one wave per segment, grid-stride over the segments of the block.  Padded rows start on
-// a 128-byte boundary (PADX), so every pair is 16-byte aligned; the unpadded b of OP 3 is read in pairs when nx is even (pairs != 0).
-#ifdef FL_KBENCH_VARIANTS  // round 2's vector updates (A/B runs)
-template <int OP>
-__global__ void __launch_bounds__(256) k_mom_pw2(GridP g, int64_t cs, const double *__restrict__ a0, const double *__restrict__ a1, const double *__restrict__ a2, const double *__restrict__ a3, double *__restrict__ w0,
-                                                 double *__restrict__ w1, const KspScal *__restrict__ s, double *__restrict__ partial, int pstride, int pairs)
-{
-  __shared__ double red[3 * 4];
-  if (OP != 3 && s->reason != 0) return;
-  const double  alpha = s->alpha, omega = s->omega, beta = s->beta, ob = s->omega_old * s->beta;
-  const int     lane = threadIdx.x & 63, nxs = (g.nx + 127) / 128;
-  const int64_t nseg = (int64_t)nxs * g.ny * g.nz, ncell = (int64_t)g.nx * g.ny * g.nz;
-  double        acc[3] = {0., 0., 0.};
-  for (int64_t seg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); seg < nseg; seg += (int64_t)gridDim.x * 4) {
-    const int     xs = (int)(seg % nxs);
-    const int64_t R  = seg / nxs;
-    const int     j = (int)(R % g.ny), k = (int)(R / g.ny), i = xs * 128 + 2 * lane;
-    if (i >= g.nx) continue;
-    const bool    two = i + 1 < g.nx;
-    const int64_t idx = g.off0 + (int64_t)k * g.sxy + (int64_t)j * g.sx + i, ub = ((int64_t)k * g.ny + j) * g.nx + i;
-    auto          ldp = [&](const double *p, int64_t q) { return two ? ld2<1>(p + q) : make_double2(p[q], 0.); };
-    auto          ldk = [&](const double *p, int64_t q) { return two ? ld2<0>(p + q) : make_double2(p[q], 0.); };  // read again soon: keep it cached
-    auto          stp = [&](double *p, int64_t q, double2 v) {
-      if (two) st2<0>(p + q, v);
-      else p[q] = v.x;
-    };
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int64_t q = c * cs + idx;
-      if (OP == 0) {
-        const double2 r = ldk(a0, q), v = ldp(a1, q), p = ldp(w0, q);
-        stp(w0, q, make_double2(r.x - ob * v.x + beta * p.x, r.y - ob * v.y + beta * p.y));
-      } else if (OP == 1) {
-        const double2 r = ldp(a0, q), v = ldp(a1, q);
-        stp(w0, q, make_double2(r.x - alpha * v.x, r.y - alpha * v.y));
-      } else if (OP == 2) {
-        const double2 P = ldp(a0, q), S = ldp(a1, q), T = ldp(a2, q), RP = ldk(a3, q), X = ldp(w0, q);
-        const double2 rn = make_double2(S.x - omega * T.x, S.y - omega * T.y);
-        double2       xn = X;
-        xn.x += alpha * P.x + omega * S.x;
-        xn.y += alpha * P.y + omega * S.y;
-        if (two) st2<1>(w0 + q, xn);
-        else w0[q] = xn.x;
-        stp(w1, q, rn);
-        acc[0] += rn.x * rn.x + (two ? rn.y * rn.y : 0.);
-        acc[1] += rn.x * RP.x + (two ? rn.y * RP.y : 0.);
-        acc[2] += rn.x + (two ? rn.y : 0.);
-      } else {
-        const int64_t u = c * ncell + ub;
-        double2       b;
-        if (two && pairs) b = ld2<1>(a0 + u);
-        else b = make_double2(a0[u], two ? a0[u + 1] : 0.);
-        double2 r = b;
-        if (a1) {
-          const double2 d = ldp(a1, q);
-          r.x = b.x / d.x;
-          if (two) r.y = b.y / d.y;
-        }
-        stp(w0, q, r);
-        stp(w1, q, r);
-        acc[0] += r.x + (two ? r.y : 0.);
-        acc[1] += r.x * r.x + (two ? r.y * r.y : 0.);
-      }
-    }
-  }
-  if (OP == 2 || OP == 3) {
-    block_sum<3>(acc, red);
-    if (threadIdx.x == 0)
-#pragma unroll
-      for (int a = 0; a < 3; ++a) partial[(int64_t)a * pstride + blockIdx.x] = acc[a];
-  }
-}
-#endif  // FL_KBENCH_VARIANTS
-
-// The tile walk of k_mom2 for the vector updates (experiment FLUCA_MOM_PW=3): a block marches a 128 x 8 tile through a z chunk, blocks in
-// the XCD-contiguous order -- the access pattern at which the stencil kernels move 6 TB/s where the grid-stride form above moves 5.3.
+//
+// The tile walk of k_mom2: a block marches a 128 x 8 tile through a z chunk, two x-adjacent cells per lane (16-byte accesses, non-temporal
+// where a value is not read again before it would be evicted anyway), blocks in the XCD-contiguous order -- the access pattern at which the
+// stencil kernels move 6 TB/s where a grid-stride walk over row segments moved 5.3.  Padded rows start on a 128-byte boundary (PADX), so every
+// pair is 16-byte aligned; the unpadded b of OP 3 is read in pairs when nx is even (pairs != 0).
 template <int OP>
 __global__ void __launch_bounds__(512) k_mom_pw3(GridP g, int64_t cs, const double *__restrict__ a0, const double *__restrict__ a1, const double *__restrict__ a2, const double *__restrict__ a3, double *__restrict__ w0,
                                                  double *__restrict__ w1, const KspScal *__restrict__ s, double *__restrict__ partial, int pstride, int pairs, int tiles_x, int nchunk, int zc)
@@ -850,10 +372,7 @@ struct fl_momentum {
   bool        have_state = false;
   double      dmean = 1.;   // mean_i a_ii, formed with gersh
   double      gersh = -1.;  // cached Gershgorin radius of the Jacobi-scaled operator (fl_momentum_gershgorin); < 0: not computed for this state
-  int         tiles_x = 1, tiles_y = 1, nchunk = 1, zc = 1, nblocks = 1;  // 64 x 4 x zc tiles of the vector-update kernels
-  int         anchunk = 1, azc = 1, ablocks = 1;                        // 64 x MOM_RY x azc tiles of k_mom_apply
-  int         t2x = 1, t2chunk = 1, t2zc = 1, t2blocks = 1;             // 128 x 8 x t2zc tiles of k_mom2
-  int         pw2blocks = 1;                                            // k_mom_pw2: grid-stride over 128-cell row segments
+  int         t2x = 1, t2chunk = 1, t2zc = 1, t2blocks = 1;  // 128 x 8 x t2zc tiles of k_mom2 / k_mom3 / k_mom_pw3 (mom_plan); t2blocks = entries of their partial sums
 };
 
 namespace {
@@ -877,44 +396,27 @@ int mom_ghosts(fl_momentum *m, double *v3)
   return 0;
 }
 
-int mom_order()
-{
-  // 1 (shipped): chunk-major, XCD-contiguous; 0: chunk fastest (round 1's order); three alternating rounds at 512^3: apply 5.83 against 6.03 ms
-  // (profiles/r02c_mom_order.txt)
-  return FL_VARIANT(mom_order, 1);
-}
+// block order of the tile walks (flags bit 0): chunk-major, XCD-contiguous; three alternating rounds at 512^3 against chunk-fastest: apply 5.83
+// against 6.03 ms (profiles/r02c_mom_order.txt)
+constexpr int MOM_XCD_ORDER = 1;
 
-int mom_kernel()
-{
-  // 3 (shipped): k_mom3 (v0interp formed in the kernel) when the state came with v0 (fl_momentum_set_state_v0), else k_mom2;
-  // 2: always k_mom2, two cells per lane on 128 x 8 tiles, all twelve face fields read; 1: round 1/2's k_mom_apply (kbench build)
-  return FL_VARIANT(mom_kernel, 3);
-}
-int mom_nt()
-{
-  return FL_VARIANT(mom_nt, 1);  // non-temporal stores of k_mom2
-}
+// k_mom3 (v0interp of the inner faces formed in the kernel) runs when the state came with v0 (fl_momentum_set_state_v0) and ny > 8: no 128 x 8
+// tile then holds both ends of the y axis (k_mom3 stages one block-end row); else k_mom2, all twelve face fields read
+bool mom3_grid(const GridP &g) { return g.ny > 8; }
 
-// DOT: 0 no inner products, 1 sum y and y.o (slots 0, 1), 2 x.y and y.y (slots 2, 3), 3 all four (k_mom_apply always forms all four)
+// DOT: 0 no inner products, 1 sum y and y.o (slots 0, 1), 2 x.y and y.y (slots 2, 3), 3 all four
 template <int DOT, bool JAC, int OUT>
 void mom_apply_t(fl_momentum *m, const double *x, double *y, const double *o, const KspScal *s, const MomP *coeffs = nullptr)
 {
   fl_poisson *h = m->p;
-  if (mom_kernel() >= 2) {
-    int flags = mom_order() & 1;
-    if (OUT == 1 && (h->g.nx & 1) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) flags |= 2;
-    if (mom_kernel() >= 3 && m->fly && h->g.ny > 8) {  // ny > 8: no 128 x 8 tile holds both ends of the y axis (k_mom3 stages one block-end row)
-      hipLaunchKernelGGL((k_mom3<8, DOT, JAC, OUT, 1>), dim3(m->t2blocks), dim3(512), 0, h->stream, h->g, coeffs ? *coeffs : m->mp, x, y, m->F, (const double *)m->v0p, (int64_t)h->padlen, o, s, h->partial,
-                         h->partial_stride, m->t2x, m->t2chunk, m->t2zc, flags);
-      return;
-    }
-    if (mom_nt()) hipLaunchKernelGGL((k_mom2<8, DOT, JAC, OUT, 1>), dim3(m->t2blocks), dim3(512), 0, h->stream, h->g, coeffs ? *coeffs : m->mp, x, y, m->F, (int64_t)h->padlen, o, s, h->partial, h->partial_stride, m->t2x, m->t2chunk, m->t2zc, flags);
-    else hipLaunchKernelGGL((k_mom2<8, DOT, JAC, OUT, 0>), dim3(m->t2blocks), dim3(512), 0, h->stream, h->g, coeffs ? *coeffs : m->mp, x, y, m->F, (int64_t)h->padlen, o, s, h->partial, h->partial_stride, m->t2x, m->t2chunk, m->t2zc, flags);
-    return;
-  }
-#ifdef FL_KBENCH_VARIANTS
-  hipLaunchKernelGGL((k_mom_apply<(DOT != 0), JAC, OUT>), dim3(m->ablocks), dim3(MOM_NT), 0, h->stream, h->g, coeffs ? *coeffs : m->mp, x, y, m->F, (int64_t)h->padlen, o, s, h->partial, h->partial_stride, m->tiles_x, m->anchunk, m->azc, mom_order());
-#endif
+  int         flags = MOM_XCD_ORDER;
+  if (OUT == 1 && (h->g.nx & 1) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) flags |= 2;
+  if (m->fly && mom3_grid(h->g))
+    hipLaunchKernelGGL((k_mom3<8, DOT, JAC, OUT, 1>), dim3(m->t2blocks), dim3(512), 0, h->stream, h->g, coeffs ? *coeffs : m->mp, x, y, m->F, (const double *)m->v0p, (int64_t)h->padlen, o, s, h->partial,
+                       h->partial_stride, m->t2x, m->t2chunk, m->t2zc, flags);
+  else
+    hipLaunchKernelGGL((k_mom2<8, DOT, JAC, OUT, 1>), dim3(m->t2blocks), dim3(512), 0, h->stream, h->g, coeffs ? *coeffs : m->mp, x, y, m->F, (int64_t)h->padlen, o, s, h->partial, h->partial_stride, m->t2x, m->t2chunk,
+                       m->t2zc, flags);
 }
 // the scaled, cell-major tables of k_mom2 for the coefficients in p (stream-ordered; slot 0: the handle's own, slot 1: a one-off operator)
 int mom_scale_tables(fl_momentum *m, int slot, MomP &p)
@@ -929,34 +431,34 @@ int mom_scale_tables(fl_momentum *m, int slot, MomP &p)
   return 0;
 }
 
-// blocks whose partial sums a DOT launch of the momentum operator leaves behind
-int mom_apply_blocks(const fl_momentum *m) { return mom_kernel() >= 2 ? m->t2blocks : m->ablocks; }
-
-int mom_pw_kernel()
-{
-  return FL_VARIANT(mom_pw, 3);  // 3 (shipped): k_mom_pw3, the tile walk; 2: k_mom_pw2, 16-byte row segments; 1: round 1's k_mom_pw (kbench build)
-}
-// blocks of the vector-update kernels = entries of their partial sums
-int mom_pw_blocks(const fl_momentum *m) { return mom_pw_kernel() >= 3 ? m->t2blocks : (mom_pw_kernel() == 2 ? m->pw2blocks : m->nblocks); }
-
 template <int OP>
 void mom_pw(fl_momentum *m, const double *a0, const double *a1, const double *a2, const double *a3, double *w0, double *w1)
 {
   fl_poisson *h = m->p;
-  if (mom_pw_kernel() >= 3) {
-    const int pairs = (h->g.nx & 1) == 0 && (reinterpret_cast<uintptr_t>(a0) & 15) == 0;
-    hipLaunchKernelGGL((k_mom_pw3<OP>), dim3(m->t2blocks), dim3(512), 0, h->stream, h->g, (int64_t)h->padlen, a0, a1, a2, a3, w0, w1, h->scal, h->partial, h->partial_stride, pairs, m->t2x, m->t2chunk, m->t2zc);
-    return;
-  }
-#ifdef FL_KBENCH_VARIANTS
-  if (mom_pw_kernel() >= 2) {
-    const int pairs = (h->g.nx & 1) == 0 && (reinterpret_cast<uintptr_t>(a0) & 15) == 0;
-    hipLaunchKernelGGL((k_mom_pw2<OP>), dim3(m->pw2blocks), dim3(256), 0, h->stream, h->g, (int64_t)h->padlen, a0, a1, a2, a3, w0, w1, h->scal, h->partial, h->partial_stride, pairs);
-    return;
-  }
-  hipLaunchKernelGGL((k_mom_pw<OP>), dim3(m->nblocks), dim3(256), 0, h->stream, h->g, (int64_t)h->padlen, a0, a1, a2, a3, w0, w1, h->scal, h->partial, h->partial_stride, m->tiles_x, m->nchunk, m->zc);
-#endif
+  const int   pairs = (h->g.nx & 1) == 0 && (reinterpret_cast<uintptr_t>(a0) & 15) == 0;
+  hipLaunchKernelGGL((k_mom_pw3<OP>), dim3(m->t2blocks), dim3(512), 0, h->stream, h->g, (int64_t)h->padlen, a0, a1, a2, a3, w0, w1, h->scal, h->partial, h->partial_stride, pairs, m->t2x, m->t2chunk, m->t2zc);
 }
+
+}  // namespace
+
+// k_mom2 / k_mom3 / k_mom_pw3: 128 x 8 tiles; about four blocks per CU in all (one is resident at a time: 158 KB of LDS) -- 512^3: 3.35 ms with
+// 4 z chunks, 3.59 with 2, 3.50 with 8 (profiles/r03_mom_plan.txt); fewer, taller chunks where the partial-sum buffers (MAX_PARTIAL_BLOCKS
+// entries per slot) would not hold a block each
+MomPlan fl::mom_plan(const GridP &g)
+{
+  MomPlan p;
+  p.t2x           = (g.nx + 127) / 128;
+  const int tiles = p.t2x * ((g.ny + 7) / 8);
+  int       nc    = z_chunk_count(tiles, g.nz, 1024);
+  if (tiles * nc > MAX_PARTIAL_BLOCKS) nc = std::max(1, MAX_PARTIAL_BLOCKS / tiles);
+  const ZChunks z = z_chunks(g.nz, nc);
+  p.t2zc     = z.zc;
+  p.t2chunk  = z.nchunk;
+  p.t2blocks = tiles * p.t2chunk;
+  return p;
+}
+
+namespace {
 
 int mom_init(fl_momentum *m, fl_poisson *h)
 {
@@ -1015,54 +517,13 @@ int mom_init(fl_momentum *m, fl_poisson *h)
   m->mp.cI = 1.;
   m->mp.cC = 0.;
   m->mp.cL = 0.;
-  m->tiles_x = (g.nx + 63) / 64;
-  m->tiles_y = (g.ny + 3) / 4;
-  const int tiles = m->tiles_x * m->tiles_y;
-  int       nchunk = std::max(1, (2048 + tiles / 2) / tiles);
-  nchunk     = std::max(1, std::min(std::min(nchunk, std::max(1, g.nz / 8)), g.nz));
-  m->zc      = (g.nz + nchunk - 1) / nchunk;
-  m->nchunk  = (g.nz + m->zc - 1) / m->zc;
-  m->nblocks = tiles * m->nchunk;
-  if (m->nblocks > MAX_PARTIAL_BLOCKS) {
-    // fewer, taller chunks: the partial-sum buffers hold MAX_PARTIAL_BLOCKS entries per slot
-    m->nchunk  = std::max(1, MAX_PARTIAL_BLOCKS / tiles);
-    m->zc      = (g.nz + m->nchunk - 1) / m->nchunk;
-    m->nchunk  = (g.nz + m->zc - 1) / m->zc;
-    m->nblocks = tiles * m->nchunk;
-    if (m->nblocks > MAX_PARTIAL_BLOCKS) return FL_ERR_SUP;
-  }
-  {
-    const int atiles = m->tiles_x * ((g.ny + MOM_RY - 1) / MOM_RY);
-    int       nc = std::max(1, (2048 + atiles / 2) / atiles);
-    nc         = std::max(1, std::min(std::min(nc, std::max(1, g.nz / 8)), g.nz));
-    if (FL_VARIANT(mom_chunks, 0) > 0) nc = std::min(FL_VARIANT(mom_chunks, 0), g.nz);  // experiments: z chunks of k_mom_apply
-    if (atiles * nc > MAX_PARTIAL_BLOCKS) nc = std::max(1, MAX_PARTIAL_BLOCKS / atiles);
-    m->azc     = (g.nz + nc - 1) / nc;
-    m->anchunk = (g.nz + m->azc - 1) / m->azc;
-    m->ablocks = atiles * m->anchunk;
-    if (m->ablocks > MAX_PARTIAL_BLOCKS) return FL_ERR_SUP;
-  }
-  {
-    // k_mom2: 128 x 8 tiles; about four blocks per CU in all (one is resident at a time: 158 KB of LDS) -- 512^3: 3.35 ms with 4 z chunks,
-    // 3.59 with 2, 3.50 with 8 (profiles/r03_mom_plan.txt)
-    m->t2x          = (g.nx + 127) / 128;
-    const int tiles = m->t2x * ((g.ny + 7) / 8);
-    int       nc    = std::max(1, (1024 + tiles / 2) / tiles);
-    nc              = std::max(1, std::min(std::min(nc, std::max(1, g.nz / 8)), g.nz));
-    if (FL_VARIANT(mom_chunks, 0) > 0) nc = std::min(FL_VARIANT(mom_chunks, 0), g.nz);
-    if (tiles * nc > MAX_PARTIAL_BLOCKS) nc = std::max(1, MAX_PARTIAL_BLOCKS / tiles);
-    m->t2zc     = (g.nz + nc - 1) / nc;
-    m->t2chunk  = (g.nz + m->t2zc - 1) / m->t2zc;
-    m->t2blocks = tiles * m->t2chunk;
-    if (m->t2blocks > MAX_PARTIAL_BLOCKS) return FL_ERR_SUP;
-  }
-  {
-    const int64_t nseg = (int64_t)((g.nx + 127) / 128) * g.ny * g.nz;
-    int           nb   = 2048;  // 8 blocks of 4 waves per CU
-    if (FL_VARIANT(mom_pw_blocks, 0) > 0) nb = FL_VARIANT(mom_pw_blocks, 0);
-    m->pw2blocks = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((nseg + 3) / 4, nb), MAX_PARTIAL_BLOCKS));
-  }
-  FL_CHK(fl_ensure_partials(h, std::max(std::max(m->nblocks, m->ablocks), m->t2blocks)));
+  const MomPlan pl = mom_plan(g);
+  if (pl.t2blocks > MAX_PARTIAL_BLOCKS) return FL_ERR_SUP;
+  m->t2x      = pl.t2x;
+  m->t2chunk  = pl.t2chunk;
+  m->t2zc     = pl.t2zc;
+  m->t2blocks = pl.t2blocks;
+  FL_CHK(fl_ensure_partials(h, m->t2blocks));
   FL_CHK(fl_dev_alloc(h, (void **)&m->F, sizeof(double) * 12 * h->padlen, true));
   FL_CHK(fl_dev_alloc(h, (void **)&m->dg, sizeof(double) * 3 * h->padlen, true));
   return fl_momentum_set_coefficients(m, 1., 0., 0.);  // A = I until the first set_state (also fills diag(A))
@@ -1151,8 +612,8 @@ int mom_set_state(fl_momentum *m, double dt, double rho, double mu, const double
   }
   const int ext[3][3] = {{g.fx, g.ny, g.nz}, {g.nx, g.fy, g.nz}, {g.nx, g.ny, g.fz}};
   // with v0 handed over and k_mom3 certain to run (see mom_apply_t), the inner faces of the nine stored v0interp fields are never read: only their
-  // block-end faces are copied (FLUCA_MOM_KERNEL=2 and grids with ny <= 8 read the whole fields through k_mom2 and get whole copies)
-  const bool ends_only = v0_dev && mom_kernel() >= 3 && g.ny > 8;
+  // block-end faces are copied (grids with ny <= 8 read the whole fields through k_mom2 and get whole copies)
+  const bool ends_only = v0_dev && mom3_grid(g);
   for (int f = 0; f < 12; ++f) {
     const int     d = f < 3 ? f : (f - 3) % 3;
     const double *src = f < 3 ? V0_dev[f] : v0interp_dev[f - 3];
@@ -1249,7 +710,6 @@ extern "C" int fl_momentum_gershgorin(fl_momentum *m, double *radius)
 {
   if (!m || !radius) return FL_ERR_ARG_NULL;
   if (!m->have_state && m->mp.cC != 0.) return FL_ERR_ARG_WRONGSTATE;
-  if (mom_kernel() < 2) return FL_ERR_SUP;
   fl_poisson *h = m->p;
   FL_HIP(hipSetDevice(h->device));
   if (m->gersh < 0.) {
@@ -1295,7 +755,6 @@ static int momentum_cheb(fl_momentum *m, const double *b_dev, double *x_dev, con
   if (opts->pc != FL_PC_JACOBI && opts->pc != FL_PC_NONE) return FL_ERR_SUP;
   if (opts->norm_type == FL_NORM_NATURAL) return FL_ERR_SUP;
   if (opts->maxit < 0) return FL_ERR_ARG_OUTOFRANGE;
-  if (mom_kernel() < 2 || mom_pw_kernel() < 3) return FL_ERR_SUP;
   fl_poisson *h = m->p;
   FL_HIP(hipSetDevice(h->device));
   std::memset(stats, 0, sizeof(*stats));
@@ -1308,13 +767,13 @@ static int momentum_cheb(fl_momentum *m, const double *b_dev, double *x_dev, con
     default_interval = true;
   }
   if (!(emax > emin) || !(emin > 0.)) return FL_ERR_ARG_OUTOFRANGE;
-  const bool fused = mom_kernel() >= 3 && m->fly && h->g.ny > 8;
+  const bool fused = m->fly && mom3_grid(h->g);
   for (int a : {0, 2, 4}) FL_CHK(mom_vec(m, a));
   if (!fused) FL_CHK(mom_vec(m, 3));
   double *B = m->vec[0], *X0 = m->vec[4], *X1 = m->vec[2], *AX = m->vec[3];
   const int nhist = opts->maxit + 2;
   FL_CHK(fl_ensure_hist(h, nhist));
-  FL_CHK(fl_ensure_partials(h, std::max(std::max(m->nblocks, m->ablocks), m->t2blocks)));
+  FL_CHK(fl_ensure_partials(h, m->t2blocks));
   fl_ksp_opts o = *opts;
   o.remove_nullspace = 0;  // A = I + ... is non-singular
   const bool watched = default_interval && o.norm_type == FL_NORM_NONE;
@@ -1334,7 +793,7 @@ static int momentum_cheb(fl_momentum *m, const double *b_dev, double *x_dev, con
   const int total = o.norm_type == FL_NORM_NONE ? o.maxit : o.maxit + 1;  // with a norm, launch maxit is only the final test
   int       j = 0, hostcur = 0;
   bool      done = total <= 0;
-  int       flags = mom_order() & 1;
+  const int flags = MOM_XCD_ORDER;
   while (!done) {
     const int stop = std::min(total, j + every);
     for (; j < stop; ++j) {
@@ -1349,7 +808,7 @@ static int momentum_cheb(fl_momentum *m, const double *b_dev, double *x_dev, con
       } else {
         mom_apply_t<0, false, 0>(m, xin, AX, nullptr, h->scal);
         mom_pw<6>(m, xin, AX, B, jac ? m->dg : nullptr, xout, nullptr);
-        FL_CHK(fl_cheb_fin_step(h, mom_pw_blocks(m), nhist));
+        FL_CHK(fl_cheb_fin_step(h, m->t2blocks, nhist));
       }
       hostcur ^= 1;
     }
@@ -1386,9 +845,9 @@ static int momentum_solve_from_guess(fl_momentum *m, const double *b_dev, double
   // its square sum in one pass (slot 1); its two outputs are scratch here
   const bool scaled = opts->pc == FL_PC_JACOBI && opts->norm_type != FL_NORM_UNPRECONDITIONED;
   for (int a = 0; a < 2; ++a) FL_CHK(mom_vec(m, a));
-  FL_CHK(fl_ensure_partials(h, std::max(std::max(m->nblocks, m->ablocks), m->t2blocks)));
+  FL_CHK(fl_ensure_partials(h, m->t2blocks));
   mom_pw<3>(m, b_dev, scaled ? m->dg : nullptr, nullptr, nullptr, m->vec[0], m->vec[1]);
-  launch_reduce(h->stream, h->partial, mom_pw_blocks(m), h->partial_stride, 3, h->sums);
+  launch_reduce(h->stream, h->partial, m->t2blocks, h->partial_stride, 3, h->sums);
   if (h->multi) FL_CHK(h->comm.allreduce(h->stream, h->sums, NSLOT));
   double sums[NSLOT];
   FL_HIP(hipMemcpyAsync(sums, h->sums, sizeof(sums), hipMemcpyDeviceToHost, h->stream));
@@ -1440,43 +899,40 @@ extern "C" int fl_momentum_solve(fl_momentum *m, const double *b_dev, double *x_
   double *R = m->vec[0], *RP = m->vec[1], *P = m->vec[2], *V = m->vec[3], *X = m->vec[4], *S = m->vec[5], *T = m->vec[6];
   const int nhist = opts->maxit + 1;
   FL_CHK(fl_ensure_hist(h, nhist));
-  FL_CHK(fl_ensure_partials(h, std::max(std::max(m->nblocks, m->ablocks), m->t2blocks)));
+  FL_CHK(fl_ensure_partials(h, m->t2blocks));
   fl_ksp_opts o = *opts;
   o.remove_nullspace = 0;  // A = I + ... is non-singular
   FL_CHK(fl_ksp_begin(h, &o));
-  // P, V and X start as zero vectors: with the tile-walk updates the first iteration says so in its kernels (P = R; X is written, not read) and
-  // nothing is zeroed -- three 3N memsets and the reads of them less per solve; the older update kernels (FLUCA_MOM_PW < 3) keep the memsets
-  const bool   lazy0 = mom_pw_kernel() >= 3;
+  // P, V and X start as zero vectors: the first iteration says so in its kernels (P = R; X is written, not read) and nothing is zeroed -- three
+  // 3N memsets and the reads of them less per solve
   const size_t bytes = sizeof(double) * 3 * h->padlen;
-  if (!lazy0)
-    for (double *v : {P, V, X}) FL_HIP(hipMemsetAsync(v, 0, bytes, h->stream));
   mom_pw<3>(m, b_dev, jac ? m->dg : nullptr, nullptr, nullptr, R, RP);
-  FL_CHK(fl_bcgs_fin_step(h, 0, mom_pw_blocks(m), 3, nhist));
+  FL_CHK(fl_bcgs_fin_step(h, 0, m->t2blocks, 3, nhist));
   const int every = o.check_every > 0 ? o.check_every : 4;
   int       it = 0;
   bool      done = false;
   while (!done) {
     const int stop = std::min(o.maxit, it + every);
     for (; it < stop; ++it) {
-      if (lazy0 && it == 0) mom_pw<4>(m, R, nullptr, nullptr, nullptr, P, nullptr);
+      if (it == 0) mom_pw<4>(m, R, nullptr, nullptr, nullptr, P, nullptr);
       else mom_pw<0>(m, R, V, nullptr, nullptr, P, nullptr);
       FL_CHK(mom_ghosts(m, P));
       if (jac) mom_apply_t<1, true, 0>(m, P, V, RP, h->scal);
       else mom_apply_t<1, false, 0>(m, P, V, RP, h->scal);
-      FL_CHK(fl_bcgs_fin_step(h, 1, mom_apply_blocks(m), 4, nhist));
+      FL_CHK(fl_bcgs_fin_step(h, 1, m->t2blocks, 4, nhist));
       mom_pw<1>(m, R, V, nullptr, nullptr, S, nullptr);
       FL_CHK(mom_ghosts(m, S));
       if (jac) mom_apply_t<2, true, 0>(m, S, T, nullptr, h->scal);
       else mom_apply_t<2, false, 0>(m, S, T, nullptr, h->scal);
-      FL_CHK(fl_bcgs_fin_step(h, 3, mom_apply_blocks(m), 4, nhist));
-      if (lazy0 && it == 0) mom_pw<5>(m, P, S, T, RP, X, R);
+      FL_CHK(fl_bcgs_fin_step(h, 3, m->t2blocks, 4, nhist));
+      if (it == 0) mom_pw<5>(m, P, S, T, RP, X, R);
       else mom_pw<2>(m, P, S, T, RP, X, R);
-      FL_CHK(fl_bcgs_fin_step(h, 4, mom_pw_blocks(m), 3, nhist));
+      FL_CHK(fl_bcgs_fin_step(h, 4, m->t2blocks, 3, nhist));
     }
     FL_CHK(fl_poll_scal(h));
     if (h->scal_host->reason != 0 || it >= o.maxit) done = true;
   }
-  if (lazy0 && h->scal_host->it == 0) FL_HIP(hipMemsetAsync(X, 0, bytes, h->stream));  // stopped before the first update wrote X: the answer is the zero guess
+  if (h->scal_host->it == 0) FL_HIP(hipMemsetAsync(X, 0, bytes, h->stream));  // stopped before the first update wrote X: the answer is the zero guess
   for (int c = 0; c < 3; ++c) launch_unpad_copy(h->stream, h->g, X + (size_t)c * h->padlen, x_dev + (size_t)c * h->ncell, nullptr);
   return fl_ksp_finish(h, &o, stats);
 }
@@ -1571,8 +1027,8 @@ extern "C" int fl_momentum_interp_faces_ends(fl_momentum *m, const double *v_dev
   if (!m || !v_dev || !out_dev) return FL_ERR_ARG_NULL;
   fl_poisson *h = m->p;
   const GridP &g = h->g;
-  // where the operator will read whole fields (k_mom2: FLUCA_MOM_KERNEL=2, or a block with ny <= 8) the whole fields are what is needed
-  if (!(mom_kernel() >= 3 && g.ny > 8)) return fl_momentum_interp_faces(m, v_dev, vbc_dev, out_dev);
+  // where the operator will read whole fields (k_mom2: a block with ny <= 8) the whole fields are what is needed
+  if (!mom3_grid(g)) return fl_momentum_interp_faces(m, v_dev, vbc_dev, out_dev);
   FL_HIP(hipSetDevice(h->device));
   FL_CHK(mom_vec(m, 7));
   for (int c = 0; c < 3; ++c) launch_pad_copy(h->stream, h->g, v_dev + (size_t)c * h->ncell, m->vec[7] + (size_t)c * h->padlen);
@@ -1950,48 +1406,6 @@ extern "C" int fl_vec_maxpy(fl_poisson *h, int64_t n, double *x_dev, const doubl
 
 // ------------------------------------------------------------------------------------------------ diagnostics
 // Streaming ceiling of the access mix of k_mom_apply: 15 read streams + 3 write streams, flat, 16 B per lane.
-#ifdef FL_KBENCH_VARIANTS  // flat streaming probe with the product's read / write mix (tools/mom_bench.py)
-namespace fl {
-__global__ void __launch_bounds__(256) k_mom_stream(const double *__restrict__ F, const double *__restrict__ x, double *__restrict__ y, int64_t cs, int64_t n2)
-{
-  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n2; q += (int64_t)gridDim.x * blockDim.x) {
-    double2 a[3] = {{0., 0.}, {0., 0.}, {0., 0.}};
-#pragma unroll
-    for (int f = 0; f < 12; ++f) {
-      const double2 v = reinterpret_cast<const double2 *>(F + f * cs)[q];
-      a[f % 3].x += v.x;
-      a[f % 3].y += v.y;
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double2 v = reinterpret_cast<const double2 *>(x + c * cs)[q];
-      a[c].x += v.x;
-      a[c].y += v.y;
-      reinterpret_cast<double2 *>(y + c * cs)[q] = a[c];
-    }
-  }
-}
-}  // namespace fl
-
-extern "C" int fldbg_mom_stream(fl_momentum *m, int reps, int blocks, double *ms_out)
-{
-  fl_poisson *h = m->p;
-  FL_HIP(hipSetDevice(h->device));
-  FL_CHK(mom_vec(m, 6));
-  FL_CHK(mom_vec(m, 7));
-  const int64_t n2 = (int64_t)(h->padlen / 2);
-  auto go = [&]() { hipLaunchKernelGGL(k_mom_stream, dim3(blocks), dim3(256), 0, h->stream, m->F, m->vec[7], m->vec[6], (int64_t)h->padlen, n2); };
-  go();
-  FL_HIP(hipEventRecord(h->ev0, h->stream));
-  for (int r = 0; r < reps; ++r) go();
-  FL_HIP(hipEventRecord(h->ev1, h->stream));
-  FL_HIP(hipStreamSynchronize(h->stream));
-  float ms = 0.f;
-  FL_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  *ms_out = ms / reps;
-  return 0;
-}
-#endif  // FL_KBENCH_VARIANTS
 
 // the operator kernel alone on padded work vectors (no pad / unpad copies): mode 0 plain, 1 Jacobi, 2 Jacobi + y.o (the first product of a
 // BiCGStab iteration), 3 Jacobi + x.y, y.y (the second)

@@ -159,10 +159,8 @@ __device__ __forceinline__ double sv_axis(const SvRows &R, const double *__restr
 }
 
 // y (unpadded) = S p.  Grid: a multiple of 8 blocks; block b works for XCD b % 8 on the y band of that XCD.
-#ifndef FL_SV_MINBLOCKS
-#define FL_SV_MINBLOCKS 4   // four blocks per CU: 128 blocks per XCD are resident and cover exactly one plane of the XCD's band per loop trip
-#endif
-__global__ void __launch_bounds__(256, FL_SV_MINBLOCKS) k_schur_var(SvGrid g, int per, const double *__restrict__ p, const double *__restrict__ ainv, double *__restrict__ y)
+constexpr int SV_MINBLOCKS = 4;  // four blocks per CU: 128 blocks per XCD are resident and cover exactly one plane of the XCD's band per loop trip
+__global__ void __launch_bounds__(256, SV_MINBLOCKS) k_schur_var(SvGrid g, int per, const double *__restrict__ p, const double *__restrict__ ainv, double *__restrict__ y)
 {
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
   const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, nlb = gridDim.x >> 3;
@@ -235,7 +233,7 @@ struct SvRing {
 };
 
 // k_schur_var on one rank's block of several; nb: bit 2 d / 2 d + 1 = a neighbouring rank behind the low / high end of axis d
-__global__ void __launch_bounds__(256, FL_SV_MINBLOCKS) k_schur_var_ring(SvGrid g, SvRing rg, int per, int nb, const double *__restrict__ p, const double *__restrict__ ainv,
+__global__ void __launch_bounds__(256, SV_MINBLOCKS) k_schur_var_ring(SvGrid g, SvRing rg, int per, int nb, const double *__restrict__ p, const double *__restrict__ ainv,
                                                                           double *__restrict__ y)
 {
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
@@ -282,9 +280,7 @@ __global__ void __launch_bounds__(256) k_sv_ring_pack(int nx, int ny, int nz, in
 using namespace fl;
 
 // The launch of either sweep: the XCD band plan of the (rank's) block.
-#ifndef FL_SV_BLOCKS_PER_XCD
-#define FL_SV_BLOCKS_PER_XCD 128
-#endif
+constexpr int SV_BLOCKS_PER_XCD = 128;
 SchurVarPlan schur_var_plan(const GridP &g)
 {
   SchurVarPlan pl;
@@ -295,7 +291,7 @@ SchurVarPlan schur_var_plan(const GridP &g)
   // it again alone, when the planes its neighbours brought in have left the L2 -- and the rows they cover per loop trip should divide the band (64 rows
   // at 512^3), or the waves straddle two planes: 256 blocks 67.7 B/cell fetched, 96 (48 rows per trip) 84.1, 128 63.5, 64 43.7, 32 36.1 (32 compulsory;
   // fewer blocks are slower all the same: profiles/r05_schur_var.txt)
-  pl.per_xcd   = (int)std::max<int64_t>(1, std::min<int64_t>((pl.items / 8 + 3) / 4, FL_SV_BLOCKS_PER_XCD));
+  pl.per_xcd   = (int)std::max<int64_t>(1, std::min<int64_t>((pl.items / 8 + 3) / 4, SV_BLOCKS_PER_XCD));
   pl.fixed_seg = ((int64_t)pl.per_xcd * 4) % pl.nseg == 0 ? 1 : 0;  // k_schur_var's own test, with its four waves per block
   return pl;
 }

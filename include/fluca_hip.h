@@ -104,11 +104,10 @@ typedef struct fl_ksp_opts {
   int     maxit;            /* -ksp_max_it   (PETSc default 10000) */
   double  rtol, atol, dtol; /* -ksp_rtol 1e-5, -ksp_atol 1e-50, -ksp_divtol 1e5 */
   double  emin, emax;       /* Chebyshev bounds of the preconditioned operator; 0,0 = Gershgorin bound * (0.1, 1.1) */
-  int     variant;          /* 0 (the only value the product accepts): CG = fused kernels, q = S p formed twice and never stored, x updated
-                               every second iteration (60 B/cell/iteration); BiCGStab = M S p and M S s formed where they are needed and never stored
-                               (120 B/cell/iteration).  Other values select superseded implementations kept for A/B measurements (CG 1 = one kernel
-                               per BLAS-1 / SpMV step, 2 = q stored and read back, 72 B/cell; BiCGStab: products stored, 152 B/cell): they exist in
-                               a -DFL_KBENCH_VARIANTS build of the library only, here the solve returns FL_ERR_SUP. */
+  int     variant;          /* must be 0 (any other value: the solve returns FL_ERR_SUP).  The field once selected superseded implementations; it
+                               stays for the layout of the struct.  CG = fused kernels, q = S p formed twice and never stored, x updated on
+                               every cg_xdepth-th iteration; BiCGStab = M S p and M S s formed where they are needed and never stored
+                               (120 B/cell/iteration). */
   int     check_every;      /* host polls the device-side convergence flag every this many iterations (0 = default 16);
                              * < 0 with FL_NORM_NONE (Chebyshev): never -- exactly maxit steps, no statistics (smoother use) */
   int     profile;          /* n > 0: bracket the kernels of every n-th pair of CG iterations (every Chebyshev launch) with HIP events ->
@@ -224,8 +223,7 @@ int fl_vec_maxpy(fl_poisson *h, int64_t n, double *x_dev, const double *alphas, 
  *   "allreduce"  0 (default) = scalar reductions through ncclAllReduce / the host callback; 1 = the one-shot all-reduce through peer-mapped buffers
  *                (fl_poisson_comm_init_oneshot below).
  * Returns FL_ERR_ARG_WRONG for an unknown name.  Process-wide atomics: handles on several host threads may read them while they run; set a knob
- * before the solves it should affect.  (Switches between a shipped code path and a superseded one -- round 1's kernels, stored-q CG, ... -- are
- * compile-time constants in this library; a -DFL_KBENCH_VARIANTS build turns them into knobs of the same table for A/B measurements.) */
+ * before the solves it should affect.  These knobs are the library's only switches: there is no second build with more of them. */
 int fl_tuning_set(const char *name, int value);
 int fl_tuning_get(const char *name, int *value);
 
@@ -383,7 +381,7 @@ int fl_momentum_face_interp_scaled(fl_momentum *m, double alpha, const double *v
 int fl_momentum_interp_faces(fl_momentum *m, const double *v_dev, const double *const vbc_dev[9], double *const out_dev[9]);
 /* The same rows on the faces at the two ends of each axis of this rank's block only (the inner entries of out are left alone): everything
  * fl_momentum_set_state_v0 reads of v0interp while the operator forms the inner faces from v0 itself (k_mom3) -- a ninth of the work on a 512^3 block.
- * Where the operator will read whole fields anyway (a block with ny <= 8, FLUCA_MOM_KERNEL=2) this IS fl_momentum_interp_faces.
+ * Where the operator will read whole fields anyway (a block with ny <= 8) this IS fl_momentum_interp_faces.
  * A state set with fl_momentum_set_state needs the whole fields: use fl_momentum_interp_faces there. */
 int fl_momentum_interp_faces_ends(fl_momentum *m, const double *v_dev, const double *const vbc_dev[9], double *const out_dev[9]);
 /* The cell-wise part of momrhs, NSFormFunction_CNLinear_Cart3d_Internal (cnlinearcart3d.c:2976-2998):

@@ -3,7 +3,7 @@ import numpy as np
 import pytest
 
 from oracle import fluca_oracle as fo
-from tests.gpu_common import CAVITY, O, PER, SYM, V, dev, host, kbench_build, make_pair, mean_free_rhs
+from tests.gpu_common import CAVITY, O, PER, SYM, V, dev, host, make_pair, mean_free_rhs
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +24,7 @@ def _common(ig, io, hist_rtol=1e-6, iters_tol=2):
     ((130, 37, 20), CAVITY, True, True),
     ((136, 70, 12), [PER, PER, V, V, PER, PER], False, True),
 ])
-@pytest.mark.parametrize("variant", [0, 2])   # 0: M S P and M S S0 formed where needed, never stored; 2: stored (round 1's kernels)
+@pytest.mark.parametrize("variant", [0, 2])   # 0: M S P and M S S0 formed where needed, never stored; 2: the stored form, which left the library
 @pytest.mark.parametrize("pc", [fo.PC_JACOBI, fo.PC_NONE])
 def test_bcgs_matches_oracle(n, bc, nonuni, nullspace, pc, variant):
     P, g = make_pair(n, bc, kappa=1e-3, nonuniform=nonuni)
@@ -34,7 +34,7 @@ def test_bcgs_matches_oracle(n, bc, nonuni, nullspace, pc, variant):
     else:
         b = np.random.default_rng(5).standard_normal(g.ncell)
     rtol = 1e-6
-    if variant and not kbench_build():   # the stored-product form of round 1: a kbench build has it, the product refuses it
+    if variant:   # the library refuses any other value than 0 (fl_ksp_opts.variant)
         from fluca_amd.capi import FlucaError
         with pytest.raises(FlucaError) as e:
             P.solve(dev(b), type=1, pc=pc, variant=variant)

@@ -35,7 +35,7 @@ for row in csv.DictReader(open(os.path.join(R, "trace", "k_kernel_trace.csv"))):
 calib = statistics.median(top_cluster(f["fl::k_pad_copy"])) * 2 * 1024 / (N * 8.0)
 out = {"calibration_k_pad_copy_fetch_over_1GiB": calib}
 for k in sorted(f):
-    if not any(t in k for t in ("k_cg_A<2, 8", "k_cg_Bq<2, 8", "k_cheb2<2, 8", "k_cg_B<4")):
+    if not any(t in k for t in ("k_cg_A<2, 8", "k_cg_Bq<2, 8", "k_cheb2<2, 8")):
         continue
     fv, wv = top_cluster(f[k]), top_cluster(w.get(k, [0.0]))
     fb, wb = statistics.median(fv) * 2 * 1024, statistics.median(wv) * 1024
@@ -53,8 +53,8 @@ json.dump(out, open(os.path.join(ROOT, "profiles", f"{tag}_pmc_summary.json"), "
 # k_cg_Bq runs in two instantiations: r-update only (x-updates 0), and on every K-th iteration of a ring of K direction buffers + the K
 # x-updates owed (k_cg_Bq<..., K, false>; <..., K, true> is the first of a solve).  The per-launch figure quoted by bench.py is their mean
 # weighted as in a solve: ((K - 1) plain + 1 flushing) / K.
-BQ0 = "fl::k_cg_Bq<2, 8, true, 2, 0, false>"
-BQK = [k for k in out if k.startswith("fl::k_cg_Bq<2, 8, true, 2, ") and k.endswith(", false>") and k != BQ0]
+BQ0 = "fl::k_cg_Bq<2, 8, true, 0, false>"
+BQK = [k for k in out if k.startswith("fl::k_cg_Bq<2, 8, true, ") and k.endswith(", false>") and k != BQ0]
 BQ_MEAN = "fl::k_cg_Bq (mean over a ring of K iterations: K - 1 plain launches, one with the x-updates)"
 if BQ0 in out and len(BQK) == 1:
     K = int(BQK[0].split(", ")[-2])
@@ -63,7 +63,7 @@ if BQ0 in out and len(BQK) == 1:
     out[BQ_MEAN] = {"ring_depth": K, "fetch_GB": mean("fetch_GB", 3), "write_GB": mean("write_GB", 3), "hbm_bytes_per_launch": mean("hbm_bytes_per_launch", None),
                     "B_per_cell": mean("B_per_cell", 2), "rocprof_avg_ms_512cubed_launches": mean("rocprof_avg_ms_512cubed_launches", 4)}
     json.dump(out, open(os.path.join(ROOT, "profiles", f"{tag}_pmc_summary.json"), "w"), indent=1)
-for k, name in (("fl::k_cg_A<2, 8, true, 1, 2, false>", "pmc_k_cg_A.json"), ("fl::k_cheb2<2, 8, true, 2, false, 0>", "pmc_k_cheb2.json"),   # the two-step sweep of config 3 (Z = 0; round 5 added the template argument)
+for k, name in (("fl::k_cg_A<2, 8, true>", "pmc_k_cg_A.json"), ("fl::k_cheb2<2, 8, true, 2, false, 0>", "pmc_k_cheb2.json"),   # the two-step sweep of config 3 (Z = 0; round 5 added the template argument)
                 (BQ_MEAN, "pmc_k_cg_Bq.json")):
     if k in out:
         o = dict(out[k])
@@ -71,7 +71,7 @@ for k, name in (("fl::k_cg_A<2, 8, true, 1, 2, false>", "pmc_k_cg_A.json"), ("fl
         o.update({"kernel_key": key, "sources_at_profiling": provenance.source_hashes(key)})
         o.update({"kernel": k, "fetch_bytes_corrected": o["fetch_GB"] * 1e9, "write_bytes": o["write_GB"] * 1e9,
                   "source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over `python3 bench.py --steps 8 --warmup 2 --full --skip-cpu --skip-extras` "
-                            f"(tools/experiments/r0N_profile.sh, summarised by tools/experiments/pmc_summary.py, {tag}); FETCH_SIZE in KB doubled (on gfx950 it counts half the bytes of a coalesced streaming read)"})
+                            f"(rocprofv3 runs as in tools/experiments/bench_profile.sh, summarised by tools/experiments/pmc_summary.py, {tag}); FETCH_SIZE in KB doubled (on gfx950 it counts half the bytes of a coalesced streaming read)"})
         json.dump(o, open(os.path.join(ROOT, "profiles", name), "w"), indent=1)
 # the other sizes the same passes saw (bench.py --full runs the configs behind the headline): 256^3 (config 2) and the 512 x 512 x 256 block of the config-5
 # rehearsal -- counter values near 1/8 and 1/2 of the 512^3 ones.  One record per workload: HBM bytes per launch of k_cg_A and of k_cg_Bq (mean of

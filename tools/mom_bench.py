@@ -82,18 +82,7 @@ def main():
         P._post()
         assert rc == 0, rc
         out[f"kernel_ms_mode{mode}"] = ms.value
-    out["kernel"] = os.environ.get("FLUCA_MOM_KERNEL", "3" if a.fly else "2")
-    # streaming ceiling of the same access mix (15 reads + 3 writes, flat)
-    if not hasattr(lib, "fldbg_mom_stream"):   # the probe lives in the kbench build of the library only (FLUCA_LIB_DIR=fluca_amd/lib_kbench)
-        print(json.dumps(out))
-        return
-    lib.fldbg_mom_stream.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
-    for blocks in (2048, 8192):
-        ms = C.c_double()
-        P._pre()
-        lib.fldbg_mom_stream(M.h, 5, blocks, C.byref(ms))
-        P._post()
-        out[f"stream15r3w_ms_{blocks}"] = ms.value
+    out["kernel"] = "3" if a.fly else "2"   # k_mom3 when the state came with v0, else k_mom2
     print(json.dumps(out))
 
 

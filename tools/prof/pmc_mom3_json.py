@@ -17,7 +17,7 @@ N = 512 ** 3
 out = {"kernel": key, "kernel_key": kk, "hbm_bytes_per_launch": e["hbm_GB"] * 1e9, "fetch_bytes_corrected": e["fetch_GB_corrected"] * 1e9,
        "write_bytes": e["write_GB"] * 1e9, "B_per_cell": round(e["hbm_GB"] * 1e9 / N, 2), "rocprof_avg_ms_512cubed_launches": e["mean_ms"], "launches": e["launches"],
        "sources_at_profiling": provenance.source_hashes(kk),
-       "source": f"tools/experiments/{tag}_profile.sh: tools/prof/pmc_kernel.sh over `python3 tools/mom_bench.py --cells 512 --fly {1 if kk == 'k_mom3' else 0} --nosolve --reps 5` (separate FETCH_SIZE / "
+       "source": f"rocprofv3 passes as in tools/prof/pmc_kernel.sh over `python3 tools/mom_bench.py --cells 512 --fly {1 if kk == 'k_mom3' else 0} --nosolve --reps 5` (separate FETCH_SIZE / "
                  f"WRITE_SIZE passes, FETCH doubled), summarised by tools/prof/pmc_table.py; all variants and the other counters in profiles/{tag}_{kk[2:]}_pmc.json"}
 json.dump(out, open(os.path.join(ROOT, "profiles", f"pmc_{kk}.json"), "w"), indent=1)
 json.dump(tab, open(os.path.join(ROOT, "profiles", f"{tag}_{kk[2:]}_pmc.json"), "w"), indent=1)

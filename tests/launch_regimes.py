@@ -5,7 +5,9 @@ The kernels pick their tiling, z chunks and grid stride from the grid size, and 
 REGIMES names a grid per plan branch that the product runs at 256^3 - 512^3, made ragged on purpose (partial tiles, a short last z chunk, a
 grid stride that wraps), with the fields of the plans it must get; the multigrid regimes name, per level of the hierarchy, the plans of the cycle
 (mg_plans).  tests/test_launch_regimes.py checks the table against the library on the CPU; tests/test_gpu_launch_regimes.py,
-tests/test_gpu_momentum_regimes.py and tests/test_gpu_mg_regimes.py check every kernel on these grids against the oracle."""
+tests/test_gpu_momentum_regimes.py and tests/test_gpu_mg_regimes.py check every kernel on these grids against the oracle.  RANK_REGIMES names
+rank grids whose blocks take the same 8-wave plans (and k_schur_var_ring's 128 blocks per XCD); tests/test_gpu_rank_regimes.py runs the several-rank
+kernels on them."""
 import ctypes as C
 
 from oracle import fluca_oracle as fo
@@ -283,3 +285,79 @@ PRODUCTION_MG = {
     (384, 384, 384): {"mg.levels": 7, "mg.rr_fused": (0, 1), "mg.coarse": "coarse_cg"},
     (256, 256, 256): {"mg.levels": 7, "mg.rr_fused": (0, 1, 2), "mg.coarse": "coarse_cg"},
 }
+
+
+# ---- several ranks: rank grids whose BLOCKS take the plans of 256^3 - 512^3.  What a rank of a several-rank solve runs differently from one rank
+# -- q stored on the block's six boundary layers only (PlanA::qb), the neighbour's ghost of r formed from them, the two-deep exchange under
+# k_cheb2, k_project_six<false> on the padded p, k_schur_var_ring -- meets the ragged tile, chunk and band edges only on such blocks.
+class RankRegime:
+    def __init__(self, name, n, ranks, own, bcs, blocks, expect, reaches):
+        # own: ownership ranges per axis, None = the DMStag default split (mp_common.decomp_of); blocks: the block of every rank, in rank order
+        # (x fastest); expect: the plan fields every block must get, or one dict per rank
+        self.name, self.n, self.ranks, self.own, self.bcs, self.blocks, self.reaches = name, tuple(n), tuple(ranks), own, bcs, blocks, reaches
+        self.expect = expect if isinstance(expect, list) else [expect] * len(blocks)
+        assert len(self.blocks) == len(self.expect) == ranks[0] * ranks[1] * ranks[2]
+
+    def __repr__(self):
+        return f"{self.name} {self.n[0]}x{self.n[1]}x{self.n[2]} on {self.ranks[0]}x{self.ranks[1]}x{self.ranks[2]} ranks"
+
+    def decomp(self, rank):
+        """the fl_decomp of a rank: the default split, or the ownership ranges"""
+        from fluca_amd import capi
+        from tests import mp_common as mpc
+        d = mpc.decomp_of(capi, self.n, self.ranks, rank)
+        if self.own is not None:
+            for a in range(3):
+                d.len[a] = self.own[a][d.coord[a]]
+                d.lo[a] = sum(self.own[a][:d.coord[a]])
+        return d
+
+    def periodic(self, bc):
+        return [bc[2 * a] == PER for a in range(3)]
+
+
+_RSTD = {"cg.regime": "standard", "cg.ry": 2, "cg.nw": 8, "cg.tiles_x": 3, "cg.tiles_y": 43, "cg.nchunk": 2, "cg.zc": 11, "cg.nblocks": 258,
+         "cheb2.nw": 8, "cheb2.tiles": 129, "cheb2.nchunk": 1, "cheb2.clamp": 1, "six.nbx": 1026, "six.items": 5355}
+_RMID = {"cg.regime": "mid", "cg.ry": 2, "cg.nw": 8, "cg.tiles_x": 3, "cg.tiles_y": 13, "cg.nchunk": 6, "cg.zc": 47, "cg.nblocks": 234,
+         "cheb2.nw": 8, "cheb2.tiles": 39, "cheb2.nchunk": 6, "cheb2.zc": 47, "cheb2.clamp": 1, "six.nbx": 1026}
+_RSF = {"cg.regime": "small_ry1", "schur.per_xcd": 128, "schur.nseg": 4, "schur.fixed_seg": 1, "schur.band": 5}
+_RSG = {"cg.regime": "small", "schur.per_xcd": 128, "schur.nseg": 5, "schur.fixed_seg": 0, "schur.band": 5}
+
+RANK_REGIMES = [
+    RankRegime("ranks_std_z", (300, 680, 42), (1, 1, 2), None, [CAVITY, CHANNEL], [(300, 680, 21)] * 2, _RSTD,
+               "the 2-GPU layout of the bench: the exchanged face is a whole 300 x 680 plane; the stored q planes are plane 0 (first of chunk 0) and "
+               "plane 20 (last of the short chunk of 10); CHANNEL: z periodic across the two ranks (the same peer on both sides)"),
+    RankRegime("ranks_std_xy", (601, 1359, 21), (2, 2, 1), None, [XPER, CAVITY], [(301, 680, 21), (300, 680, 21), (301, 679, 21), (300, 679, 21)], _RSTD,
+               "2 x 2 ranks: the edge cells of the deep exchange travel in two hops; blocks with odd nx (301: the last cell alone in its lane's pair) "
+               "and odd ny (679: the last row alone in its wave's pair); XPER: x periodic across ranks, z wraps inside the block"),
+    RankRegime("ranks_mid_y", (300, 401, 281), (1, 2, 1), None, [CHANNEL], [(300, 201, 281), (300, 200, 281)], _RMID,
+               "a y face of 300 x 281 cells across the 6 z chunks of the mid plan (5 x 47 + 46); the last row of the low block (201 rows) sits alone in "
+               "its wave's pair of rows in a partial y tile; z periodic inside the block across the chunks"),
+    RankRegime("ranks_mid_x", (601, 200, 280), (2, 1, 1), None, [XPER], [(301, 200, 280), (300, 200, 280)], _RMID,
+               "an x face of 200 x 280 cells across the 6 z chunks (5 x 47 + 45), x periodic across the two ranks; the last cell of the 301 block "
+               "alone in its lane's pair, in the partial x tile"),
+    # k_schur_var_ring at 128 blocks per XCD: the blocks are those of the schur_fixed_seg and schur_general regimes, split along each axis in turn
+    # (the x split of that block, 400 x 37 x 40, is no use: the momentum kernels form diag(A) of the x component by another code path in the first, the
+    # inner and the last 128-column tile of a block, 2 ulp apart in a quarter of the cells; in 256 of the 400 columns a rank's tile is of another kind than
+    # the one-rank tile, and tests/test_gpu_schur_var_multirank.py::_same_bits then finds 34 % of the cells next to such an entry, above its cap of a
+    # quarter (measured).  Blocks of 456 columns -- eight segments, the last one again 8 cells wide -- leave 256 such columns of 912: 15 %)
+    RankRegime("ranks_schur_fixed_x", (912, 37, 40), (2, 1, 1), ([456, 456], [37], [40]), [CAVITY], [(456, 37, 40)] * 2,
+               {"cg.regime": "small", "schur.per_xcd": 128, "schur.nseg": 8, "schur.fixed_seg": 1, "schur.band": 5},
+               "a wave keeps its x segment (eight of them, the last one 8 cells wide): the x split puts the ring into the rows a wave loads once"),
+    RankRegime("ranks_schur_fixed_y", (200, 74, 40), (1, 2, 1), ([200], [37, 37], [40]), [CAVITY], [(200, 37, 40)] * 2, _RSF,
+               "the ring rows below / above the y bands of 5 with a last band of 2"),
+    RankRegime("ranks_schur_fixed_z", (200, 37, 80), (1, 1, 2), ([200], [37], [40, 40]), [CAVITY], [(200, 37, 40)] * 2, _RSF,
+               "the ring planes; a symmetry plane and a wall at the two outer z ends"),
+    RankRegime("ranks_schur_general_x", (600, 37, 40), (2, 1, 1), ([300, 300], [37], [40]), [XPER], [(300, 37, 40)] * 2, _RSG,
+               "a wave's x segment changes from row to row; x periodic across the two ranks (the same peer on both sides)"),
+    RankRegime("ranks_schur_general_z", (300, 37, 80), (1, 1, 2), ([300], [37], [40, 40]), [XPER], [(300, 37, 40)] * 2, _RSG,
+               "z periodic across the two ranks, x wraps inside the block"),
+]
+RANK_BY_NAME = {r.name: r for r in RANK_REGIMES}
+
+# the blocks of the several-rank tests on toy grids (tests/test_gpu_multirank.py, tests/test_gpu_config5.py, tests/test_gpu_schur_var_multirank.py): none
+# takes an 8-wave plan
+TOY_RANK_BLOCKS = [(24, 20, 8), (12, 20, 16), (24, 10, 16), (70, 18, 12), (68, 20, 12), (70, 6, 10), (20, 18, 12), (16, 16, 16), (24, 16, 16),
+                   (12, 20, 8), (16, 16, 8), (8, 16, 8),                                                             # test_gpu_multirank
+                   (32, 24, 16), (21, 19, 15), (20, 18, 14), (24, 20, 16), (20, 16, 12), (64, 32, 16), (64, 32, 15),   # test_gpu_config5
+                   (5, 9, 8), (8, 9, 8), (9, 6, 4), (9, 7, 7), (5, 6, 3), (7, 5, 7), (7, 6, 7), (12, 16, 12)]          # test_gpu_schur_var_multirank

@@ -1,12 +1,12 @@
 """The regime table of tests/launch_regimes.py against the plans the library computes (fldbg_launch_plans: host arithmetic, no GPU).
 
 If a threshold of a plan moves, these tests name the regime whose grid no longer reaches its branch: the -m gpu modules
-tests/test_gpu_launch_regimes.py, tests/test_gpu_momentum_regimes.py and tests/test_gpu_mg_regimes.py then check another plan than the one they were written for, and the
-table must be re-aimed."""
+tests/test_gpu_launch_regimes.py, tests/test_gpu_momentum_regimes.py, tests/test_gpu_mg_regimes.py and tests/test_gpu_rank_regimes.py then check another plan
+than the one they were written for, and the table must be re-aimed."""
 import pytest
 
-from tests.launch_regimes import (BY_NAME, CAVITY, CHANNEL, FIELDS, PER, PRODUCTION, PRODUCTION_MG, REGIMES, SYM, O, V, launch_plans, mg_levels,
-                                  mg_plans, mg_restrict_fused, mg_summary, mom_last_chunk, mom_regime, mom_tiles, six_trips)
+from tests.launch_regimes import (BY_NAME, CAVITY, CHANNEL, FIELDS, PER, PRODUCTION, PRODUCTION_MG, RANK_REGIMES, REGIMES, SYM, TOY_RANK_BLOCKS, XPER, O, V,
+                                  launch_plans, mg_levels, mg_plans, mg_restrict_fused, mg_summary, mom_last_chunk, mom_regime, mom_tiles, six_trips)
 
 
 @pytest.mark.parametrize("reg", REGIMES, ids=[r.name for r in REGIMES])
@@ -71,6 +71,68 @@ def test_table_covers_every_branch_of_the_momentum_tiling():
     }
     missing = [what for what, names in covered.items() if not names]
     assert not missing, f"no momentum regime reaches: {missing}"
+
+
+@pytest.mark.parametrize("reg", RANK_REGIMES, ids=[r.name for r in RANK_REGIMES])
+def test_rank_regime_blocks_take_their_plans(reg):
+    """every rank's block, formed as the library forms it (fl_decomp_default / the ownership ranges), has the table's shape and takes the table's plan"""
+    size = reg.ranks[0] * reg.ranks[1] * reg.ranks[2]
+    cells = 0
+    for rank in range(size):
+        d = reg.decomp(rank)
+        blk = tuple(int(d.len[a]) for a in range(3))
+        assert blk == reg.blocks[rank], f"regime {reg.name}: rank {rank} owns {blk}, the table says {reg.blocks[rank]}"
+        cells += blk[0] * blk[1] * blk[2]
+        got = launch_plans(blk)
+        wrong = {k: (v, got[k]) for k, v in reg.expect[rank].items() if got[k] != v}
+        assert not wrong, f"regime {reg.name} {reg.n}, rank {rank} block {blk} left its plan ({reg.reaches}); field: (expected, got) {wrong}"
+    assert cells == reg.n[0] * reg.n[1] * reg.n[2], f"regime {reg.name}: the blocks do not tile the grid"
+
+
+def test_rank_table_covers_every_edge_of_the_several_rank_path():
+    """what tests/test_gpu_rank_regimes.py is there for: rank faces, periodic seams, two-hop edges and ragged block edges on 8-wave plans, the
+    clamped k_cheb2 plan over several chunks, k_schur_var_ring at 128 blocks per XCD -- and that the toy grids of the other several-rank tests
+    reach none of the 8-wave plans"""
+    plans = {r.name: [launch_plans(b) for b in r.blocks] for r in RANK_REGIMES}
+    w8 = [r for r in RANK_REGIMES if all(p["cg.nw"] == 8 for p in plans[r.name])]
+    left = [(r.name, b) for r in RANK_REGIMES if not r.name.startswith("ranks_schur") for b, p in zip(r.blocks, plans[r.name]) if p["cg.nw"] != 8]
+    assert not left, f"blocks that left the 8-wave plans: {left}"
+    regime = lambda r: {p["cg.regime"] for p in plans[r.name]}
+    blocks8 = [(r, b, p) for r in w8 for b, p in zip(r.blocks, plans[r.name])]
+    covered = {
+        # a rank face on every axis in the standard regime, on x and y in the mid regime
+        **{f"standard, rank face on axis {a}": [r.name for r in w8 if regime(r) == {"standard"} and r.ranks[a] > 1] for a in range(3)},
+        **{f"mid, rank face on axis {a}": [r.name for r in w8 if regime(r) == {"mid"} and r.ranks[a] > 1] for a in range(2)},
+        # a periodic axis split over two ranks (the same peer on both sides), and one held by one rank (wrap_local) next to a split axis
+        "periodic axis over two ranks": [r.name for r in w8 for bc in r.bcs for a in range(3) if r.periodic(bc)[a] and r.ranks[a] == 2],
+        "periodic axis inside the block next to a split axis": [r.name for r in w8 for bc in r.bcs for a in range(3)
+                                                                if r.periodic(bc)[a] and r.ranks[a] == 1 and max(r.ranks) > 1],
+        # 2 x 2 ranks: the edge cells of fl_fill_ghosts_deep travel in two hops
+        "2 x 2 rank grid": [r.name for r in w8 if sorted(r.ranks) == [1, 2, 2]],
+        # ragged block edges: odd nx / ny (the last cell / row alone in its pair), partial last tiles, a short last z chunk
+        "odd nx": [r.name for r, b, p in blocks8 if b[0] % 2 == 1],
+        "odd ny": [r.name for r, b, p in blocks8 if b[1] % 2 == 1],
+        "cheb2 clamp, several z chunks": [r.name for r, b, p in blocks8 if p["cheb2.clamp"] == 1 and p["cheb2.nchunk"] > 1 and b[2] % p["cheb2.zc"] != 0],
+        # k_schur_var_ring: the full launch, with and without a fixed x segment; a split of each axis
+        "schur ring, fixed segment": [r.name for r in RANK_REGIMES if all(p["schur.per_xcd"] == 128 and p["schur.fixed_seg"] == 1 for p in plans[r.name])
+                                      and r.name.startswith("ranks_schur")],
+        "schur ring, general segments": [r.name for r in RANK_REGIMES if all(p["schur.per_xcd"] == 128 and p["schur.fixed_seg"] == 0 for p in plans[r.name])
+                                         and r.name.startswith("ranks_schur")],
+        **{f"schur ring, split of axis {a}": [r.name for r in RANK_REGIMES if r.name.startswith("ranks_schur") and r.ranks[a] == 2] for a in range(3)},
+    }
+    missing = [what for what, names in covered.items() if not names]
+    assert not missing, f"no rank regime reaches: {missing}"
+    assert {tuple(bc) for r in w8 for bc in r.bcs} >= {tuple(CAVITY), tuple(CHANNEL), tuple(XPER)}
+    for r, b, p in blocks8:
+        assert b[0] % 128 != 0 and b[1] % 16 != 0, f"{r.name} {b}: the last 8-wave tile is full in x or y"
+        assert p["cg.nchunk"] > 1 and b[2] % p["cg.zc"] != 0, f"{r.name} {b}: no short last z chunk"
+        assert six_trips(p) > 1, f"{r.name} {b}: k_project_six takes one grid-stride trip"
+    for r in RANK_REGIMES:
+        if r.name.startswith("ranks_schur"):
+            assert all(p["schur.per_xcd"] == 128 for p in plans[r.name]), r.name
+    # the several-rank tests on toy grids: no block of theirs takes an 8-wave plan
+    for b in TOY_RANK_BLOCKS:
+        assert launch_plans(b)["cg.nw"] != 8, b
 
 
 MOM = [r for r in REGIMES if r.name.startswith("mom_")]

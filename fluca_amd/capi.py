@@ -129,6 +129,7 @@ PROTOTYPES = {
     "fl_halo_plan": (C.c_int, [C.POINTER(fl_decomp), C.POINTER(C.c_int), C.POINTER(fl_halo_msg)]),
     "fl_decomp_default": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int), C.c_int, C.POINTER(fl_decomp)]),
     "fl_decomp_neighbor": (C.c_int, [C.POINTER(fl_decomp), C.POINTER(C.c_int), C.c_int]),
+    "fl_decomp_neighbor_offset": (C.c_int, [C.POINTER(fl_decomp), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "fl_momentum_create": (C.c_int, [_P, C.POINTER(_P)]),
     "fl_momentum_destroy": (C.c_int, [_P]),
     "fl_momentum_set_state": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P, _P]),
@@ -162,6 +163,9 @@ PROTOTYPES = {
     "fl_ibm_interp": (C.c_int, [_P, C.c_int, _P, _P]),
     "fl_ibm_spread": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "fl_ibm_destroy": (C.c_int, [_P]),
+    "fl_ibm_owned_select": (C.c_int, [_P, C.c_int, C.c_int64, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "fl_ibm_create_owned": (C.c_int, [_P, C.c_int, C.c_int64, _P, _P, _P, _P, C.POINTER(_P)]),
+    "fl_ibm_owned_counts": (C.c_int, [_P, C.POINTER(C.c_int64)]),
 }
 for _name, (_res, _args) in PROTOTYPES.items():
     _f = getattr(lib, _name)  # AttributeError if the library lacks a declared symbol

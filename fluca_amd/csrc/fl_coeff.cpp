@@ -216,6 +216,21 @@ extern "C" int fl_decomp_neighbor(const fl_decomp *d, const int periodic[3], int
   return (c[2] * d->ranks[1] + c[1]) * d->ranks[0] + c[0];
 }
 
+extern "C" int fl_decomp_neighbor_offset(const fl_decomp *d, const int periodic[3], const int offset[3])
+{
+  if (!d || !periodic || !offset) return -1;
+  int c[3];
+  for (int ax = 0; ax < 3; ++ax) {
+    if (offset[ax] < -1 || offset[ax] > 1) return -1;
+    c[ax] = d->coord[ax] + offset[ax];
+    if (c[ax] < 0 || c[ax] >= d->ranks[ax]) {
+      if (!periodic[ax]) return -1;
+      c[ax] = (c[ax] + d->ranks[ax]) % d->ranks[ax];
+    }
+  }
+  return (c[2] * d->ranks[1] + c[1]) * d->ranks[0] + c[0];
+}
+
 extern "C" int fl_halo_plan(const fl_decomp *d, const int periodic[3], fl_halo_msg out[12])
 {
   if (!d || !periodic || !out) return FL_ERR_ARG_NULL;

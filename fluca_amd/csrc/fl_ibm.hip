@@ -17,6 +17,18 @@
 //   k_ibm_spread    gather form, no atomics: one 256-thread block per 8x8x8 tile of cells; the markers whose support
 //                   touches the tile (per-tile bins built at create/update) are staged in LDS, rank-sorted by marker id
 //                   in LDS so that every cell accumulates in a run-independent order -> bitwise reproducible
+//
+// Several ranks, two ways to hold the markers:
+//   replicated (fl_ibm_create)        every rank holds all L markers; interp ends in an all-reduce of ncomp L doubles
+//   owner rank (fl_ibm_create_owned)  a marker lives on the rank that owns the cell nearest to it; where its support reaches into a
+//                                     neighbouring block, that neighbour holds a GHOST COPY of the marker (position and id, exchanged at
+//                                     create / update).  Both ranks run the kernels above over own + ghost markers on their own cells;
+//                                     interp returns the ghosts' partial sums to the owners, spread sends F and dV of the copies out.
+//                                     No field and no all-reduce is involved: (ghost copies) x 24-32 bytes per call.
+//   k_ibm_route     one lane per own marker: is its cell in this block, and which of the 26 neighbour offsets does its support reach
+//   k_ibm_pack_pos / k_ibm_unpack_pos, k_ibm_pack_U, k_ibm_collect_U, k_ibm_pack_F, k_ibm_stage_F
+//                   one lane per copy / ghost / marker: records of the messages through the send list, and the owners' sums in
+//                   ascending offset code (a fixed order: deterministic)
 #include "fl_handle.h"
 
 namespace fl {
@@ -53,6 +65,23 @@ struct IbmP {
   const double *idx[3];  // LOCAL 1/dx (GridP::idx): the target cell's volume
 };
 
+// position -> continuous cell-centre index s along axis d
+__device__ __forceinline__ double ibm_index(const IbmP &P, int d, double pos)
+{
+  if (P.uniform[d]) return (pos - P.x0[d]) / P.h[d] - 0.5;
+  // the interval [centre(c), centre(c+1)) that holds the marker, c = -1 .. ng-1 (linear extension beyond the ghost centres)
+  const double *xc = P.xcg[d];
+  int           lo = -1, hi = P.ng[d] - 1;
+  while (lo < hi) {
+    const int mid = lo + (hi - lo + 1) / 2;
+    if (xc[mid] <= pos) lo = mid;
+    else hi = mid - 1;
+  }
+  return (double)lo + (pos - xc[lo]) / (xc[lo + 1] - xc[lo]);
+}
+// first support cell (GLOBAL index, may be out of range)
+__device__ __forceinline__ int ibm_first(const IbmP &P, double s) { return (P.kind == FL_DELTA_PESKIN4) ? (int)floor(s) - 1 : (int)floor(s + 0.5) - 1; }
+
 // i0[d*L + l] = first support cell (GLOBAL index, may be out of range); w[(d*4 + a)*L + l] = phi weights
 __global__ void k_ibm_weights(IbmP P, const double *__restrict__ X, const double *__restrict__ Y, const double *__restrict__ Z, int *__restrict__ i0, double *__restrict__ w)
 {
@@ -61,20 +90,8 @@ __global__ void k_ibm_weights(IbmP P, const double *__restrict__ X, const double
   const double pos[3] = {X[l], Y[l], Z[l]};
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
-    double s;  // position in units of the cell-centre index
-    if (P.uniform[d]) s = (pos[d] - P.x0[d]) / P.h[d] - 0.5;
-    else {
-      // the interval [centre(c), centre(c+1)) that holds the marker, c = -1 .. ng-1 (linear extension beyond the ghost centres)
-      const double *xc = P.xcg[d];
-      int           lo = -1, hi = P.ng[d] - 1;
-      while (lo < hi) {
-        const int mid = lo + (hi - lo + 1) / 2;
-        if (xc[mid] <= pos[d]) lo = mid;
-        else hi = mid - 1;
-      }
-      s = (double)lo + (pos[d] - xc[lo]) / (xc[lo + 1] - xc[lo]);
-    }
-    const int    i = (P.kind == FL_DELTA_PESKIN4) ? (int)floor(s) - 1 : (int)floor(s + 0.5) - 1;
+    const double s = ibm_index(P, d, pos[d]);  // position in units of the cell-centre index
+    const int    i = ibm_first(P, s);
     for (int a = 0; a < 4; ++a) {
       const double r          = s - (double)(i + a);
       w[(d * 4 + a) * P.L + l] = a < P.S ? (P.kind == FL_DELTA_PESKIN4 ? phi_peskin4(r) : phi_roma3(r)) : 0.;
@@ -83,9 +100,10 @@ __global__ void k_ibm_weights(IbmP P, const double *__restrict__ X, const double
   }
 }
 
-// LOCAL cell index of support entry a, or -1 when that cell is not owned by this rank.  Every rank sees every marker
-// (markers are replicated); a support that straddles a block face is simply shared out between the two owners, and a
-// support that crosses a periodic boundary wraps in GLOBAL index space first.
+// LOCAL cell index of support entry a, or -1 when that cell is not owned by this rank.  Every rank sees every marker whose
+// support touches its block (replicated markers: all of them; owner-rank markers: its own and the ghost copies); a support
+// that straddles a block face is simply shared out between the two owners, and a support that crosses a periodic boundary
+// wraps in GLOBAL index space first.
 __device__ __forceinline__ int support_cell(const IbmP &P, int d, int i0, int a)
 {
   int c = i0 + a;
@@ -263,8 +281,10 @@ __global__ void k_ibm_active(const int *__restrict__ off, int ntiles, int *__res
   if (t < ntiles && off[t + 1] > off[t]) active[atomicAdd(nactive, 1)] = t;
 }
 
-// in-place ascending sort of every bin (marker ids are unique within a bin): rank sort, one block per tile
-__global__ void __launch_bounds__(256) k_ibm_sort_bins(const int *__restrict__ off, int *__restrict__ list, int *__restrict__ scratch, const int *__restrict__ active)
+// in-place ascending sort of every bin by marker id: rank sort, one block per tile.  The id is the list index (replicated markers,
+// unique within a bin) or, for owner-rank markers, the caller's global number gid[] (ties, which a caller's duplicate numbers would
+// make, fall back to the list index) -- so that a cell adds the same markers in the same order however they are shared out.
+__global__ void __launch_bounds__(256) k_ibm_sort_bins(const int *__restrict__ off, int *__restrict__ list, int *__restrict__ scratch, const int *__restrict__ active, const int64_t *__restrict__ gid)
 {
   const int tile = active[blockIdx.x];
   const int beg = off[tile], end = off[tile + 1], n = end - beg;
@@ -272,11 +292,134 @@ __global__ void __launch_bounds__(256) k_ibm_sort_bins(const int *__restrict__ o
   for (int e = threadIdx.x; e < n; e += 256) {
     const int v = list[beg + e];
     int       rank = 0;
-    for (int o = 0; o < n; ++o) rank += list[beg + o] < v;
+    if (!gid)
+      for (int o = 0; o < n; ++o) rank += list[beg + o] < v;
+    else {
+      const int64_t kv = gid[v];
+      for (int o = 0; o < n; ++o) {
+        const int     u  = list[beg + o];
+        const int64_t ku = gid[u];
+        rank += (ku < kv) || (ku == kv && u < v);
+      }
+    }
     scratch[beg + rank] = v;
   }
   __syncthreads();
   for (int e = threadIdx.x; e < n; e += 256) list[beg + e] = scratch[beg + e];
+}
+
+// ---- owner-rank markers ---------------------------------------------------------------------------------------------------------
+// Neighbour offsets o in {-1,0,1}^3 are numbered code = (oz+1)*9 + (oy+1)*3 + (ox+1); 13 is the block itself, 26 - code the opposite offset.
+struct RouteP {
+  int peer_lo[3], peer_hi[3];  // a rank sits behind the low / high end of the block along this axis (not a wall, not an axis one rank holds alone)
+};
+
+// mask[l] = the set of offsets (bit = code) whose blocks the support of own marker l reaches, or -1 when the marker does not belong to this
+// rank.  THE OWNERSHIP RULE: the marker belongs to the block that holds the cell floor(s_d + 1/2) on every axis, the index wrapped on a periodic
+// axis and clamped to [0, ng-1] otherwise -- global quantities only, so every marker has exactly one owner.  That cell lies inside the support of
+// either delta function, so along an axis the support leaves a block of >= 4 cells through one end at most: below, if its first entries are not
+// this rank's (support_cell < 0), above, if its last ones are not.
+__global__ void k_ibm_route(IbmP P, RouteP R, const double *__restrict__ X, const double *__restrict__ Y, const double *__restrict__ Z, int *__restrict__ mask)
+{
+  const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= P.L) return;
+  const double pos[3] = {X[l], Y[l], Z[l]};
+  bool         mine = true, dn[3], up[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const double s = ibm_index(P, d, pos[d]);
+    int          c = (int)floor(s + 0.5);
+    if (P.periodic[d]) {
+      c %= P.ng[d];
+      if (c < 0) c += P.ng[d];
+    } else c = min(max(c, 0), P.ng[d] - 1);
+    mine = mine && c >= P.lo[d] && c < P.lo[d] + P.n[d];
+    const int i     = ibm_first(P, s);
+    int       first = -1, last = -1;
+    for (int a = 0; a < P.S; ++a)
+      if (support_cell(P, d, i, a) >= 0) {
+        if (first < 0) first = a;
+        last = a;
+      }
+    dn[d] = first > 0 && R.peer_lo[d];
+    up[d] = last >= 0 && last < P.S - 1 && R.peer_hi[d];
+  }
+  int bits = 0;
+  for (int code = 0; code < 27; ++code) {
+    if (code == 13) continue;
+    const int o[3] = {code % 3 - 1, (code / 3) % 3 - 1, code / 9 - 1};
+    bool      hit  = true;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) hit = hit && (o[d] == 0 || (o[d] < 0 ? dn[d] : up[d]));
+    if (hit) bits |= 1 << code;
+  }
+  mask[l] = mine ? bits : -1;
+}
+
+// Messages hold one record per copy, the copies of an offset next to each other (the send list is grouped by ascending offset code, the
+// ghosts are stored in that order too): a message is a contiguous piece of the buffer and no kernel needs to know where one ends.
+// positions: (X, Y, Z, gid) of the copies through the send list
+__global__ void k_ibm_pack_pos(int ncopy, const int *__restrict__ sendlist, const double *__restrict__ X, const double *__restrict__ Y, const double *__restrict__ Z, const int64_t *__restrict__ gid, double *__restrict__ buf)
+{
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= ncopy) return;
+  const int l    = sendlist[j];
+  buf[4 * j + 0] = X[l];
+  buf[4 * j + 1] = Y[l];
+  buf[4 * j + 2] = Z[l];
+  buf[4 * j + 3] = gid ? (double)gid[l] : 0.;  // marker numbers stay below 2^27: exact
+}
+// ... and into the marker arrays behind the Lo own markers
+__global__ void k_ibm_unpack_pos(int nghost, int64_t Lo, const double *__restrict__ buf, double *__restrict__ X, double *__restrict__ Y, double *__restrict__ Z, int64_t *__restrict__ gid)
+{
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= nghost) return;
+  X[Lo + g] = buf[4 * g + 0];
+  Y[Lo + g] = buf[4 * g + 1];
+  Z[Lo + g] = buf[4 * g + 2];
+  if (gid) gid[Lo + g] = (int64_t)buf[4 * g + 3];
+}
+// interp: the ghosts' partial sums (Ui: ncomp x Lt, own markers first) as records of ncomp
+__global__ void k_ibm_pack_U(int nghost, int64_t Lo, int64_t Lt, int ncomp, const double *__restrict__ Ui, double *__restrict__ buf)
+{
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= nghost) return;
+  for (int c = 0; c < ncomp; ++c) buf[(int64_t)g * ncomp + c] = Ui[(int64_t)c * Lt + Lo + g];
+}
+// interp: U of own marker l = its own partial sum + those of its copies cl[cs[l] .. cs[l+1]) in ascending copy number (= offset code)
+__global__ void k_ibm_collect_U(int64_t Lo, int64_t Lt, int ncomp, const double *__restrict__ Ui, const int *__restrict__ cs, const int *__restrict__ cl, const double *__restrict__ buf, double *__restrict__ U)
+{
+  const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= Lo) return;
+  const int beg = cs[l], end = cs[l + 1];
+  for (int c = 0; c < ncomp; ++c) {
+    double v = Ui[(int64_t)c * Lt + l];
+    for (int j = beg; j < end; ++j) v += buf[(int64_t)cl[j] * ncomp + c];
+    U[(int64_t)c * Lo + l] = v;
+  }
+}
+// spread: (F_0 .. F_ncomp-1, dV) of the copies through the send list
+__global__ void k_ibm_pack_F(int ncopy, int64_t Lo, int ncomp, const int *__restrict__ sendlist, const double *__restrict__ F, const double *__restrict__ dV, double *__restrict__ buf)
+{
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= ncopy) return;
+  const int l = sendlist[j];
+  for (int c = 0; c < ncomp; ++c) buf[(int64_t)j * (ncomp + 1) + c] = F[(int64_t)c * Lo + l];
+  buf[(int64_t)j * (ncomp + 1) + ncomp] = dV[l];
+}
+// spread: F / dV of own + ghost markers in the layout k_ibm_spread reads (stride Lt): the caller's for the own ones, the records received for the ghosts
+__global__ void k_ibm_stage_F(int64_t Lo, int64_t Lt, int ncomp, const double *__restrict__ F, const double *__restrict__ dV, const double *__restrict__ buf, double *__restrict__ Fi, double *__restrict__ dVi)
+{
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= Lt) return;
+  if (t < Lo) {
+    for (int c = 0; c < ncomp; ++c) Fi[(int64_t)c * Lt + t] = F[(int64_t)c * Lo + t];
+    dVi[t] = dV[t];
+  } else {
+    const int64_t g = t - Lo;
+    for (int c = 0; c < ncomp; ++c) Fi[(int64_t)c * Lt + t] = buf[g * (ncomp + 1) + c];
+    dVi[t] = buf[g * (ncomp + 1) + ncomp];
+  }
 }
 
 }  // namespace fl
@@ -289,7 +432,19 @@ struct fl_ibm {
   double     *X = nullptr, *Y = nullptr, *Z = nullptr, *w = nullptr;
   int        *i0 = nullptr, *cnt = nullptr, *off = nullptr, *list = nullptr, *scratch = nullptr, *active = nullptr, *nact_dev = nullptr;
   int         ntiles = 0, listcap = 0, nactive = 0;
+  int64_t     cap = -1;                               // markers the per-marker arrays above hold
   double     *xcg[3] = {nullptr, nullptr, nullptr};  // device copies of the extended global centre arrays (stretched axes only)
+  // owner-rank markers (fl_ibm_create_owned): P.L = Lo + Lg, own markers first, then the ghosts grouped by ascending offset code
+  bool        owned = false, has_gid = false;
+  int64_t     Lo = 0, Lg = 0;                         // own markers, ghost markers held
+  int         ncopy = 0;                              // copies of own markers held by other ranks
+  RouteP      R;
+  int         peer[27], scnt[27], soff[27], gcnt[27], goff[27];  // per offset code: rank behind it (-1 none), copies sent / ghosts held and where they start
+  int64_t    *gid_own = nullptr, *gid = nullptr;      // the caller's marker numbers: of the own markers (kept for update), of own + ghost (sort key)
+  int        *mask = nullptr, *sendlist = nullptr, *cstart = nullptr, *clist = nullptr;
+  int64_t     maskcap = 0;
+  double     *sbuf = nullptr, *rbuf = nullptr, *Ui = nullptr, *Fi = nullptr, *cbuf = nullptr;  // message records out / in, U and (F, dV) of own + ghost, counts
+  int64_t     sbufcap = 0, rbufcap = 0, Uicap = 0, Ficap = 0;
 };
 
 static int ibm_rebin(fl_ibm *m)
@@ -297,6 +452,8 @@ static int ibm_rebin(fl_ibm *m)
   fl_poisson *h = m->gp;
   hipStream_t s = h->stream;
   const IbmP &P = m->P;
+  m->nactive    = 0;
+  if (P.L == 0) return 0;  // a rank that owns no marker and holds no ghost
   const int   nb = (int)((P.L + 255) / 256);
   hipLaunchKernelGGL(k_ibm_weights, dim3(nb), dim3(256), 0, s, P, m->X, m->Y, m->Z, m->i0, m->w);
   FL_HIP(hipMemsetAsync(m->cnt, 0, sizeof(int) * (m->ntiles + 1), s));
@@ -309,24 +466,60 @@ static int ibm_rebin(fl_ibm *m)
   FL_HIP(hipMemcpyAsync(&m->nactive, m->nact_dev, sizeof(int), hipMemcpyDeviceToHost, s));
   FL_HIP(hipStreamSynchronize(s));  // set-up time only (create / marker update), never inside interp / spread
   // sort only the non-empty bins (ascending marker id -> run-independent accumulation order)
-  if (m->nactive > 0) hipLaunchKernelGGL(k_ibm_sort_bins, dim3(m->nactive), dim3(256), 0, s, m->off, m->list, m->scratch, m->active);
+  if (m->nactive > 0) hipLaunchKernelGGL(k_ibm_sort_bins, dim3(m->nactive), dim3(256), 0, s, m->off, m->list, m->scratch, m->active, (const int64_t *)(m->has_gid ? m->gid : nullptr));
   FL_HIP(hipGetLastError());
   return 0;
 }
 
-extern "C" int fl_ibm_create(fl_poisson *h, int kind, int64_t L, const double *X, const double *Y, const double *Z, fl_ibm **out)
+static void ibm_free(fl_poisson *h, void *pp)
 {
-  if (!h || !X || !Y || !Z || !out) return FL_ERR_ARG_NULL;
-  if (kind != FL_DELTA_PESKIN4 && kind != FL_DELTA_ROMA3) return FL_ERR_ARG_OUTOFRANGE;
-  if (L < 1 || L > (int64_t)1 << 27) return FL_ERR_ARG_OUTOFRANGE;
-  *out = nullptr;
-  FL_HIP(hipSetDevice(h->device));
-  fl_ibm *m = new fl_ibm();
-  m->gp     = h;
-  IbmP &P   = m->P;
-  P.kind    = kind;
-  P.S       = kind == FL_DELTA_PESKIN4 ? 4 : 3;
-  P.L       = L;
+  void **p = (void **)pp;
+  if (*p) {
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(*p);
+  }
+  *p = nullptr;
+}
+
+// the per-marker arrays for L markers (own + ghost of an owner-rank set: the number changes with every update)
+static int ibm_alloc_markers(fl_ibm *m, int64_t L)
+{
+  fl_poisson *h = m->gp;
+  if (L <= m->cap) return 0;
+  for (void *p : {(void *)&m->X, (void *)&m->Y, (void *)&m->Z, (void *)&m->w, (void *)&m->i0, (void *)&m->list, (void *)&m->scratch, (void *)&m->gid}) ibm_free(h, p);
+  m->listcap = (int)std::min<int64_t>(L * 27, (int64_t)1 << 30);
+  int rc     = 0;
+  rc |= fl_dev_alloc(h, (void **)&m->X, sizeof(double) * L, false);
+  rc |= fl_dev_alloc(h, (void **)&m->Y, sizeof(double) * L, false);
+  rc |= fl_dev_alloc(h, (void **)&m->Z, sizeof(double) * L, false);
+  rc |= fl_dev_alloc(h, (void **)&m->w, sizeof(double) * 12 * L, false);
+  rc |= fl_dev_alloc(h, (void **)&m->i0, sizeof(int) * 3 * L, false);
+  rc |= fl_dev_alloc(h, (void **)&m->list, sizeof(int) * m->listcap, true);
+  rc |= fl_dev_alloc(h, (void **)&m->scratch, sizeof(int) * m->listcap, true);
+  if (m->owned) rc |= fl_dev_alloc(h, (void **)&m->gid, sizeof(int64_t) * L, true);
+  if (rc) return FL_ERR_MEM;
+  m->cap = L;
+  return 0;
+}
+
+// a buffer of at least `need` elements (grown, never shrunk; the old contents are not kept)
+template <class T>
+static int ibm_reserve(fl_poisson *h, T **p, int64_t *cap, int64_t need)
+{
+  if (*p && need <= *cap) return 0;
+  ibm_free(h, p);
+  need = std::max<int64_t>(need + need / 4, 64);
+  if (fl_dev_alloc(h, (void **)p, sizeof(T) * (size_t)need, true)) return FL_ERR_MEM;
+  *cap = need;
+  return 0;
+}
+
+// grid, block and delta function of a marker set; xcg[d] receives the device copy of a stretched axis' centres (the caller frees it)
+static int ibm_geometry(fl_poisson *h, int kind, IbmP &P, double *xcg[3])
+{
+  P.kind = kind;
+  P.S    = kind == FL_DELTA_PESKIN4 ? 4 : 3;
+  P.L    = 0;
   for (int d = 0; d < 3; ++d) {
     const Axis &A = h->ax[d];
     P.n[d]        = (int)h->dec.len[d];
@@ -348,33 +541,50 @@ extern "C" int fl_ibm_create(fl_poisson *h, int kind, int64_t L, const double *X
         xc[0]                  = 2. * A.xf[0] - A.xcc(0);
         xc[(size_t)A.n + 1]    = 2. * A.xf[A.n] - A.xcc(A.n - 1);
       }
-      if (hipMalloc((void **)&m->xcg[d], sizeof(double) * xc.size()) != hipSuccess || hipMemcpy(m->xcg[d], xc.data(), sizeof(double) * xc.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        fl_ibm_destroy(m);
-        return FL_ERR_GPU;
-      }
-      P.xcg[d] = m->xcg[d] + 1;
+      if (hipMalloc((void **)&xcg[d], sizeof(double) * xc.size()) != hipSuccess || hipMemcpy(xcg[d], xc.data(), sizeof(double) * xc.size(), hipMemcpyHostToDevice) != hipSuccess) return FL_ERR_GPU;
+      P.xcg[d] = xcg[d] + 1;
     }
-    if (P.periodic[d] && P.ng[d] < 2 * P.S) {
-      fl_ibm_destroy(m);
-      return FL_ERR_ARG_OUTOFRANGE;
-    }
+    if (P.periodic[d] && P.ng[d] < 2 * P.S) return FL_ERR_ARG_OUTOFRANGE;
     P.nt[d] = (P.n[d] + TB - 1) / TB;
   }
-  m->ntiles  = P.nt[0] * P.nt[1] * P.nt[2];
-  m->listcap = (int)std::min<int64_t>(L * 27, (int64_t)1 << 30);
-  int rc     = 0;
-  rc |= fl_dev_alloc(h, (void **)&m->X, sizeof(double) * L, false);
-  rc |= fl_dev_alloc(h, (void **)&m->Y, sizeof(double) * L, false);
-  rc |= fl_dev_alloc(h, (void **)&m->Z, sizeof(double) * L, false);
-  rc |= fl_dev_alloc(h, (void **)&m->w, sizeof(double) * 12 * L, false);
-  rc |= fl_dev_alloc(h, (void **)&m->i0, sizeof(int) * 3 * L, false);
-  rc |= fl_dev_alloc(h, (void **)&m->cnt, sizeof(int) * (m->ntiles + 1), true);
-  rc |= fl_dev_alloc(h, (void **)&m->off, sizeof(int) * (m->ntiles + 1), true);
-  rc |= fl_dev_alloc(h, (void **)&m->list, sizeof(int) * m->listcap, true);
-  rc |= fl_dev_alloc(h, (void **)&m->scratch, sizeof(int) * m->listcap, true);
-  rc |= fl_dev_alloc(h, (void **)&m->active, sizeof(int) * m->ntiles, true);
-  rc |= fl_dev_alloc(h, (void **)&m->nact_dev, sizeof(int), true);
+  return 0;
+}
+
+static int ibm_new(fl_poisson *h, int kind, bool owned, fl_ibm **out)
+{
+  fl_ibm *m = new fl_ibm();
+  m->gp     = h;
+  m->owned  = owned;
+  int rc    = ibm_geometry(h, kind, m->P, m->xcg);
+  if (!rc) {
+    const IbmP &P = m->P;
+    m->ntiles     = P.nt[0] * P.nt[1] * P.nt[2];
+    int bad       = 0;
+    bad |= fl_dev_alloc(h, (void **)&m->cnt, sizeof(int) * (m->ntiles + 1), true);
+    bad |= fl_dev_alloc(h, (void **)&m->off, sizeof(int) * (m->ntiles + 1), true);
+    bad |= fl_dev_alloc(h, (void **)&m->active, sizeof(int) * m->ntiles, true);
+    bad |= fl_dev_alloc(h, (void **)&m->nact_dev, sizeof(int), true);
+    if (bad) rc = FL_ERR_MEM;
+  }
   if (rc) {
+    fl_ibm_destroy(m);
+    return rc;
+  }
+  *out = m;
+  return 0;
+}
+
+extern "C" int fl_ibm_create(fl_poisson *h, int kind, int64_t L, const double *X, const double *Y, const double *Z, fl_ibm **out)
+{
+  if (!h || !X || !Y || !Z || !out) return FL_ERR_ARG_NULL;
+  if (kind != FL_DELTA_PESKIN4 && kind != FL_DELTA_ROMA3) return FL_ERR_ARG_OUTOFRANGE;
+  if (L < 1 || L > (int64_t)1 << 27) return FL_ERR_ARG_OUTOFRANGE;
+  *out = nullptr;
+  FL_HIP(hipSetDevice(h->device));
+  fl_ibm *m = nullptr;
+  FL_CHK(ibm_new(h, kind, false, &m));
+  m->P.L = L;
+  if (ibm_alloc_markers(m, L)) {
     fl_ibm_destroy(m);
     return FL_ERR_MEM;
   }
@@ -382,10 +592,246 @@ extern "C" int fl_ibm_create(fl_poisson *h, int kind, int64_t L, const double *X
   return fl_ibm_update(m, X, Y, Z);
 }
 
+// ---- owner-rank markers: routing (set-up time: host waits as in ibm_rebin) -----------------------------------------------------------
+
+static bool ibm_split(const fl_poisson *h) { return h->dec.ranks[0] * h->dec.ranks[1] * h->dec.ranks[2] > 1; }
+
+// sum of n <= 8 flags over the ranks: every rank takes the same way out of a collective call
+static int ibm_vote(fl_poisson *h, double *v, int n)
+{
+  if (!ibm_split(h)) return 0;
+  if (h->comm.kind == Comm::NONE) return FL_ERR_ARG_WRONGSTATE;
+  return fl_poisson_allreduce_sum(h, v, n);
+}
+
+// the masks of k_ibm_route for L markers at (X, Y, Z), on the host
+static int ibm_masks(fl_ibm *m, const RouteP &R, int64_t L, const double *X, const double *Y, const double *Z, std::vector<int> &host)
+{
+  fl_poisson *h = m->gp;
+  host.assign((size_t)L, 0);
+  if (L == 0) return 0;
+  FL_CHK(ibm_reserve(h, &m->mask, &m->maskcap, L));
+  IbmP P = m->P;
+  P.L    = L;
+  hipLaunchKernelGGL(k_ibm_route, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, h->stream, P, R, X, Y, Z, m->mask);
+  FL_HIP(hipGetLastError());
+  FL_HIP(hipMemcpyAsync(host.data(), m->mask, sizeof(int) * (size_t)L, hipMemcpyDeviceToHost, h->stream));
+  FL_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// The messages of one exchange between owners and ghost holders.  to_ghosts: the owners send (spread, positions), else the ghost holders
+// do (interp).  per = doubles per copy.  Sends in ascending offset code; receives in the order the peer sends, which is DESCENDING code
+// here (the peer numbers the same pair of blocks 26 - code): RCCL matches the messages between two ranks by order, and two offsets may
+// lead to the same rank (two ranks on a periodic axis) -- fl_halo_plan's rule.  Empty messages are left out: both sides know every count.
+static void ibm_msgs(const fl_ibm *m, bool to_ghosts, int per, double *sbuf, double *rbuf, std::vector<Msg> &msgs)
+{
+  const int *sc = to_ghosts ? m->scnt : m->gcnt, *so = to_ghosts ? m->soff : m->goff;
+  const int *rc = to_ghosts ? m->gcnt : m->scnt, *ro = to_ghosts ? m->goff : m->soff;
+  msgs.clear();
+  for (int code = 0; code < 27; ++code)
+    if (m->peer[code] >= 0 && sc[code] > 0) msgs.push_back({m->peer[code], sbuf + (int64_t)per * so[code], nullptr, (int64_t)per * sc[code], code, 26 - code});
+  for (int code = 26; code >= 0; --code)
+    if (m->peer[code] >= 0 && rc[code] > 0) msgs.push_back({m->peer[code], nullptr, rbuf + (int64_t)per * ro[code], (int64_t)per * rc[code], code, 26 - code});
+}
+
+// own markers (Lo of them, the caller's device arrays) -> ghost copies on the neighbours, marker arrays of own + ghost, bins.  Collective.
+static int ibm_route(fl_ibm *m, int64_t Lo, const double *X, const double *Y, const double *Z, const int64_t *gid_new, bool first)
+{
+  fl_poisson *h = m->gp;
+  hipStream_t s = h->stream;
+  const IbmP &P = m->P;
+  const bool  split = ibm_split(h);
+  // which offsets have a rank behind them
+  RouteP R;
+  int    periodic[3];
+  for (int d = 0; d < 3; ++d) {
+    periodic[d]  = P.periodic[d];
+    const bool sp = h->dec.ranks[d] > 1;
+    R.peer_lo[d] = sp && (h->dec.coord[d] > 0 || P.periodic[d]);
+    R.peer_hi[d] = sp && (h->dec.coord[d] < h->dec.ranks[d] - 1 || P.periodic[d]);
+  }
+  int peer[27];
+  for (int code = 0; code < 27; ++code) {
+    const int o[3] = {code % 3 - 1, (code / 3) % 3 - 1, code / 9 - 1};
+    bool      ok   = code != 13;
+    for (int d = 0; d < 3; ++d) ok = ok && (o[d] == 0 || (o[d] < 0 ? R.peer_lo[d] : R.peer_hi[d]));
+    peer[code] = ok ? fl_decomp_neighbor_offset(&h->dec, periodic, o) : -1;
+  }
+  // every marker in its owner's block, every split axis >= 4 cells long: or every rank leaves here with the same error
+  std::vector<int> mask;
+  FL_CHK(ibm_masks(m, R, Lo, X, Y, Z, mask));
+  double vote[3] = {0., gid_new ? 1. : 0., (!gid_new && Lo > 0) ? 1. : 0.};
+  for (int64_t l = 0; l < Lo; ++l)
+    if (mask[(size_t)l] < 0) vote[0] = 1.;
+  for (int d = 0; d < 3; ++d)
+    if (h->dec.ranks[d] > 1 && P.n[d] < 4) vote[0] = 1.;
+  if (!first) vote[1] = vote[2] = 0.;  // update keeps the numbers given at create
+  FL_CHK(ibm_vote(h, vote, 3));
+  if (vote[0] > 0.) return FL_ERR_ARG_OUTOFRANGE;
+  if (first) {
+    if (vote[1] > 0. && vote[2] > 0.) return FL_ERR_ARG_WRONG;  // marker numbers on some ranks only
+    m->has_gid = vote[1] > 0.;
+  }
+  // send list: the own markers of every offset in ascending local order, offsets in ascending code; per marker the copies it has
+  std::vector<int> sendlist, cstart((size_t)Lo + 1, 0), clist;
+  for (int code = 0; code < 27; ++code) {
+    m->peer[code] = peer[code];
+    m->soff[code] = (int)sendlist.size();
+    if (peer[code] >= 0)
+      for (int64_t l = 0; l < Lo; ++l)
+        if (mask[(size_t)l] >> code & 1) {
+          sendlist.push_back((int)l);
+          cstart[(size_t)l + 1]++;
+        }
+    m->scnt[code] = (int)sendlist.size() - m->soff[code];
+    m->gcnt[code] = m->goff[code] = 0;
+  }
+  const int ncopy = (int)sendlist.size();
+  for (int64_t l = 0; l < Lo; ++l) cstart[(size_t)l + 1] += cstart[(size_t)l];
+  clist.resize((size_t)ncopy);
+  {
+    std::vector<int> cur(cstart.begin(), cstart.end() - 1);
+    for (int j = 0; j < ncopy; ++j) clist[(size_t)cur[(size_t)sendlist[(size_t)j]]++] = j;  // ascending j per marker
+  }
+  m->Lo    = Lo;
+  m->ncopy = ncopy;
+  m->R     = R;
+  ibm_free(h, &m->sendlist);
+  ibm_free(h, &m->cstart);
+  ibm_free(h, &m->clist);
+  if (fl_dev_alloc(h, (void **)&m->sendlist, sizeof(int) * (size_t)ncopy, false) || fl_dev_alloc(h, (void **)&m->cstart, sizeof(int) * ((size_t)Lo + 1), false) || fl_dev_alloc(h, (void **)&m->clist, sizeof(int) * (size_t)ncopy, false))
+    return FL_ERR_MEM;
+  if (ncopy) FL_HIP(hipMemcpyAsync(m->sendlist, sendlist.data(), sizeof(int) * (size_t)ncopy, hipMemcpyHostToDevice, s));
+  if (ncopy) FL_HIP(hipMemcpyAsync(m->clist, clist.data(), sizeof(int) * (size_t)ncopy, hipMemcpyHostToDevice, s));
+  FL_HIP(hipMemcpyAsync(m->cstart, cstart.data(), sizeof(int) * ((size_t)Lo + 1), hipMemcpyHostToDevice, s));
+  if (first && m->has_gid && Lo > 0) {
+    if (fl_dev_alloc(h, (void **)&m->gid_own, sizeof(int64_t) * (size_t)Lo, false)) return FL_ERR_MEM;
+    FL_HIP(hipMemcpyAsync(m->gid_own, gid_new, sizeof(int64_t) * (size_t)Lo, hipMemcpyDeviceToDevice, s));
+  }
+  // the counts of the copies, one double per offset that has a rank behind it
+  int64_t Lg = 0;
+  if (split) {
+    if (!m->cbuf && fl_dev_alloc(h, (void **)&m->cbuf, sizeof(double) * 54, true)) return FL_ERR_MEM;
+    double hc[54];
+    for (int code = 0; code < 27; ++code) hc[code] = (double)m->scnt[code], hc[27 + code] = 0.;
+    FL_HIP(hipMemcpyAsync(m->cbuf, hc, sizeof(hc), hipMemcpyHostToDevice, s));
+    std::vector<Msg> msgs;
+    for (int code = 0; code < 27; ++code)
+      if (peer[code] >= 0) msgs.push_back({peer[code], m->cbuf + code, nullptr, 1, code, 26 - code});
+    for (int code = 26; code >= 0; --code)
+      if (peer[code] >= 0) msgs.push_back({peer[code], nullptr, m->cbuf + 27 + code, 1, code, 26 - code});
+    FL_CHK(h->comm.exchange(s, msgs));
+    FL_HIP(hipMemcpyAsync(hc, m->cbuf, sizeof(hc), hipMemcpyDeviceToHost, s));
+    FL_HIP(hipStreamSynchronize(s));  // the sendlist vectors above are still alive here
+    for (int code = 0; code < 27; ++code) {
+      m->goff[code] = (int)Lg;
+      m->gcnt[code] = peer[code] >= 0 ? (int)hc[27 + code] : 0;
+      Lg += m->gcnt[code];
+    }
+  } else FL_HIP(hipStreamSynchronize(s));
+  m->Lg             = Lg;
+  const int64_t Lt = Lo + Lg;
+  if (Lt > (int64_t)1 << 27) return FL_ERR_ARG_OUTOFRANGE;
+  m->P.L = Lt;
+  FL_CHK(ibm_alloc_markers(m, Lt));
+  if (Lo > 0) {
+    FL_HIP(hipMemcpyAsync(m->X, X, sizeof(double) * (size_t)Lo, hipMemcpyDeviceToDevice, s));
+    FL_HIP(hipMemcpyAsync(m->Y, Y, sizeof(double) * (size_t)Lo, hipMemcpyDeviceToDevice, s));
+    FL_HIP(hipMemcpyAsync(m->Z, Z, sizeof(double) * (size_t)Lo, hipMemcpyDeviceToDevice, s));
+    if (m->has_gid) FL_HIP(hipMemcpyAsync(m->gid, m->gid_own, sizeof(int64_t) * (size_t)Lo, hipMemcpyDeviceToDevice, s));
+  }
+  // positions (and numbers) of the copies
+  if (ncopy > 0 || Lg > 0) {
+    FL_CHK(ibm_reserve(h, &m->sbuf, &m->sbufcap, 4 * (int64_t)ncopy));
+    FL_CHK(ibm_reserve(h, &m->rbuf, &m->rbufcap, 4 * Lg));
+    if (ncopy > 0) hipLaunchKernelGGL(k_ibm_pack_pos, dim3((ncopy + 255) / 256), dim3(256), 0, s, ncopy, m->sendlist, m->X, m->Y, m->Z, (const int64_t *)(m->has_gid ? m->gid : nullptr), m->sbuf);
+    std::vector<Msg> msgs;
+    ibm_msgs(m, true, 4, m->sbuf, m->rbuf, msgs);
+    FL_CHK(h->comm.exchange(s, msgs));
+    if (Lg > 0) hipLaunchKernelGGL(k_ibm_unpack_pos, dim3((unsigned)((Lg + 255) / 256)), dim3(256), 0, s, (int)Lg, Lo, m->rbuf, m->X, m->Y, m->Z, m->has_gid ? m->gid : nullptr);
+    FL_HIP(hipGetLastError());
+  }
+  return ibm_rebin(m);
+}
+
+extern "C" int fl_ibm_owned_select(fl_poisson *h, int kind, int64_t L, const double *X, const double *Y, const double *Z, int64_t *idx_out_dev, int64_t *count_out)
+{
+  if (!h || !X || !Y || !Z || !idx_out_dev || !count_out) return FL_ERR_ARG_NULL;
+  if (kind != FL_DELTA_PESKIN4 && kind != FL_DELTA_ROMA3) return FL_ERR_ARG_OUTOFRANGE;
+  if (L < 1 || L > (int64_t)1 << 27) return FL_ERR_ARG_OUTOFRANGE;
+  FL_HIP(hipSetDevice(h->device));
+  fl_ibm m;  // geometry and the mask buffer only
+  m.gp   = h;
+  int rc = ibm_geometry(h, kind, m.P, m.xcg);
+  std::vector<int>     mask;
+  std::vector<int64_t> idx;
+  const RouteP         none = {{0, 0, 0}, {0, 0, 0}};
+  if (!rc) rc = ibm_masks(&m, none, L, X, Y, Z, mask);
+  if (!rc) {
+    for (int64_t l = 0; l < L; ++l)
+      if (mask[(size_t)l] >= 0) idx.push_back(l);
+    if (!idx.empty() && hipMemcpyAsync(idx_out_dev, idx.data(), sizeof(int64_t) * idx.size(), hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = FL_ERR_GPU;
+    if (hipStreamSynchronize(h->stream) != hipSuccess) rc = FL_ERR_GPU;
+    *count_out = (int64_t)idx.size();
+  }
+  for (void *p : {(void *)m.mask, (void *)m.xcg[0], (void *)m.xcg[1], (void *)m.xcg[2]})
+    if (p) (void)hipFree(p);
+  return rc;
+}
+
+extern "C" int fl_ibm_create_owned(fl_poisson *h, int kind, int64_t L_local, const double *X, const double *Y, const double *Z, const int64_t *gid_dev, fl_ibm **out)
+{
+  if (!h || !out) return FL_ERR_ARG_NULL;
+  *out = nullptr;
+  // argument errors of one rank are voted like a misplaced marker: the others must not wait in an exchange this rank never enters
+  int bad = 0;
+  if (L_local > 0 && (!X || !Y || !Z)) bad = FL_ERR_ARG_NULL;
+  if (kind != FL_DELTA_PESKIN4 && kind != FL_DELTA_ROMA3) bad = FL_ERR_ARG_OUTOFRANGE;
+  if (L_local < 0 || L_local > (int64_t)1 << 27) bad = FL_ERR_ARG_OUTOFRANGE;
+  FL_HIP(hipSetDevice(h->device));
+  fl_ibm *m = nullptr;
+  if (!bad) bad = ibm_new(h, kind, true, &m);
+  double v = bad ? 1. : 0.;
+  const int vrc = ibm_vote(h, &v, 1);
+  if (vrc || v > 0.) {
+    if (m) fl_ibm_destroy(m);
+    return vrc ? vrc : (bad ? bad : FL_ERR_ARG_OUTOFRANGE);
+  }
+  const int rc = ibm_route(m, L_local, X, Y, Z, L_local > 0 ? gid_dev : nullptr, true);
+  if (rc) {
+    fl_ibm_destroy(m);
+    return rc;
+  }
+  *out = m;
+  return FL_SUCCESS;
+}
+
+extern "C" int fl_ibm_owned_counts(fl_ibm *m, int64_t out[5])
+{
+  if (!m || !out) return FL_ERR_ARG_NULL;
+  if (!m->owned) return FL_ERR_ARG_WRONGSTATE;
+  out[0] = m->Lo;
+  out[1] = m->Lg;
+  out[2] = m->ncopy;
+  out[3] = 8 * m->Lg;                   // interp: one double per ghost and component back to its owner
+  out[4] = 32 * (int64_t)m->ncopy;      // spread of three components: (F_0, F_1, F_2, dV) per copy
+  return FL_SUCCESS;
+}
+
 extern "C" int fl_ibm_update(fl_ibm *m, const double *X, const double *Y, const double *Z)
 {
-  if (!m || !X || !Y || !Z) return FL_ERR_ARG_NULL;
+  if (!m) return FL_ERR_ARG_NULL;
   fl_poisson *h = m->gp;
+  if (m->owned) {
+    FL_HIP(hipSetDevice(h->device));
+    double    v   = (m->Lo > 0 && (!X || !Y || !Z)) ? 1. : 0.;
+    const int vrc = ibm_vote(h, &v, 1);
+    if (vrc) return vrc;
+    if (v > 0.) return (m->Lo > 0 && (!X || !Y || !Z)) ? FL_ERR_ARG_NULL : FL_ERR_ARG_OUTOFRANGE;
+    return ibm_route(m, m->Lo, X, Y, Z, nullptr, false);
+  }
+  if (!X || !Y || !Z) return FL_ERR_ARG_NULL;
   FL_HIP(hipSetDevice(h->device));
   FL_HIP(hipMemcpyAsync(m->X, X, sizeof(double) * m->P.L, hipMemcpyDeviceToDevice, h->stream));
   FL_HIP(hipMemcpyAsync(m->Y, Y, sizeof(double) * m->P.L, hipMemcpyDeviceToDevice, h->stream));
@@ -393,12 +839,64 @@ extern "C" int fl_ibm_update(fl_ibm *m, const double *X, const double *Y, const 
   return ibm_rebin(m);
 }
 
+// ---- owner-rank markers: per call (stream-ordered; the host waits only where the host transport itself does) ---------------------------
+
+static int ibm_interp_owned(fl_ibm *m, int ncomp, const double *u, double *U)
+{
+  fl_poisson   *h  = m->gp;
+  hipStream_t   s  = h->stream;
+  const int64_t Lo = m->Lo, Lg = m->Lg, Lt = Lo + Lg;
+  if (Lo > 0 && !U) return FL_ERR_ARG_NULL;
+  if (Lt == 0) return FL_SUCCESS;
+  FL_CHK(ibm_reserve(h, &m->Ui, &m->Uicap, (int64_t)ncomp * Lt));
+  FL_CHK(ibm_reserve(h, &m->sbuf, &m->sbufcap, (int64_t)ncomp * Lg));
+  FL_CHK(ibm_reserve(h, &m->rbuf, &m->rbufcap, (int64_t)ncomp * m->ncopy));
+  hipLaunchKernelGGL(k_ibm_interp, dim3((unsigned)((Lt + 3) / 4)), dim3(256), 0, s, m->P, m->i0, m->w, ncomp, h->ncell, u, m->Ui);
+  if (Lg > 0) hipLaunchKernelGGL(k_ibm_pack_U, dim3((unsigned)((Lg + 255) / 256)), dim3(256), 0, s, (int)Lg, Lo, Lt, ncomp, m->Ui, m->sbuf);
+  FL_HIP(hipGetLastError());
+  if (Lg > 0 || m->ncopy > 0) {
+    std::vector<Msg> msgs;
+    ibm_msgs(m, false, ncomp, m->sbuf, m->rbuf, msgs);
+    FL_CHK(h->comm.exchange(s, msgs));
+  }
+  if (Lo > 0) hipLaunchKernelGGL(k_ibm_collect_U, dim3((unsigned)((Lo + 255) / 256)), dim3(256), 0, s, Lo, Lt, ncomp, m->Ui, m->cstart, m->clist, m->rbuf, U);
+  FL_HIP(hipGetLastError());
+  return FL_SUCCESS;
+}
+
+static int ibm_spread_owned(fl_ibm *m, int ncomp, const double *F, const double *dV, double *f)
+{
+  fl_poisson   *h  = m->gp;
+  hipStream_t   s  = h->stream;
+  const int64_t Lo = m->Lo, Lg = m->Lg, Lt = Lo + Lg;
+  if (Lo > 0 && (!F || !dV)) return FL_ERR_ARG_NULL;
+  if (Lt == 0) return FL_SUCCESS;
+  const int per = ncomp + 1;
+  FL_CHK(ibm_reserve(h, &m->Fi, &m->Ficap, (int64_t)per * Lt));
+  FL_CHK(ibm_reserve(h, &m->sbuf, &m->sbufcap, (int64_t)per * m->ncopy));
+  FL_CHK(ibm_reserve(h, &m->rbuf, &m->rbufcap, (int64_t)per * Lg));
+  if (m->ncopy > 0) hipLaunchKernelGGL(k_ibm_pack_F, dim3((m->ncopy + 255) / 256), dim3(256), 0, s, m->ncopy, Lo, ncomp, m->sendlist, F, dV, m->sbuf);
+  FL_HIP(hipGetLastError());
+  if (Lg > 0 || m->ncopy > 0) {
+    std::vector<Msg> msgs;
+    ibm_msgs(m, true, per, m->sbuf, m->rbuf, msgs);
+    FL_CHK(h->comm.exchange(s, msgs));
+  }
+  double *Fi = m->Fi, *dVi = m->Fi + (int64_t)ncomp * Lt;
+  hipLaunchKernelGGL(k_ibm_stage_F, dim3((unsigned)((Lt + 255) / 256)), dim3(256), 0, s, Lo, Lt, ncomp, F, dV, m->rbuf, Fi, dVi);
+  if (m->nactive > 0) hipLaunchKernelGGL(k_ibm_spread, dim3(m->nactive), dim3(256), 0, s, m->P, m->i0, m->w, m->off, m->list, m->active, ncomp, h->ncell, Fi, dVi, f);
+  FL_HIP(hipGetLastError());
+  return FL_SUCCESS;
+}
+
 extern "C" int fl_ibm_interp(fl_ibm *m, int ncomp, const double *u, double *U)
 {
-  if (!m || !u || !U) return FL_ERR_ARG_NULL;
+  if (!m || !u) return FL_ERR_ARG_NULL;
   if (ncomp < 1) return FL_ERR_ARG_OUTOFRANGE;
   fl_poisson *h = m->gp;
   FL_HIP(hipSetDevice(h->device));
+  if (m->owned) return ibm_interp_owned(m, ncomp, u, U);
+  if (!U) return FL_ERR_ARG_NULL;
   hipLaunchKernelGGL(k_ibm_interp, dim3((unsigned)((m->P.L + 3) / 4)), dim3(256), 0, h->stream, m->P, m->i0, m->w, ncomp, h->ncell, u, U);
   FL_HIP(hipGetLastError());
   // multi-rank: every rank summed over the support cells it owns; the marker value is the sum over ranks
@@ -411,10 +909,12 @@ extern "C" int fl_ibm_interp(fl_ibm *m, int ncomp, const double *u, double *U)
 
 extern "C" int fl_ibm_spread(fl_ibm *m, int ncomp, const double *F, const double *dV, double *f)
 {
-  if (!m || !F || !dV || !f) return FL_ERR_ARG_NULL;
+  if (!m || !f) return FL_ERR_ARG_NULL;
   if (ncomp < 1 || ncomp > 3) return FL_ERR_ARG_OUTOFRANGE;
   fl_poisson *h = m->gp;
   FL_HIP(hipSetDevice(h->device));
+  if (m->owned) return ibm_spread_owned(m, ncomp, F, dV, f);
+  if (!F || !dV) return FL_ERR_ARG_NULL;
   if (m->nactive > 0) hipLaunchKernelGGL(k_ibm_spread, dim3(m->nactive), dim3(256), 0, h->stream, m->P, m->i0, m->w, m->off, m->list, m->active, ncomp, h->ncell, F, dV, f);
   FL_HIP(hipGetLastError());
   return FL_SUCCESS;
@@ -425,7 +925,8 @@ extern "C" int fl_ibm_destroy(fl_ibm *m)
   if (!m) return FL_SUCCESS;
   if (m->gp) (void)hipStreamSynchronize(m->gp->stream);
   for (void *p : {(void *)m->X, (void *)m->Y, (void *)m->Z, (void *)m->w, (void *)m->i0, (void *)m->cnt, (void *)m->off, (void *)m->list, (void *)m->scratch, (void *)m->active, (void *)m->nact_dev, (void *)m->xcg[0],
-                  (void *)m->xcg[1], (void *)m->xcg[2]})
+                  (void *)m->xcg[1], (void *)m->xcg[2], (void *)m->gid_own, (void *)m->gid, (void *)m->mask, (void *)m->sendlist, (void *)m->cstart, (void *)m->clist, (void *)m->sbuf, (void *)m->rbuf, (void *)m->Ui,
+                  (void *)m->Fi, (void *)m->cbuf})
     if (p) (void)hipFree(p);
   delete m;
   return FL_SUCCESS;

@@ -861,6 +861,14 @@ FlErrorCode NSSetFromOptions(NS ns, int argc, char **argv)
     if (got < 0) return E_ARG_WRONG;
     if (got) ns->bc_keep = flg;
   }
+  /* mirror only: how NSSetImmersedBoundary holds the markers on several ranks.  replicated (default): every rank keeps all of them, the
+   * interpolation ends in an all-reduce.  owner: every rank keeps the markers of its block and ghost copies of its neighbours' (fl_ibm_create_owned).
+   * A user's choice for now: which one is faster is decided by the latency between GPUs, and nothing has been measured on two GPUs yet. */
+  if ((s = opt_find(argc, argv, "-ns_ibm_marker_distribution"))) {
+    if (!strcmp(s, "replicated")) ns->ibm_owner = 0;
+    else if (!strcmp(s, "owner")) ns->ibm_owner = 1;
+    else return E_ARG_UNKNOWN_TYPE;
+  }
   /* sub-KSP of the Schur complement: prefix ns_ + abf_schur_ (nssol.c:19, abfpc.c:206) */
   if ((s = opt_find(argc, argv, "-ns_abf_schur_ksp_type"))) {
     if (!strcmp(s, "cg")) ns->schur.type = FL_KSP_CG;
@@ -1277,6 +1285,8 @@ FlErrorCode NSGetTime(NS ns, double *t)
   return 0;
 }
 
+static void ibm_free_own(NS ns);
+
 FlErrorCode NSDestroy(NS *ns)
 {
   if (!ns || !*ns) return 0;
@@ -1284,6 +1294,7 @@ FlErrorCode NSDestroy(NS *ns)
   if ((*ns)->ops->destroy) (*ns)->ops->destroy(*ns);
   if ((*ns)->ibm) fl_ibm_destroy((*ns)->ibm);
   if ((*ns)->ibm_U) fl_free((*ns)->device, (*ns)->ibm_U);
+  ibm_free_own(*ns);
   if ((*ns)->momentum) fl_momentum_destroy((*ns)->momentum);
   if ((*ns)->poisson) fl_poisson_destroy((*ns)->poisson);
   free((*ns)->bcs);
@@ -1341,6 +1352,49 @@ FlErrorCode NSPressureCorrection(NS ns, double *vstar[3], double *Vstar[3], cons
  * every step adds  spread(U_target - interp(v0))  to momrhs, i.e. the force density (U_target - U)/dt that would bring the
  * interpolated marker velocity to its target within the step, times dt.  Markers / volumes / targets are device arrays
  * owned by the caller; Utarget_dev may be NULL (body at rest). */
+static void ibm_free_own(NS ns)
+{
+  for (int q = 0; q < 6; ++q) {
+    if (ns->ibm_own[q]) fl_free(ns->device, ns->ibm_own[q]);
+    ns->ibm_own[q] = NULL;
+  }
+}
+
+/* -ns_ibm_marker_distribution owner: this rank's share of the replicated arrays, gathered into arrays the NS owns -- ibm_own[0..2] positions, [3] volumes,
+ * [4] targets (3 x Lloc, or NULL), [5] the global marker numbers.  Set-up time: through the host. */
+static FlErrorCode ibm_gather_own(NS ns, int kind, int64_t L, const double *const src[5], int64_t *Lloc)
+{
+  void    *idx_dev = NULL;
+  int64_t  n = 0, *idx = NULL;
+  double  *in = NULL, *out = NULL;
+  int      rc = fl_malloc(ns->device, sizeof(int64_t) * (size_t)L, &idx_dev);
+  if (!rc) rc = fl_ibm_owned_select(ns->poisson, kind, L, src[0], src[1], src[2], (int64_t *)idx_dev, &n);
+  if (!rc) {
+    idx = (int64_t *)malloc(sizeof(int64_t) * (size_t)(n + 1));
+    in  = (double *)malloc(sizeof(double) * 3 * (size_t)L);
+    out = (double *)malloc(sizeof(double) * 3 * (size_t)(n + 1));
+    if (!idx || !in || !out) rc = -E_MEM;
+  }
+  if (!rc && n > 0) rc = fl_memcpy_d2h(ns->device, idx, idx_dev, sizeof(int64_t) * (size_t)n);
+  for (int q = 0; q < 5 && !rc; ++q) {
+    if (!src[q]) continue;
+    const int ncomp = q == 4 ? 3 : 1;
+    rc = fl_memcpy_d2h(ns->device, in, src[q], sizeof(double) * (size_t)(ncomp * L));
+    for (int c = 0; c < ncomp; ++c)
+      for (int64_t a = 0; a < n; ++a) out[c * n + a] = in[c * L + idx[a]];
+    if (!rc) rc = fl_malloc(ns->device, sizeof(double) * (size_t)(ncomp * n + 1), &ns->ibm_own[q]);
+    if (!rc && n > 0) rc = fl_memcpy_h2d(ns->device, ns->ibm_own[q], out, sizeof(double) * (size_t)(ncomp * n));
+  }
+  if (!rc) rc = fl_malloc(ns->device, sizeof(int64_t) * (size_t)(n + 1), &ns->ibm_own[5]);
+  if (!rc && n > 0) rc = fl_memcpy_h2d(ns->device, ns->ibm_own[5], idx, sizeof(int64_t) * (size_t)n);
+  free(idx);
+  free(in);
+  free(out);
+  if (idx_dev) fl_free(ns->device, idx_dev);
+  *Lloc = n;
+  return rc ? -rc : 0;
+}
+
 FlErrorCode NSSetImmersedBoundary(NS ns, int kind, int64_t L, const double *X_dev, const double *Y_dev, const double *Z_dev, const double *dV_dev, const double *Utarget_dev)
 {
   if (!ns || !X_dev || !Y_dev || !Z_dev || !dV_dev) return E_ARG_NULL;
@@ -1352,8 +1406,23 @@ FlErrorCode NSSetImmersedBoundary(NS ns, int kind, int64_t L, const double *X_de
   }
   if (ns->ibm_U) fl_free(ns->device, ns->ibm_U);
   ns->ibm_U = NULL;
-  FLABI(fl_ibm_create(ns->poisson, kind, L, X_dev, Y_dev, Z_dev, &ns->ibm));
+  ibm_free_own(ns);
   void *u = NULL;
+  if (ns->ibm_owner) {
+    /* the caller still hands over the replicated arrays; every rank keeps what the ownership rule gives it (the global index is the marker number,
+     * so the forcing adds up in the replicated order) */
+    const double *const src[5] = {X_dev, Y_dev, Z_dev, dV_dev, Utarget_dev};
+    int64_t             Lloc   = 0;
+    FLCHK(ibm_gather_own(ns, kind, L, src, &Lloc));
+    FLABI(fl_ibm_create_owned(ns->poisson, kind, Lloc, (const double *)ns->ibm_own[0], (const double *)ns->ibm_own[1], (const double *)ns->ibm_own[2], (const int64_t *)ns->ibm_own[5], &ns->ibm));
+    FLABI(fl_malloc(ns->device, sizeof(double) * (3 * (size_t)Lloc + 1), &u));
+    ns->ibm_U  = (double *)u;
+    ns->ibm_L  = Lloc;
+    ns->ibm_dV = (const double *)ns->ibm_own[3];
+    ns->ibm_Ut = (const double *)ns->ibm_own[4];
+    return 0;
+  }
+  FLABI(fl_ibm_create(ns->poisson, kind, L, X_dev, Y_dev, Z_dev, &ns->ibm));
   FLABI(fl_malloc(ns->device, sizeof(double) * 3 * (size_t)L, &u));
   ns->ibm_U  = (double *)u;
   ns->ibm_L  = L;

@@ -162,7 +162,7 @@ int fl_poisson_allreduce_sum(fl_poisson *h, double *host_vals, int n);
 int fl_poisson_sizes(const fl_poisson *h, int64_t out[4]);
 void fl_ksp_opts_default(fl_ksp_opts *o); /* PETSc defaults + cg/jacobi/preconditioned norm */
 const char *fl_version(void);
-#define FL_ABI_VERSION 6
+#define FL_ABI_VERSION 7
 int fl_abi_version(void); /* the FL_ABI_VERSION the library was built with */
 
 /* ---- device memory for hosts that have no allocator of their own (the C host mirror, a PETSc host without HIP Vecs) - */
@@ -337,6 +337,9 @@ int fl_halo_plan(const fl_decomp *d, const int periodic[3], fl_halo_msg out[12])
 int fl_decomp_default(const int64_t n[3], const int ranks[3], int rank, fl_decomp *out);
 /* rank of the neighbour across boundary 0..5 of this block, -1 if physical (non-periodic) boundary */
 int fl_decomp_neighbor(const fl_decomp *d, const int periodic[3], int boundary);
+/* the same across an edge or a corner: rank of the block at coord + offset, offset[d] in {-1, 0, 1}; -1 if the offset leaves the rank grid
+ * through a non-periodic end.  A periodic axis wraps, so on an axis one rank holds alone the neighbour is the rank itself. */
+int fl_decomp_neighbor_offset(const fl_decomp *d, const int periodic[3], const int offset[3]);
 
 /* ---- momentum block of the Jacobian (first "next" row) --------------- */
 /* Matrix-free A = I + dt C - (mu dt / 2 rho) L on the cell-centred velocity, replacing the AIJ matrix the reference
@@ -433,6 +436,35 @@ int fl_ibm_interp(fl_ibm *m, int ncomp, const double *u_dev, double *U_dev);
 /* f[c*ncell + x] += sum_l F[c*L + l] delta_h(x - X_l) dV_l */
 int fl_ibm_spread(fl_ibm *m, int ncomp, const double *F_dev, const double *dV_dev, double *f_dev);
 int fl_ibm_destroy(fl_ibm *m);
+
+/* Several ranks.  fl_ibm_create REPLICATES the markers: every rank hands over all L of them, interp ends in an all-reduce of ncomp L doubles.
+ * fl_ibm_create_owned gives every marker to ONE rank -- memory, kernel work and bytes on the wire follow the rank's share:
+ *
+ * The ownership rule: marker l belongs to the rank whose block holds the cell floor(s_d + 1/2) on every axis d, s_d = the continuous
+ * cell-centre index of the marker (stretched axes included), the cell index wrapped on a periodic axis and clamped to [0, n_d - 1]
+ * otherwise.  fl_ibm_owned_select applies it to a replicated list (device arrays of length L): idx_out_dev (device, room for L) receives
+ * the ascending indices of the markers this rank owns, *count_out their number.  Global quantities only: the selections of the ranks are
+ * disjoint and cover the list without any communication.  Not collective; waits for the handle's stream. */
+int fl_ibm_owned_select(fl_poisson *grid_from, int kind, int64_t L, const double *X_dev, const double *Y_dev, const double *Z_dev, int64_t *idx_out_dev, int64_t *count_out);
+/* COLLECTIVE over grid_from's communicator.  X, Y, Z (device, length L_local >= 0): the markers this rank owns; a rank without markers takes
+ * part with L_local = 0 (the pointers may then be NULL).  gid_dev (device, int64, may be NULL): the caller's global marker numbers (< 2^27,
+ * distinct); they fix the order in which a cell adds its markers when spreading, so that the result does not depend on how the markers are shared
+ * out -- with the list index as number, spreading gives the bits of fl_ibm_create.  NULL (on every rank that has markers): own markers in local
+ * order, then the ghosts by neighbour.  Where the support of a marker reaches into a neighbouring block (face, edge or corner), that
+ * neighbour receives a ghost copy of the marker here; no field is ever exchanged.
+ * FL_ERR_ARG_OUTOFRANGE on EVERY rank (voted, nobody waits for a rank that left) if any rank was handed a marker that is not its own by the
+ * rule above, or if a block is shorter than 4 cells along an axis that is split between ranks (with 4 a support reaches one neighbour per
+ * axis at most).  On one rank: the bits of fl_ibm_create.
+ * On such a set fl_ibm_update / fl_ibm_interp / fl_ibm_spread are collective too; L is L_local there (U, F, dV indexed by local marker):
+ *   update  routes the copies anew; a marker that has left the block is the voted FL_ERR_ARG_OUTOFRANGE and the set stays as it was
+ *           (markers do not migrate: re-partition with fl_ibm_owned_select and create a new set)
+ *   interp  own + ghost markers on the owned cells, the ghosts' partial sums go back to the owners (8 bytes per copy and component), which
+ *           add them in a fixed order; no all-reduce
+ *   spread  F and dV of the copies go out (8 (ncomp + 1) bytes per copy), every rank spreads own + ghost markers into its own cells */
+int fl_ibm_create_owned(fl_poisson *grid_from, int kind, int64_t L_local, const double *X_dev, const double *Y_dev, const double *Z_dev, const int64_t *gid_dev, fl_ibm **out);
+/* out = { markers owned, ghost markers held, copies of own markers held by other ranks, bytes this rank sends per interp and component,
+ * bytes this rank sends per spread of three components }.  FL_ERR_ARG_WRONGSTATE on a replicated set. */
+int fl_ibm_owned_counts(fl_ibm *m, int64_t out[5]);
 
 #ifdef __cplusplus
 }

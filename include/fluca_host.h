@@ -221,7 +221,11 @@ FlErrorCode NSPressureCorrection(NS ns, double *vstar_dev[3], double *Vstar_dev[
 FlErrorCode NSSolve(NS ns);
 /* Immersed boundary by explicit direct forcing -- build-defined, the reference has none (THEORY_GUIDE.md:130-132): every
  * step adds spread(U_target - interp(v0)) to momrhs.  kind: fl_delta_kind; L markers X,Y,Z with volumes dV (device arrays
- * owned by the caller, uniform grid spacing required); Utarget_dev: 3*L target velocities or NULL for a body at rest. */
+ * owned by the caller, uniform grid spacing required); Utarget_dev: 3*L target velocities or NULL for a body at rest.
+ * Several ranks: every rank hands over the whole list.  -ns_ibm_marker_distribution replicated (default) keeps it whole on every rank
+ * (fl_ibm_create: interpolation ends in an all-reduce of 3 L doubles); owner keeps on every rank the markers of its block, copied into arrays the
+ * NS owns, plus ghost copies of the neighbours' markers near its faces (fl_ibm_create_owned: a few bytes per copy, no all-reduce).  The option
+ * is the user's choice for now: nothing measured on two or more GPUs could pick a default yet.  Another value: PETSC_ERR_ARG_UNKNOWN_TYPE. */
 FlErrorCode NSSetImmersedBoundary(NS ns, int kind, int64_t L, const double *X_dev, const double *Y_dev, const double *Z_dev, const double *dV_dev, const double *Utarget_dev);
 FlErrorCode NSGetSolutionArrays(NS ns, double **v_dev, double *V_dev[3], double **p_dev);
 FlErrorCode NSGetPressureHalfStep(NS ns, double **phalf_dev); /* cnl->phalf, the vector named "PressureHalfStep" (cnlinear.c:54) */

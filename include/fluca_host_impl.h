@@ -87,6 +87,8 @@ struct _p_NS {
   int64_t              ibm_L;
   const double        *ibm_dV, *ibm_Ut;
   double              *ibm_U;
+  int                  ibm_owner;  /* -ns_ibm_marker_distribution: 0 replicated (default), 1 owner */
+  void                *ibm_own[6]; /* owner: this rank's X, Y, Z, dV, Utarget and marker numbers (device, owned by the NS) */
   fl_ksp_opts          schur;    /* -ns_abf_schur_* */
   fl_ksp_opts          mom;      /* -ns_abf_momentum_* */
   int                  schur_ainv, upper_ainv; /* -ns_pc_abf_schur_ainv_type / -ns_pc_abf_upper_ainv_type (PCABFAinvType), default ID */

@@ -81,8 +81,17 @@ __device__ __forceinline__ double ibm_index(const IbmP &P, int d, double pos)
 }
 // first support cell (GLOBAL index, may be out of range)
 __device__ __forceinline__ int ibm_first(const IbmP &P, double s) { return (P.kind == FL_DELTA_PESKIN4) ? (int)floor(s) - 1 : (int)floor(s + 0.5) - 1; }
+// ... as it is stored and handed to support_cell: on a periodic axis taken modulo ng, so that a position any number of periods beyond either end
+// counts as its image in the box (the rule of k_ibm_route's ownership test and of the oracle), and first + a < ng + S: the single wrap of
+// support_cell and of k_ibm_spread's staging step is a full one.  The weights are formed from the unwrapped index.
+__device__ __forceinline__ int ibm_wrap_first(const IbmP &P, int d, int i)
+{
+  if (!P.periodic[d]) return i;
+  i %= P.ng[d];
+  return i < 0 ? i + P.ng[d] : i;
+}
 
-// i0[d*L + l] = first support cell (GLOBAL index, may be out of range); w[(d*4 + a)*L + l] = phi weights
+// i0[d*L + l] = first support cell (GLOBAL index; beyond a wall out of range, on a periodic axis in [0, ng)); w[(d*4 + a)*L + l] = phi weights
 __global__ void k_ibm_weights(IbmP P, const double *__restrict__ X, const double *__restrict__ Y, const double *__restrict__ Z, int *__restrict__ i0, double *__restrict__ w)
 {
   const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -96,14 +105,14 @@ __global__ void k_ibm_weights(IbmP P, const double *__restrict__ X, const double
       const double r          = s - (double)(i + a);
       w[(d * 4 + a) * P.L + l] = a < P.S ? (P.kind == FL_DELTA_PESKIN4 ? phi_peskin4(r) : phi_roma3(r)) : 0.;
     }
-    i0[d * P.L + l] = i;
+    i0[d * P.L + l] = ibm_wrap_first(P, d, i);
   }
 }
 
 // LOCAL cell index of support entry a, or -1 when that cell is not owned by this rank.  Every rank sees every marker whose
 // support touches its block (replicated markers: all of them; owner-rank markers: its own and the ghost copies); a support
 // that straddles a block face is simply shared out between the two owners, and a support that crosses a periodic boundary
-// wraps in GLOBAL index space first.
+// wraps in GLOBAL index space first (once: i0 comes from ibm_wrap_first).
 __device__ __forceinline__ int support_cell(const IbmP &P, int d, int i0, int a)
 {
   int c = i0 + a;
@@ -334,7 +343,7 @@ __global__ void k_ibm_route(IbmP P, RouteP R, const double *__restrict__ X, cons
       if (c < 0) c += P.ng[d];
     } else c = min(max(c, 0), P.ng[d] - 1);
     mine = mine && c >= P.lo[d] && c < P.lo[d] + P.n[d];
-    const int i     = ibm_first(P, s);
+    const int i     = ibm_wrap_first(P, d, ibm_first(P, s));
     int       first = -1, last = -1;
     for (int a = 0; a < P.S; ++a)
       if (support_cell(P, d, i, a) >= 0) {

@@ -428,7 +428,9 @@ int fl_momentum_chebyshev_interval(fl_momentum *m, double *emin, double *emax);
 typedef enum { FL_DELTA_PESKIN4 = 0, FL_DELTA_ROMA3 = 1 } fl_delta_kind;
 /* markers X,Y,Z (device, length L) are binned per cell at create / update.  Any tensor-product grid: on a stretched axis the delta
  * function is evaluated in index space (marker position -> continuous cell-centre index, piecewise linear through the centres) and
- * spreading divides by the volume of the target cell; on uniform axes that is the textbook delta_h. */
+ * spreading divides by the volume of the target cell; on uniform axes that is the textbook delta_h.  A position on a
+ * periodic axis is taken modulo the period: a marker any number of periods beyond either end counts as its image in the box.  The caller keeps
+ * positions within reach of an int: (X - x0) / h, in cells, must stay below 2^31 in size. */
 int fl_ibm_create(fl_poisson *grid_from, int kind, int64_t L, const double *X_dev, const double *Y_dev, const double *Z_dev, fl_ibm **out);
 int fl_ibm_update(fl_ibm *m, const double *X_dev, const double *Y_dev, const double *Z_dev);
 /* U[c*L + l] = sum_x u[c*ncell + x] delta_h(x - X_l) h^3 */

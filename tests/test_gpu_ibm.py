@@ -1,5 +1,7 @@
 """-m gpu: IBM interpolation / spreading kernels against the CPU oracle and the analytic invariants of the spec
-(no reference implementation exists: SURVEY section 0 / 8a row I1)."""
+(no reference implementation exists: SURVEY section 0 / 8a row I1).  Small sets on small grids: bins of several LDS chunks, more than 4096 tiles,
+marker counts that are no multiple of 4, moved, on-lattice and stray markers are in tests/test_gpu_ibm_regimes.py (sets: tests/ibm_regimes.py),
+which also holds the kernels against a long-double reference that is independent of the oracle (tests/ibm_reference.py)."""
 import ctypes as C
 
 import numpy as np

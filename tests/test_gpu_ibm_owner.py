@@ -202,7 +202,8 @@ def _owner_worker(R, case, ref, kind, replicated, hand_to=None, with_gid=True):
                 capi.check(lib.fl_ibm_interp(mr, 3, _ptr(ul), _ptr(Ur)))
                 s.synchronize()
                 out["rep_interp_wire"] = {k: R.stats()[k] - st0[k] for k in st0}
-                capi.check(lib.fl_ibm_spread(mr, 3, _ptr(dev(ref["F"])), _ptr(dev(ref["dV"])), _ptr(fr)))
+                Fr, dVr = dev(ref["F"]), dev(ref["dV"])      # named: a temporary would be freed, and its block handed out again, before the call
+                capi.check(lib.fl_ibm_spread(mr, 3, _ptr(Fr), _ptr(dVr), _ptr(fr)))
                 s.synchronize()
                 out.update(U_rep=Ur.cpu().numpy().reshape(3, L), f_rep=fr.cpu().numpy().reshape(3, -1), rep_counts_rc=lib.fl_ibm_owned_counts(mr, c5b))
                 lib.fl_ibm_destroy(mr)

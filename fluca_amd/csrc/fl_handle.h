@@ -1,20 +1,17 @@
-// fl_handle.h -- the fl_poisson handle, the halo transports and the kernel launchers shared by the .hip files.
+// fl_handle.h -- the fl_poisson handle, the declarations of the halo transports (fl_comm.hip) and the kernel launchers shared by the .hip files.
 #pragma once
-#include <dlfcn.h>
-#include <rccl/rccl.h>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <ctime>
 #include <limits>
 #include <list>
-#include <mutex>
 #include <string>
 
 #include "fl_internal.h"
 #include "fl_knobs.h"
+
+typedef struct ncclComm *ncclComm_t;  // RCCL's opaque communicator, as <rccl/rccl.h> declares it
 
 namespace fl {
 
@@ -52,7 +49,7 @@ void  launch_cg_Bq(hipStream_t, const GridP &, bool, const PlanA &, int xu, bool
 void  launch_stream_ref(hipStream_t, int, int, int64_t, const double *, const double *, const double *, double *, double *, double *);
 void  launch_stream_par(hipStream_t, int, int, int, int, int, int64_t, const double *, const double *, const double *, double *, double *, double *);
 
-// ------------------------------------------------------------------------------------------------ transports
+// ------------------------------------------------------------------------------------------------ transports (fl_comm.hip)
 
 struct Msg {
   int     peer;
@@ -60,54 +57,6 @@ struct Msg {
   int64_t count;
   int     sendtag, recvtag;
 };
-
-struct Rccl {
-  void *lib = nullptr;
-  decltype(&ncclGetUniqueId)    GetUniqueId    = nullptr;
-  decltype(&ncclCommInitRank)   CommInitRank   = nullptr;
-  decltype(&ncclCommDestroy)    CommDestroy    = nullptr;
-  decltype(&ncclSend)           Send           = nullptr;
-  decltype(&ncclRecv)           Recv           = nullptr;
-  decltype(&ncclAllReduce)      AllReduce      = nullptr;
-  decltype(&ncclGroupStart)     GroupStart     = nullptr;
-  decltype(&ncclGroupEnd)       GroupEnd       = nullptr;
-  decltype(&ncclGetErrorString) GetErrorString = nullptr;
-  decltype(&ncclCommCount)      CommCount      = nullptr;
-  decltype(&ncclCommUserRank)   CommUserRank   = nullptr;
-  std::mutex mu;  // handles of several host threads may reach their first RCCL call together
-  int        load()
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    if (lib) return 0;
-    // the soname: inside a process that already loaded torch this resolves to the very RCCL torch.distributed uses
-    void *l = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-    if (!l) l = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!l) {
-      std::fprintf(stderr, "[flucahip] cannot dlopen librccl: %s\n", dlerror());
-      return FL_ERR_LIB;
-    }
-#define FL_SYM(n)                                                \
-  n = (decltype(n))dlsym(l, "nccl" #n);                          \
-  if (!n) {                                                      \
-    std::fprintf(stderr, "[flucahip] librccl lacks nccl" #n "\n"); \
-    return FL_ERR_LIB;                                           \
-  }
-    FL_SYM(GetUniqueId) FL_SYM(CommInitRank) FL_SYM(CommDestroy) FL_SYM(Send) FL_SYM(Recv) FL_SYM(AllReduce) FL_SYM(GroupStart) FL_SYM(GroupEnd) FL_SYM(GetErrorString) FL_SYM(CommCount) FL_SYM(CommUserRank)
-#undef FL_SYM
-    lib = l;  // last: a reader that sees lib != nullptr sees every symbol
-    return 0;
-  }
-};
-inline Rccl g_rccl;
-
-#define FL_NCCL(call)                                                                                              \
-  do {                                                                                                             \
-    ncclResult_t r_ = (call);                                                                                      \
-    if (r_ != ncclSuccess) {                                                                                       \
-      std::fprintf(stderr, "[flucahip] %s:%d %s -> %s\n", __FILE__, __LINE__, #call, g_rccl.GetErrorString(r_)); \
-      return FL_ERR_LIB;                                                                                           \
-    }                                                                                                              \
-  } while (0)
 
 // One-shot all-reduce of up to NSLOT doubles: every rank owns a MAILBOX in fine-grained device memory --
 // two parities of nranks slots of NSLOT doubles and nranks sequence numbers each -- that its peers have mapped (hipIpc handles exchanged once
@@ -153,130 +102,12 @@ struct Comm {
     // sequence numbers -- the coarse levels' reductions go through the borrowed RCCL / host wire
   }
 
-  int exchange(hipStream_t st, const std::vector<Msg> &m)
-  {
-    if (m.empty()) return 0;
-    if (kind == RCCL) {
-      FL_NCCL(g_rccl.GroupStart());
-      // a failing Send / Recv must not leave the communicator inside an open group: remember the error, close the group, report
-      ncclResult_t bad = ncclSuccess;
-      for (const Msg &x : m) {
-        if (bad == ncclSuccess && x.send) bad = g_rccl.Send(x.send, (size_t)x.count, ncclDouble, x.peer, nccl, st);
-        if (bad == ncclSuccess && x.recv) bad = g_rccl.Recv(x.recv, (size_t)x.count, ncclDouble, x.peer, nccl, st);
-      }
-      const ncclResult_t end = g_rccl.GroupEnd();
-      if (bad != ncclSuccess || end != ncclSuccess) {
-        std::fprintf(stderr, "[flucahip] halo exchange over RCCL failed: %s\n", g_rccl.GetErrorString(bad != ncclSuccess ? bad : end));
-        return FL_ERR_LIB;
-      }
-      return 0;
-    }
-    if (kind == HOST) {
-      const int n = (int)m.size();
-      if (knob(K_comm_trace) != 0) {
-        static std::atomic<long> seq{0};
-        struct timespec ts;
-        clock_gettime(CLOCK_MONOTONIC, &ts);
-        std::fprintf(stderr, "[%.3f comm r%d #%ld] exchange %d msgs:", ts.tv_sec % 1000 + 1e-9 * ts.tv_nsec, rank, seq.fetch_add(1), n);
-        for (const Msg &x : m) std::fprintf(stderr, " (peer %d stag %d rtag %d n %lld%s%s)", x.peer, x.sendtag, x.recvtag, (long long)x.count, x.send ? " S" : "", x.recv ? " R" : "");
-        std::fprintf(stderr, "\n");
-        std::fflush(stderr);
-      }
-      if ((int)hsend.size() < n) {
-        hsend.resize(n, nullptr);
-        hrecv.resize(n, nullptr);
-        hcap.resize(n, 0);
-      }
-      std::vector<int>     peer(n), stag(n), rtag(n);
-      std::vector<void *>  sp(n), rp(n);
-      std::vector<int64_t> nb(n);
-      for (int a = 0; a < n; ++a) {
-        if (hcap[a] < m[a].count) {
-          if (hsend[a]) (void)hipHostFree(hsend[a]);
-          if (hrecv[a]) (void)hipHostFree(hrecv[a]);
-          FL_HIP(hipHostMalloc((void **)&hsend[a], sizeof(double) * m[a].count));
-          FL_HIP(hipHostMalloc((void **)&hrecv[a], sizeof(double) * m[a].count));
-          hcap[a] = m[a].count;
-        }
-        if (m[a].send) FL_HIP(hipMemcpyAsync(hsend[a], m[a].send, sizeof(double) * m[a].count, hipMemcpyDeviceToHost, st));
-        peer[a] = m[a].peer;
-        stag[a] = m[a].sendtag;
-        rtag[a] = m[a].recvtag;
-        sp[a]   = m[a].send ? hsend[a] : nullptr;
-        rp[a]   = m[a].recv ? hrecv[a] : nullptr;
-        nb[a]   = (int64_t)sizeof(double) * m[a].count;
-      }
-      FL_HIP(hipStreamSynchronize(st));
-      if (xchg(ctx, n, peer.data(), stag.data(), rtag.data(), sp.data(), rp.data(), nb.data()) != 0) return FL_ERR_LIB;
-      for (int a = 0; a < n; ++a)
-        if (m[a].recv) FL_HIP(hipMemcpyAsync(m[a].recv, hrecv[a], sizeof(double) * m[a].count, hipMemcpyHostToDevice, st));
-      return 0;
-    }
-    return FL_ERR_ARG_WRONGSTATE;
-  }
-
   bool loopback = false;
-  int  allreduce(hipStream_t st, double *dev, int n)
-  {
-    if (nranks == 1 && !loopback) return 0;
-    if (oneshot_ready && n <= NSLOT && knob(K_allreduce) == 1) {
-      launch_oneshot_allreduce(st, peers_dev, rank, nranks, ++oneshot_calls, dev, n);
-      return 0;
-    }
-    if (kind == RCCL) {
-      FL_NCCL(g_rccl.AllReduce(dev, dev, (size_t)n, ncclDouble, ncclSum, nccl, st));
-      return 0;
-    }
-    if (kind == HOST) {
-      if (hredcap < n) {
-        if (hred) (void)hipHostFree(hred);
-        FL_HIP(hipHostMalloc((void **)&hred, sizeof(double) * (size_t)std::max(n, 64)));
-        hredcap = std::max(n, 64);
-      }
-      FL_HIP(hipMemcpyAsync(hred, dev, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-      FL_HIP(hipStreamSynchronize(st));
-      if (allred(ctx, hred, n) != 0) return FL_ERR_LIB;
-      FL_HIP(hipMemcpyAsync(dev, hred, sizeof(double) * n, hipMemcpyHostToDevice, st));
-      return 0;
-    }
-    return FL_ERR_ARG_WRONGSTATE;
-  }
-
-  void destroy_oneshot()
-  {
-    if (!owns) {  // a multigrid level: the mailboxes belong to the fine handle
-      box = nullptr;
-      peers_dev = nullptr;
-      oneshot_ready = false;
-      return;
-    }
-    for (void *p : ipc_opened) (void)hipIpcCloseMemHandle(p);
-    ipc_opened.clear();
-    if (peers_dev) (void)hipFree(peers_dev);
-    if (box) (void)hipFree(box);
-    peers_dev = nullptr;
-    box = nullptr;
-    oneshot_ready = false;
-    oneshot_calls = 0;
-  }
-  void destroy()
-  {
-    destroy_oneshot();
-    if (kind == RCCL && nccl && owns) g_rccl.CommDestroy(nccl);
-    for (double *p : hsend)
-      if (p) (void)hipHostFree(p);
-    for (double *p : hrecv)
-      if (p) (void)hipHostFree(p);
-    if (hred) (void)hipHostFree(hred);
-    hsend.clear();
-    hrecv.clear();
-    hcap.clear();
-    hred = nullptr;
-    hredcap = 0;
-    nccl = nullptr;
-    kind = NONE;
-    owns = true;
-  }
+  // fl_comm.hip
+  int  exchange(hipStream_t st, const std::vector<Msg> &m);
+  int  allreduce(hipStream_t st, double *dev, int n);
+  void destroy_oneshot();
+  void destroy();
 };
 
 }  // namespace fl
@@ -324,11 +155,11 @@ struct fl_poisson {
   double *sv_ring[12] = {};  // several ranks: [b] the ring of a^-1 received across boundary b, [6 + b] the plane sent across it (fl_schur_var.hip; freed with h->tables)
   double *rb = nullptr;   // where the three-step sweep from a zero guess writes the updated right-hand side; swaps roles with r afterwards
   std::vector<void *> vec_bases;
-  // placement (fl_api.hip): one arena, the five CG vectors in a window found by probing, two side pools for the rest
+  // placement (fl_place.hip): one arena, the five CG vectors in a window found by probing, two side pools for the rest
   void  *arena = nullptr;
   size_t arena_bytes = 0, pool_vec = 0;
   size_t vec_bytes = 0;  // device memory behind vec_bases
-  struct VmmArena *vmm = nullptr;  // placement window that lives in chunk-mapped virtual memory (fl_api.hip)
+  struct VmmArena *vmm = nullptr;  // placement window that lives in chunk-mapped virtual memory (fl_place.hip)
   char  *pool_next[2] = {nullptr, nullptr}, *pool_end[2] = {nullptr, nullptr};
   int    pool_flip = 0;
   bool   placed = false;
@@ -406,22 +237,30 @@ struct ProfEvents {
   }
 };
 
-// shared host helpers (fl_api.hip)
-int  fl_dev_alloc(fl_poisson *h, void **p, size_t bytes, bool zero);
+// shared host helpers
+inline int fl_plane_size(const fl_poisson *h, int d) { return d == 0 ? h->g.ny * h->g.nz : (d == 1 ? h->g.nx * h->g.nz : h->g.nx * h->g.ny); }  // cells of a face across axis d
+int  fl_dev_alloc(fl_poisson *h, void **p, size_t bytes, bool zero);  // fl_api.hip
+// fl_place.hip
 int  fl_ensure_vec(fl_poisson *h, double **v);
 void fl_vmm_destroy(fl_poisson *h);
 int  fl_ensure_partials(fl_poisson *h, int nblocks);
 int  fl_ensure_hist(fl_poisson *h, int nhist);
 int  fl_zero_vec(fl_poisson *h, double *v);
+// fl_halo.hip
+int  fl_halo_messages(const fl_poisson *h, bool self, fl_halo_msg plan[12]);  // fl_halo_plan of the handle (+ the loopback self-messages); -> their number
 int  fl_fill_ghosts(fl_poisson *h, double *v);
 int  fl_fill_ghosts_full(fl_poisson *h, double *v);  // edges and corners too (dimension by dimension)
+int  fl_fill_ghosts_deep(fl_poisson *h, double *v);
+int  fl_fill_hifaces(fl_poisson *h, const double *const V[3]);
 int  fl_exchange_r_begin(fl_poisson *h, double *r, const double *q);
+int  fl_exchange_sr_begin(fl_poisson *h, const double *r, const double *sb, const double *W, double *rn);
 int  fl_exchange_r_end(fl_poisson *h, double *r);
 bool fl_any_ghost_exchange(const fl_poisson *h);
-int  fl_poll_scal(fl_poisson *h);
-int  fl_fill_ghosts_deep(fl_poisson *h, double *v);
-int  fl_exchange_sr_begin(fl_poisson *h, const double *r, const double *sb, const double *W, double *rn);
+// fl_comm.hip
+int fl_allreduce_max(fl_poisson *h, double *v);
+int fl_allreduce_sum(fl_poisson *h, double *v);
 // fl_ksp.hip
+int fl_poll_scal(fl_poisson *h);
 int fl_apply_tiled(fl_poisson *h, const double *xpad, double *y, int unpadded_y);
 int fl_residual(fl_poisson *h, const double *x, const double *b, double *r);
 int fl_residual_padded(fl_poisson *h, double *xpad, const double *bpad, double *rpad);
@@ -429,13 +268,12 @@ bool fl_residual_restrict_fusable(const GridP &g);
 int fl_residual_restrict_padded(fl_poisson *h, double *xpad, const double *bpad, const double *wx, const double *wy, const double *wz, fl_poisson *hc, double *cpad);
 int fl_apply_padded_dot(fl_poisson *h, double *xpad, double *ypad, double *xy);
 int fl_cheb_smooth_padded(fl_poisson *h, int nu, bool jac, bool guess_zero, bool *mgdots = nullptr, const double *subq = nullptr, const double *suba_dev = nullptr);
+int fl_solve_cg(fl_poisson *h, const double *b, double *x, const fl_ksp_opts *o, fl_ksp_stats *st);
 int fl_solve_bcgs(fl_poisson *h, const double *b, double *x, const fl_ksp_opts *o, fl_ksp_stats *st);
 int fl_solve_cg_sr(fl_poisson *h, const double *b, double *x, const fl_ksp_opts *o, fl_ksp_stats *st);
 int fl_ksp_begin(fl_poisson *h, const fl_ksp_opts *o);
 int fl_bcgs_fin_step(fl_poisson *h, int mode, int nblocks, int nslot, int nhist);
 int fl_ksp_finish(fl_poisson *h, const fl_ksp_opts *o, fl_ksp_stats *st);
-int fl_allreduce_max(fl_poisson *h, double *v);
-int fl_allreduce_sum(fl_poisson *h, double *v);
 int fl_cheb_begin(fl_poisson *h, const fl_ksp_opts *o, double emin, double emax);
 int fl_cheb_fin_step(fl_poisson *h, int nblocks, int nhist);
 int fl_solve_cheb(fl_poisson *h, const double *b, double *x, const fl_ksp_opts *o, fl_ksp_stats *st);

@@ -2,7 +2,7 @@
 //
 // fl_tuning_set / fl_tuning_get (include/fluca_hip.h): process-wide integers, atomics -- handles of several host threads read them while they
 // run; set them before the solves they should affect.  Their initial value is the table's default or, if set, the environment variable
-// FLUCA_<NAME IN CAPITALS>; the environment is read ONCE, in one place (knob_table_init, fl_api.hip).  Nothing else in the library reads the
+// FLUCA_<NAME IN CAPITALS>; the environment is read ONCE, in one place (knob_table_init, fl_knobs.cpp).  Nothing else in the library reads the
 // environment, and there is no second build: every other choice is a constant next to the code it steers.
 #pragma once
 #include <atomic>

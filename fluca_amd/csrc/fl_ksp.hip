@@ -1080,6 +1080,23 @@ void init_scal(fl_poisson *h, const fl_ksp_opts *o)
   S.nullspace    = o->remove_nullspace;
 }
 
+// The polled loop of the CG, single-reduction CG and BiCGStab drivers: enqueue(it) queues iteration `it`; after every check_every of them the
+// host reads the scalar block back (fl_poll_scal, its only wait) and stops on a reason or at `total`.
+template <class F>
+int polled_loop(fl_poisson *h, const fl_ksp_opts *o, int total, F &&enqueue)
+{
+  const int every = o->check_every > 0 ? o->check_every : 16;
+  int       it    = 0;
+  bool      done  = false;
+  while (!done) {
+    const int stop = std::min(total, it + every);
+    for (; it < stop; ++it) FL_CHK(enqueue(it));
+    FL_CHK(fl_poll_scal(h));
+    if (h->scal_host->reason != 0 || it >= total) done = true;
+  }
+  return 0;
+}
+
 int finish_stats(fl_poisson *h, const fl_ksp_opts *o, fl_ksp_stats *st)
 {
   FL_HIP(hipEventRecord(h->ev1, h->stream));
@@ -1090,7 +1107,7 @@ int finish_stats(fl_poisson *h, const fl_ksp_opts *o, fl_ksp_stats *st)
   const KspScal &R = *h->scal_host;
   st->iters        = R.it;
   st->reason       = R.reason ? R.reason : FL_DIVERGED_ITS;
-  if (R.reason == FL_DIVERGED_NANORINF || R.reason == FL_DIVERGED_DTOL || !std::isfinite(R.dp)) h->poisoned = true;  // see solve_cg
+  if (R.reason == FL_DIVERGED_NANORINF || R.reason == FL_DIVERGED_DTOL || !std::isfinite(R.dp)) h->poisoned = true;  // see fl_solve_cg
   st->rnorm0       = R.rnorm0;
   st->rnorm        = R.dp;
   st->seconds      = ms * 1e-3;
@@ -1103,6 +1120,13 @@ int finish_stats(fl_poisson *h, const fl_ksp_opts *o, fl_ksp_stats *st)
 
 }  // namespace
 
+
+int fl_poll_scal(fl_poisson *h)
+{
+  FL_HIP(hipMemcpyAsync(h->scal_host, h->scal, sizeof(KspScal), hipMemcpyDeviceToHost, h->stream));
+  FL_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
 
 int fl_apply_tiled(fl_poisson *h, const double *xpad, double *y, int unpadded_y)
 {
@@ -1392,6 +1416,107 @@ int fl_cheb_smooth_padded(fl_poisson *h, int nu, bool jac, bool guess_zero, bool
 }
 
 
+// KSPCG, the default pair: k_cg_A + k_cg_Bq (fl_kernels.hip)
+int fl_solve_cg(fl_poisson *h, const double *b, double *x, const fl_ksp_opts *o, fl_ksp_stats *st)
+{
+  if (o->variant != 0) return FL_ERR_SUP;  // the superseded forms of the iteration left the library (include/fluca_hip.h, fl_ksp_opts.variant)
+  const GridP &g   = h->g;
+  const bool   jac = o->pc == FL_PC_JACOBI;
+  for (double **v : {&h->r, &h->P0, &h->P1, &h->q, &h->xp}) FL_CHK(fl_ensure_vec(h, v));
+  // k_cg_A + k_cg_Bq: q = S p' is formed twice and never stored (64 B/cell/iteration, less with batched x-updates); k_cg_Bq walks the tiles of k_cg_A
+  PlanA plan = plan_cg_A(g, 0, 0);
+  plan.qb    = h->multi ? 1 : 0;  // several ranks: q of the boundary layers is kept for the overlapped exchange of r
+  const int   nsb  = stream_blocks(g);
+  FL_CHK(fl_ensure_partials(h, std::max(nsb, plan.nblocks)));
+  const int nhist = o->maxit + 1;
+  FL_CHK(fl_ensure_hist(h, nhist));
+  hipStream_t s = h->stream;
+
+  const bool xbatch_env = knob(K_cg_xbatch) != 0;
+  // batched x-updates: x is read and written on every K-th iteration only, K = the slots of the direction ring (one rank: cg_xdepth; several
+  // ranks: 2).  The padded x is not zeroed -- the first flush (iteration K - 1) writes it
+  // without reading it, and until then KspScal::x_valid = 0 tells k_cg_finish that it stands for 0
+  const bool xlazy  = xbatch_env;
+  const int  xdepth = (xlazy && !h->multi) ? knob(K_cg_xdepth) : 2;
+  if (!cg_xdepth_ok(xdepth)) return FL_ERR_ARG_OUTOFRANGE;
+  for (int k = 2; k < xdepth; ++k) FL_CHK(fl_ensure_vec(h, &h->Pr[k - 2]));
+  DirRing ring = dir_ring2(h->P0, h->P1);
+  for (int k = 2; k < xdepth; ++k) ring.v[k] = h->Pr[k - 2];
+  init_scal(h, o);
+  KspScal &S = *h->scal_host;
+  S.rz_old  = 1.;
+  S.x_valid = xlazy ? 0 : 1;
+  S.xdepth  = xdepth;
+
+  FL_HIP(hipEventRecord(h->ev0, s));
+  FL_HIP(hipMemcpyAsync(h->scal, h->scal_host, sizeof(KspScal), hipMemcpyHostToDevice, s));
+  // The direction buffers need no zeroing: the first iteration multiplies the old direction by beta = 0 and by alpha_prev = 0,
+  // so whatever FINITE numbers an earlier solve left there drop out (wall ghosts included: they only ever meet the stencil
+  // coefficient 0).  After a solve that produced NaN / Inf they are cleared.  x is zeroed by the kernel that pads b into r.
+  if (h->poisoned) {
+    for (int k = 0; k < xdepth; ++k) FL_CHK(fl_zero_vec(h, ring.v[k]));
+    FL_CHK(fl_zero_vec(h, h->xp));
+    h->poisoned = false;
+  }
+  launch_cg_init(s, g, jac, b, h->r, xlazy ? nullptr : h->xp, h->partial, h->partial_stride, nsb);
+  FL_CHK(fin_step(h, nsb, 5, [=](const double *partial, int nb, int stride, const double *sums) { launch_cg_fin(s, 0, partial, nb, stride, sums, h->scal, h->hist, nhist); }));
+  const bool ghosts = fl_any_ghost_exchange(h);
+  if (ghosts) FL_CHK(fl_fill_ghosts(h, h->r));
+  const bool overlap_env  = knob(K_overlap) != 0;  // 0: pack / transfer / unpack after the update kernel, on the handle's stream (A/B measurements, tests)
+  // single rank: the last block of k_cg_A / k_cg_Bq performs the scalar update itself (no k_cg_fin launches); several ranks: it still reduces
+  // the rank's partial sums (no k_reduce launch), the all-reduce and the scalar kernel follow
+  const bool fusedsum = h->multi;
+  FL_HIP(hipMemsetAsync(h->tickets, 0, sizeof(unsigned) * 2, s));
+  auto fin_sums = [&](int mode) -> int {
+    FL_CHK(h->comm.allreduce(s, h->sums, NSLOT));
+    launch_cg_fin(s, mode, nullptr, 0, 0, h->sums, h->scal, h->hist, nhist);
+    return 0;
+  };
+
+  ProfEvents               prof_events;
+  std::vector<hipEvent_t> &pev = prof_events.ev;
+  if (o->profile) FL_CHK(prof_events.create(4 * (size_t)std::min(o->maxit, 4096)));  // around k_cg_A, around k_cg_Bq
+
+  int nprof = 0;  // iterations whose kernels are bracketed by events so far
+  FL_CHK(polled_loop(h, o, o->maxit, [&](int it) -> int {
+    // profile = n: the kernels of every n-th GROUP of xdepth iterations are bracketed (one k_cg_Bq of a group also updates x)
+    const bool prof = o->profile > 0 && (it / xdepth) % o->profile == 0 && (size_t)(4 * nprof + 3) < pev.size();
+    const int  pi   = 4 * nprof;
+    if (prof) ++nprof;
+    if (prof) FL_HIP(hipEventRecord(pev[pi], s));
+    launch_cg_A(s, g, jac, plan, h->r, ring, h->q, h->xp, h->scal, h->partial, h->tickets, h->hist, nhist, fusedsum ? h->sums : nullptr);
+    if (prof) FL_HIP(hipEventRecord(pev[pi + 1], s));
+    if (fusedsum) FL_CHK(fin_sums(3));  // k_cg_A does not touch x (see cg_fin_apply)
+    // several ranks: the boundary layers of the new r leave now (packed as r - alpha q), the transfers overlap k_cg_Bq
+    // k_cg_Bq owns the x-update -- all xdepth updates of a group of iterations on its last one (x is read and written
+    // every xdepth-th iteration only), or one per iteration with FLUCA_CG_XBATCH=0
+    const int  xu      = xbatch_env ? (it % xdepth == xdepth - 1 ? xdepth : 0) : 1;
+    const bool xz      = xbatch_env && it == xdepth - 1;  // the first flush: x = 0 is not read
+    const bool overlap = ghosts && h->multi && overlap_env;
+    if (overlap) FL_CHK(fl_exchange_r_begin(h, h->r, h->q));
+    if (prof) FL_HIP(hipEventRecord(pev[pi + 2], s));
+    launch_cg_Bq(s, g, jac, plan, xu, xz, ring, h->r, h->xp, h->scal, h->partial, h->partial_stride, h->tickets + 1, h->hist, nhist, fusedsum ? h->sums : nullptr);
+    if (prof) FL_HIP(hipEventRecord(pev[pi + 3], s));
+    // the handle's stream joins the exchange BEFORE the all-reduce is enqueued: the two RCCL operations never run at the same time
+    // (one communicator, two streams), only the transfers and k_cg_Bq do
+    if (overlap) FL_CHK(fl_exchange_r_end(h, h->r));
+    if (fusedsum) FL_CHK(fin_sums(xu ? 4 : 2));
+    if (!overlap && ghosts) FL_CHK(fl_fill_ghosts(h, h->r));
+    return 0;
+  }));
+  launch_cg_finish(s, g, ring, h->xp, x, h->scal, nsb);  // x = xp + the x-updates still owed
+  FL_CHK(finish_stats(h, o, st));
+  if (o->profile) {
+    // iterations enqueued after the device had stopped are early exits: count only those that ran
+    int ran = 0;
+    for (int a = 0, q = 0; a < st->iters; ++a)
+      if ((a / xdepth) % o->profile == 0 && q++ < nprof) ++ran;
+    prof_events.mean_of(ran, 4, 0, 1, &st->kernel_ms, &st->kernel_launches);
+    prof_events.mean_of(ran, 4, 2, 3, &st->kernel2_ms, &st->kernel2_launches);
+  }
+  return FL_SUCCESS;
+}
+
 int fl_solve_bcgs(fl_poisson *h, const double *b, double *x, const fl_ksp_opts *o, fl_ksp_stats *st)
 {
   // V0 = M S P and T0 = M S S0 are formed wherever they are needed and never stored (k_bcgs_st, 120 B/cell/iteration)
@@ -1418,29 +1543,22 @@ int fl_solve_bcgs(fl_poisson *h, const double *b, double *x, const fl_ksp_opts *
   FL_CHK(fin_step(h, tp.nblocks, 3, fin(0)));
   launch_pw<4>(h, tp, jac, nullptr, nullptr, nullptr, nullptr, R, RP);
   const bool ghosts = fl_any_ghost_exchange(h);
-  const int  every  = o->check_every > 0 ? o->check_every : 16;
-  int        it = 0;
-  bool       done = false;
-  while (!done) {
-    const int stop = std::min(o->maxit, it + every);
-    for (; it < stop; ++it) {
-      // P' = R - omega_old beta (M S P - vshift) + beta P   (the old P's ghosts are still those filled for the iteration before)
-      launch_bcgs_st<5>(h, pa, jac, P, R, nullptr, nullptr, Pn, nullptr);
-      std::swap(P, Pn);
-      if (ghosts) FL_CHK(fl_fill_ghosts(h, P));
-      launch_bcgs_st<1>(h, pa, jac, P, RP, nullptr, nullptr, nullptr, nullptr);
-      FL_CHK(fin_step(h, pa.nblocks, 4, fin(1)));
-      launch_bcgs_st<2>(h, pa, jac, P, R, nullptr, nullptr, S0, nullptr);
-      FL_CHK(fin_step(h, pa.nblocks, 3, fin(2)));
-      if (ghosts) FL_CHK(fl_fill_ghosts(h, S0));
-      launch_bcgs_st<3>(h, pa, jac, S0, nullptr, nullptr, nullptr, nullptr, nullptr);
-      FL_CHK(fin_step(h, pa.nblocks, 4, fin(3)));
-      launch_bcgs_st<4>(h, pa, jac, S0, P, X, RP, X, R);
-      FL_CHK(fin_step(h, pa.nblocks, 3, fin(4)));
-    }
-    FL_CHK(fl_poll_scal(h));
-    if (h->scal_host->reason != 0 || it >= o->maxit) done = true;
-  }
+  FL_CHK(polled_loop(h, o, o->maxit, [&](int) -> int {
+    // P' = R - omega_old beta (M S P - vshift) + beta P   (the old P's ghosts are still those filled for the iteration before)
+    launch_bcgs_st<5>(h, pa, jac, P, R, nullptr, nullptr, Pn, nullptr);
+    std::swap(P, Pn);
+    if (ghosts) FL_CHK(fl_fill_ghosts(h, P));
+    launch_bcgs_st<1>(h, pa, jac, P, RP, nullptr, nullptr, nullptr, nullptr);
+    FL_CHK(fin_step(h, pa.nblocks, 4, fin(1)));
+    launch_bcgs_st<2>(h, pa, jac, P, R, nullptr, nullptr, S0, nullptr);
+    FL_CHK(fin_step(h, pa.nblocks, 3, fin(2)));
+    if (ghosts) FL_CHK(fl_fill_ghosts(h, S0));
+    launch_bcgs_st<3>(h, pa, jac, S0, nullptr, nullptr, nullptr, nullptr, nullptr);
+    FL_CHK(fin_step(h, pa.nblocks, 4, fin(3)));
+    launch_bcgs_st<4>(h, pa, jac, S0, P, X, RP, X, R);
+    FL_CHK(fin_step(h, pa.nblocks, 3, fin(4)));
+    return 0;
+  }));
   launch_unpad_copy(s, g, X, x, nullptr);
   return finish_stats(h, o, st);
 }
@@ -1478,23 +1596,16 @@ int fl_solve_cg_sr(fl_poisson *h, const double *b, double *x, const fl_ksp_opts 
   const bool overlap = h->multi && overlap_env;
   launch_bcgs_st<9>(h, pa, jac, R, nullptr, nullptr, nullptr, overlap ? Rn : nullptr, nullptr);
   FL_CHK(fin_step(h, pa.nblocks, 7, fin(0)));
-  const int every = o->check_every > 0 ? o->check_every : 16;
-  int       it = 0;
-  bool      done = false;
-  while (!done) {
-    const int stop = std::min(o->maxit, it + every);
-    for (; it < stop; ++it) {
-      if (overlap) FL_CHK(fl_exchange_sr_begin(h, R, Rn, W, Rn));  // packs before MODE 10 overwrites the kept S with the new residual
-      launch_bcgs_st<10>(h, pa, jac, R, P, W, X, Rn, nullptr);
-      std::swap(R, Rn);
-      if (overlap) FL_CHK(fl_exchange_r_end(h, R));
-      else if (ghosts) FL_CHK(fl_fill_ghosts(h, R));
-      launch_bcgs_st<9>(h, pa, jac, R, nullptr, nullptr, nullptr, overlap ? Rn : nullptr, nullptr);
-      FL_CHK(fin_step(h, pa.nblocks, 7, fin(1)));
-    }
-    FL_CHK(fl_poll_scal(h));
-    if (h->scal_host->reason != 0 || it >= o->maxit) done = true;
-  }
+  FL_CHK(polled_loop(h, o, o->maxit, [&](int) -> int {
+    if (overlap) FL_CHK(fl_exchange_sr_begin(h, R, Rn, W, Rn));  // packs before MODE 10 overwrites the kept S with the new residual
+    launch_bcgs_st<10>(h, pa, jac, R, P, W, X, Rn, nullptr);
+    std::swap(R, Rn);
+    if (overlap) FL_CHK(fl_exchange_r_end(h, R));
+    else if (ghosts) FL_CHK(fl_fill_ghosts(h, R));
+    launch_bcgs_st<9>(h, pa, jac, R, nullptr, nullptr, nullptr, overlap ? Rn : nullptr, nullptr);
+    FL_CHK(fin_step(h, pa.nblocks, 7, fin(1)));
+    return 0;
+  }));
   launch_unpad_copy(s, g, X, x, nullptr);
   return finish_stats(h, o, st);
 }

@@ -409,10 +409,8 @@ int sv_ring_exchange(fl_poisson *h, const double *ainv)
       h->sv_ring[b]     = (double *)rv;
     }
   if (h->comm.kind == Comm::NONE) return FL_ERR_ARG_WRONGSTATE;
-  int periodic[3];
-  for (int d = 0; d < 3; ++d) periodic[d] = h->ax[d].periodic;
   fl_halo_msg plan[12];
-  const int   np = fl_halo_plan(&h->dec, periodic, plan);
+  const int   np = fl_halo_messages(h, false, plan);
   std::vector<Msg> msgs;
   for (int a = 0; a < np; ++a) {
     const int sb = plan[a].send_boundary, rb = plan[a].recv_boundary, d = sb / 2;

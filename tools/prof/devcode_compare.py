@@ -5,7 +5,7 @@
 
 Every .hip translation unit of fluca_amd/csrc is compiled device-only with the flags of fluca_amd/build.py of its own tree, the code object is
 disassembled (llvm-objdump -d) and its metadata note read (llvm-readelf --notes).  Kernels are matched by their demangled base name plus
-template arguments; `--drop k_cg_A:3,4,5` removes the 0-based template arguments 3, 4 and 5 from the OLD tree's kernels of that name (arguments
+template arguments, within their translation unit -- a kernel whose file changed is matched by name alone and listed as MOVED; `--drop k_cg_A:3,4,5` removes the 0-based template arguments 3, 4 and 5 from the OLD tree's kernels of that name (arguments
 that the new tree no longer has); `--rename 'k_x<false>=k_x'` renames one kernel of the OLD tree outright.  Compared per kernel: the instruction stream (encodings and addresses stripped: inter-function padding, pc-relative displacements) and the VGPR / AGPR / SGPR /
 spill / LDS / scratch / kernarg figures.  Exit status 1 if a matched kernel differs or the new tree has a kernel the old one lacks.
 """
@@ -138,6 +138,15 @@ def main():
     with tempfile.TemporaryDirectory() as w0, tempfile.TemporaryDirectory() as w1:
         old, new = kernels_of(os.path.abspath(a.old), drop, w0), kernels_of(os.path.abspath(a.new), {}, w1)
     old = {(tu, rename.get(name, name)): v for (tu, name), v in old.items()}
+    # a kernel that moved to another translation unit is matched by its name, where that name is unambiguous
+    moved, where = [], {}
+    for tu, name in new:
+        where.setdefault(name, []).append(tu)
+    for tu, name in list(old):
+        tus = where.get(name, [])
+        if (tu, name) not in new and len(tus) == 1 and (tus[0], name) not in old:
+            old[(tus[0], name)] = old.pop((tu, name))
+            moved.append((name, tu, tus[0]))
     print("device code, old tree against new tree: gfx950, product flags, per translation unit")
     print("produced by: tools/prof/devcode_compare.py OLD NEW" + "".join(" --drop " + d for d in a.drop) + "".join(f" --rename '{r}'" for r in a.rename))
     same = [k for k in old if k in new and old[k] == new[k]]
@@ -149,6 +158,8 @@ def main():
     for tu in sorted({k[0] for k in old} | {k[0] for k in new}):
         n_old, n_new = sum(k[0] == tu for k in old), sum(k[0] == tu for k in new)
         print(f"  {tu}: old {n_old}, new {n_new}, identical {sum(k[0] == tu for k in same)}")
+    for name, tu_old, tu_new in moved:
+        print(f"MOVED {name}: {tu_old} -> {tu_new} (matched by name)")
     for k in differ:
         print(f"\nDIFFERS {k[0]} {k[1]}")
         for f in FIGURES:

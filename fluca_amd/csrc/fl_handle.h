@@ -43,7 +43,7 @@ int  stream_blocks(const GridP &);
 void launch_cg_init(hipStream_t, const GridP &, bool, const double *, double *, double *, double *, int, int);
 void launch_cg_finish(hipStream_t, const GridP &, const DirRing &, const double *, double *, const KspScal *, int);
 void  launch_cg_A(hipStream_t, const GridP &, bool, const PlanA &, const double *r, const DirRing &P, double *q, double *x, KspScal *, double *, unsigned *, double *, int, double *sums = nullptr);
-bool  cg_xdepth_ok(int k);  // the direction-ring depths k_cg_Bq is built for (2, 3, 4, 8)
+bool  cg_xdepth_ok(int k);  // the direction-ring depths k_cg_Bq is built for (2, 3, 4, 8, 16)
 void  launch_cg_Bq(hipStream_t, const GridP &, bool, const PlanA &, int xu, bool xz, const DirRing &P, double *r, double *x, KspScal *, double *partial, int stride, unsigned *counter, double *hist,
                    int nhist, double *sums = nullptr);
 void  launch_stream_ref(hipStream_t, int, int, int64_t, const double *, const double *, const double *, double *, double *, double *);

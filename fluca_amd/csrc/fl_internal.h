@@ -74,7 +74,7 @@ struct GridP {
 
 // CG: the direction buffers form a ring of xdepth (2 .. CG_XRING_MAX) slots; iteration i writes slot (i + 1) mod xdepth, and x owes the
 // updates of the directions still in the ring (k_cg_Bq applies xdepth of them at once, k_cg_finish what is left when the solve stops)
-constexpr int CG_XRING_MAX = 8;
+constexpr int CG_XRING_MAX = 16;
 struct DirRing {
   double *v[CG_XRING_MAX];  // slots 0 .. xdepth - 1 are used; the others may be null
 };

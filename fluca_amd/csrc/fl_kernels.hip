@@ -1093,6 +1093,17 @@ __global__ void __launch_bounds__(64 * NW, 2) k_cg_A_probe(FL_CG_A_ARGS)
 }
 #undef FL_CG_A_ARGS
 
+// 16-B non-temporal load from a wave-uniform base + the lane's 32-bit byte offset.  The empty asm pins the base in scalar registers (and the
+// address-space cast keeps the load a global one behind it), so that every such load of a wave shares ONE address register per lane: left
+// alone, hipcc forms a 64-bit address per stream and row outside the plane loop and keeps them all in VGPRs -- 60 of them at ring depth 16.
+__device__ __forceinline__ double2 ld2_nt_su(const double *ubase, unsigned lane_bytes)
+{
+  unsigned long long a = reinterpret_cast<unsigned long long>(ubase);
+  asm volatile("" : "+s"(a));
+  const v2d v = __builtin_nontemporal_load(reinterpret_cast<const __attribute__((address_space(1))) v2d *>(a + lane_bytes));
+  return make_double2(v.x, v.y);
+}
+
 // r -= alpha q with q = S p' FORMED AGAIN from the direction k_cg_A has just written, instead of being read back: k_cg_A never writes
 // q.  Per cell this kernel reads p' (plus the tile's one-cell ring) and r and writes r -- 24 B + ring -- where a q store in k_cg_A and
 // a q load here would move 16 B: an iteration moves 64 B/cell instead of 72.  Same tile walk as k_cg_A
@@ -1105,11 +1116,17 @@ __global__ void __launch_bounds__(64 * NW, 2) k_cg_A_probe(FL_CG_A_ARGS)
 // on the others: 8 (K - 1) + 16 B/cell per K iterations instead of 16 per iteration.  XZ: the first such launch of a solve, x = 0 is not
 // read (the padded x is not zeroed by k_cg_init then).  XU == 1: x += alpha p' every iteration (cg_xbatch = 0, A/B runs).
 // The fma of XU > 1 are the separate updates in iteration order: same x bit for bit.
+// x and the older directions are NOT prefetched a plane ahead with p' and r: step() loads them for the plane it updates, before it issues
+// the next plane's prefetch (the in-order vmcnt wait then releases them without draining that prefetch), and consumes them after the
+// r-update -- XG directions at a time: a ring of 8 holds one set of 7 directions instead of two (two spilled), a ring of 16 at most 8 + 7 while the
+// second group is in flight (254 VGPRs, no scratch: profiles/xflush_resources.txt).
 template <int RY, int NW, bool JAC, int XU, bool XZ>
 __device__ __forceinline__ void cg_Bq_body(const GridP &g, const DirRing &P, double *__restrict__ r, double *__restrict__ x, KspScal *__restrict__ s,
                                            double *__restrict__ partial, int stride, int nchunk, int zc, int tiles_x, int tiles, int remap, FinCtx fin)
 {
   constexpr int NO = XU > 1 ? XU - 1 : 1;  // older directions read by an x-flush (array extent)
+  constexpr int NOL = XU > 1 ? XU - 1 : 0;  // ... and their number
+  constexpr int XG = 8, NG = NOL < XG ? (NOL ? NOL : 1) : XG;  // they are loaded and consumed in groups of at most XG
   using T               = TileA<RY, NW>;
   constexpr int TX = T::TX, TY = T::TY, LX = T::LX, LY = T::LY;
   constexpr int NTL = 1, NTS = 1;  // the non-temporal hint on tile loads / stores
@@ -1173,7 +1190,6 @@ __device__ __forceinline__ void cg_Bq_body(const GridP &g, const DirRing &P, dou
   double zlc = 0., zcc = 0., zhc = 0.;  // z-row of plane kk-1 (the plane whose q is formed)
   struct Raw {
     double2 p[RY], r[RY];  // p' of plane kn, r of plane kn - 1
-    double2 x[(XU >= 1 && !XZ) ? RY : 1], pp[NO][XU > 1 ? RY : 1];  // x (and the older directions) of plane kn - 1
     double  hpA, hpB;
     double  zl, zc, zh;
   };
@@ -1184,10 +1200,6 @@ __device__ __forceinline__ void cg_Bq_body(const GridP &g, const DirRing &P, dou
     for (int m = 0; m < RY; ++m) {
       R.p[m] = ld2<NTL>(p + RO(m) + pl);
       R.r[m] = ld2<NTL>(r + RO(m) + pr);
-      if (XU >= 1 && !XZ) R.x[m] = ld2<NTL>(x + RO(m) + pr);
-      if (XU > 1)
-#pragma unroll
-        for (int t = 0; t < NO; ++t) R.pp[t][m] = ld2<NTL>(pold[t] + RO(m) + pr);
     }
     R.hpA = p[tbase + pl + hAo];
     R.hpB = p[tbase + pl + hBo];
@@ -1196,10 +1208,26 @@ __device__ __forceinline__ void cg_Bq_body(const GridP &g, const DirRing &P, dou
     R.zh  = g.sh[2][kn];
   };
   auto step = [&](int kk, Raw &C, Raw &N) {
+    const int     kc = kk - 1;
+    const int64_t px = (int64_t)min(max(kc, k0), k1 - 1) * g.sxy;  // clamped like every load: the two trips before the chunk's first plane re-read it
+    double2       xn[XU ? RY : 1], pg[NG][RY];  // x of plane kc and one group of older directions
+    const unsigned ilb = (unsigned)il * (unsigned)sizeof(double);
+    auto          load_group = [&](int t0) {
+#pragma unroll
+      for (int t = 0; t < NG; ++t)
+        if (t0 + t < NOL)
+#pragma unroll
+          for (int m = 0; m < RY; ++m) pg[t][m] = ld2_nt_su(pold[t0 + t] + (rob[m] + px), ilb);
+    };
+    if (XU) {
+#pragma unroll
+      for (int m = 0; m < RY; ++m) xn[m] = XZ ? make_double2(0., 0.) : ld2_nt_su(x + (rob[m] + px), ilb);  // XZ: the first updates of a solve, x = 0 is not read
+      load_group(0);
+      asm volatile("" ::: "memory");  // hipcc sinks the last of these loads behind the prefetch, to where it is used, without this
+    }
     load(kk + 1, N);
     const double nzl = C.zl, nzc = C.zc, nzh = C.zh;
     const int    buf = (kk + 3) % 3;
-    const int    kc  = kk - 1;
     if (kc >= k0) {
       const int     bc = (kc + 3) % 3, bp = (kc + 2) % 3;
       const int64_t pc = (int64_t)kc * g.sxy;
@@ -1224,21 +1252,6 @@ __device__ __forceinline__ void cg_Bq_body(const GridP &g, const DirRing &P, dou
           if (own1) st2<NTS>(r + RO(m) + pc, rn);
           else if (own0) r[RO(m) + pc] = rn.x;
         }
-        if (XU) {
-          double2 xn = XZ ? make_double2(0., 0.) : C.x[m];  // XZ: the first updates of a solve, x = 0 is not read
-          if (XU > 1)
-#pragma unroll
-            for (int t = 0; t < NO; ++t) {
-              xn.x = fma(aold[t], C.pp[t][m].x, xn.x);
-              xn.y = fma(aold[t], C.pp[t][m].y, xn.y);
-            }
-          xn.x = fma(alpha, cen.x, xn.x);
-          xn.y = fma(alpha, cen.y, xn.y);
-          if (rown[m]) {
-            if (own1) st2<NTS>(x + RO(m) + pc, xn);
-            else if (own0) x[RO(m) + pc] = xn.x;
-          }
-        }
         // selects, not 0/1 factors: outside the block q is inf * 0 (the ghost diagonal is +inf)
         const bool   o0 = rown[m] && own0, o1 = rown[m] && own1;
         const double r0 = o0 ? rn.x : 0., r1 = o1 ? rn.y : 0., zz0 = o0 ? z0 : 0., zz1 = o1 ? z1 : 0.;
@@ -1247,6 +1260,34 @@ __device__ __forceinline__ void cg_Bq_body(const GridP &g, const DirRing &P, dou
         acc[2] += zz0 + zz1;
         acc[3] += r0 + r1;
         acc[4] += r0 * r0 + r1 * r1;
+      }
+      if (XU) {
+        // x of plane kc: the older directions oldest first, group by group (a later group is loaded once the one before it is consumed), then p'
+#pragma unroll
+        for (int t0 = 0; t0 < NOL; t0 += XG) {
+          if (t0 > 0) {
+            __builtin_amdgcn_sched_barrier(0);  // the next group's loads stay behind the r-update (hipcc still issues them while the group before is consumed)
+            load_group(t0);
+          }
+#pragma unroll
+          for (int t = 0; t < NG; ++t)
+            if (t0 + t < NOL)
+#pragma unroll
+              for (int m = 0; m < RY; ++m) {
+                xn[m].x = fma(aold[t0 + t], pg[t][m].x, xn[m].x);
+                xn[m].y = fma(aold[t0 + t], pg[t][m].y, xn[m].y);
+              }
+        }
+#pragma unroll
+        for (int m = 0; m < RY; ++m) {
+          const double2 cen = *reinterpret_cast<const double2 *>(&lds[bc][w * RY + m + 1][lc]);
+          xn[m].x           = fma(alpha, cen.x, xn[m].x);
+          xn[m].y           = fma(alpha, cen.y, xn[m].y);
+          if (rown[m]) {
+            if (own1) st2<NTS>(x + RO(m) + pc, xn[m]);
+            else if (own0) x[RO(m) + pc] = xn[m].x;
+          }
+        }
       }
     }
 #pragma unroll
@@ -1626,7 +1667,7 @@ void launch_cg_A(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const
 
 
 // k_cg_Bq on the tiling of k_cg_A (plan_cg_A).  xu: x-updates applied (0 none, 1 x += alpha p', K the K owed on every K-th iteration of a
-// ring of K direction buffers, K = 2, 3, 4 or 8); xz: the first of those launches in a solve (x = 0 is not read)
+// ring of K direction buffers, K = 2, 3, 4, 8 or 16); xz: the first of those launches in a solve (x = 0 is not read)
 template <int RY, int NW, int XU, bool XZ>
 static void launch_cg_Bq_x(hipStream_t st, const GridP &g, bool jac, const PlanA &p, const DirRing &P, double *r, double *x, KspScal *s, double *partial, int stride, const FinCtx &fin)
 {
@@ -1646,6 +1687,7 @@ template <int RY, int NW>
 static void launch_cg_Bq_t(hipStream_t st, const GridP &g, bool jac, const PlanA &p, int xu, bool xz, const DirRing &P, double *r, double *x, KspScal *s, double *partial, int stride, const FinCtx &fin)
 {
   switch (xu) {
+  case 16: launch_cg_Bq_z<RY, NW, 16>(st, g, jac, p, xz, P, r, x, s, partial, stride, fin); break;
   case 8: launch_cg_Bq_z<RY, NW, 8>(st, g, jac, p, xz, P, r, x, s, partial, stride, fin); break;
   case 4: launch_cg_Bq_z<RY, NW, 4>(st, g, jac, p, xz, P, r, x, s, partial, stride, fin); break;
   case 3: launch_cg_Bq_z<RY, NW, 3>(st, g, jac, p, xz, P, r, x, s, partial, stride, fin); break;
@@ -1654,7 +1696,7 @@ static void launch_cg_Bq_t(hipStream_t st, const GridP &g, bool jac, const PlanA
   default: launch_cg_Bq_x<RY, NW, 0, false>(st, g, jac, p, P, r, x, s, partial, stride, fin); break;
   }
 }
-bool cg_xdepth_ok(int k) { return k == 2 || k == 3 || k == 4 || k == 8; }
+bool cg_xdepth_ok(int k) { return k == 2 || k == 3 || k == 4 || k == 8 || k == 16; }
 void launch_cg_Bq(hipStream_t st, const GridP &g, bool jac, const PlanA &p, int xu, bool xz, const DirRing &P, double *r, double *x, KspScal *s, double *partial, int stride, unsigned *counter, double *hist,
                   int nhist, double *sums)
 {

@@ -205,9 +205,11 @@ int fl_vec_maxpy(fl_poisson *h, int64_t n, double *x_dev, const double *alphas, 
  *                "placement_vmm" (1): its arenas live in chunk-mapped virtual memory; "placement_verbose" (0): it narrates on stderr.
  *   "cg_xbatch"  1 (default) = the CG solver updates x every cg_xdepth-th iteration (all updates of the group at once, while the older
  *                directions are still in their buffers); 0 = one update per iteration.  The same x bit for bit.
- *   "cg_xdepth"  4 (default) = direction buffers of the Jacobi-PCG ring, i.e. iterations per x-update with cg_xbatch = 1: 2, 3, 4 or 8
+ *   "cg_xdepth"  8 (default) = direction buffers of the Jacobi-PCG ring, i.e. iterations per x-update with cg_xbatch = 1: 2, 3, 4, 8 or 16
  *                (another value fails the solve with FL_ERR_ARG_OUTOFRANGE).  x costs 8 (K - 1) + 16 B/cell per K iterations; the ring
- *                holds K - 2 more padded vectors than two.  Several ranks and the stored-q variants keep K = 2.
+ *                holds K - 2 more padded vectors than two, created by the first solve that needs them: a one-rank handle holds K + 3
+ *                padded vectors in all (r, q, x and the ring) -- 7 at depth 4, 11 at depth 8 (12.7 GB at 512^3), 19 at depth 16
+ *                (21.9 GB).  16 is no faster than 8 at 512^3 (profiles/xflush_ab.txt).  Several ranks keep K = 2.
  *   "mg_prolong" 1 (default) = tri-linear prolongation of the FL_PC_MG cycle; 0 = piecewise constant.  (This one and the next change the
  *                preconditioner, i.e. iteration counts -- not the converged answer.)
  *   "mg_flexible" 1 (default) = the CG around the FL_PC_MG cycle forms beta in the Polak-Ribiere way (flexible CG, KSPFCG with

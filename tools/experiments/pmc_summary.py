@@ -70,7 +70,7 @@ for k, name in (("fl::k_cg_A<2, 8, true>", "pmc_k_cg_A.json"), ("fl::k_cheb2<2, 
         key = name[len("pmc_"):-len(".json")]
         o.update({"kernel_key": key, "sources_at_profiling": provenance.source_hashes(key)})
         o.update({"kernel": k, "fetch_bytes_corrected": o["fetch_GB"] * 1e9, "write_bytes": o["write_GB"] * 1e9,
-                  "source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over `python3 bench.py --steps 8 --warmup 2 --full --skip-cpu --skip-extras` "
+                  "source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over `python3 bench.py --steps 16 --warmup 2 --full --skip-cpu --skip-extras` (16 steps: a ring of 8 flushes twice, the second time reading x) "
                             f"(rocprofv3 runs as in tools/experiments/bench_profile.sh, summarised by tools/experiments/pmc_summary.py, {tag}); FETCH_SIZE in KB doubled (on gfx950 it counts half the bytes of a coalesced streaming read)"})
         json.dump(o, open(os.path.join(ROOT, "profiles", name), "w"), indent=1)
 # the other sizes the same passes saw (bench.py --full runs the configs behind the headline): 256^3 (config 2) and the 512 x 512 x 256 block of the config-5

@@ -24,11 +24,12 @@ static int upload_table(fl_poisson *h, const std::vector<T> &host, const T **dev
 // "abi N": bumped whenever a struct of include/fluca_hip.h grows or an entry point changes its meaning (FL_ABI_VERSION there): a caller built
 // against another header must not be handed this library.  5: fl_ksp_opts carries cg_single_reduction (round 3's trailing field), the
 // momentum solve accepts FL_KSP_CHEBYSHEV, fl_momentum_gershgorin / fl_momentum_chebyshev_interval exist.  7: owner-rank IBM markers
-// (fl_ibm_owned_select / fl_ibm_create_owned / fl_ibm_owned_counts; fl_ibm_update / _interp / _spread are collective on such a set).
+// (fl_ibm_owned_select / fl_ibm_create_owned / fl_ibm_owned_counts; fl_ibm_update / _interp / _spread are collective on such a set).  8: owner-rank markers migrate
+// (fl_ibm_migrate / fl_ibm_owned_fetch).
 extern "C" const char *fl_build_id(void);  // lib/fl_build_id.cpp, written by fluca_amd/build.py: a hash over every source, header and compiler flag
 extern "C" const char *fl_version(void)
 {
-  static const std::string v = std::string("fluca_amd 0.3 (gfx950, abi 7, sources ") + fl_build_id() + ")";
+  static const std::string v = std::string("fluca_amd 0.3 (gfx950, abi 8, sources ") + fl_build_id() + ")";
   return v.c_str();
 }
 extern "C" int fl_abi_version(void) { return FL_ABI_VERSION; }

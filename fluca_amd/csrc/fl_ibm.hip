@@ -29,6 +29,13 @@
 //   k_ibm_pack_pos / k_ibm_unpack_pos, k_ibm_pack_U, k_ibm_collect_U, k_ibm_pack_F, k_ibm_stage_F
 //                   one lane per copy / ghost / marker: records of the messages through the send list, and the owners' sums in
 //                   ascending offset code (a fixed order: deterministic)
+//   migration (fl_ibm_migrate): a marker whose owner cell has moved into a neighbouring block goes there with position, number and attributes
+//   k_ibm_dest      one lane per own marker: the offset code of its new owner (13: it stays), the 27 counts by ballot and popcount per wave
+//   k_ibm_split     stayers compacted in order (ballot scan per block + block offsets), leavers packed as records per offset
+//   k_ibm_rank_arrivals, k_ibm_merge
+//                   arrivals ranked by number (counting, tiled through LDS), then stayers and arrivals -- both ascending -- into one ascending
+//                   list by binary search in each other's numbers: the own list of a set created afresh, without a sort
+//   k_ibm_rigid_pose  a rigid body's markers and target velocities from their reference positions (the host mirror's moving body)
 #include "fl_handle.h"
 
 namespace fl {
@@ -323,6 +330,17 @@ struct RouteP {
   int peer_lo[3], peer_hi[3];  // a rank sits behind the low / high end of the block along this axis (not a wall, not an axis one rank holds alone)
 };
 
+// the cell that decides the owner along axis d (GLOBAL index), s = the marker's continuous cell-centre index: k_ibm_route and k_ibm_dest share it
+__device__ __forceinline__ int ibm_owner_cell(const IbmP &P, int d, double s)
+{
+  int c = (int)floor(s + 0.5);
+  if (P.periodic[d]) {
+    c %= P.ng[d];
+    if (c < 0) c += P.ng[d];
+  } else c = min(max(c, 0), P.ng[d] - 1);
+  return c;
+}
+
 // mask[l] = the set of offsets (bit = code) whose blocks the support of own marker l reaches, or -1 when the marker does not belong to this
 // rank.  THE OWNERSHIP RULE: the marker belongs to the block that holds the cell floor(s_d + 1/2) on every axis, the index wrapped on a periodic
 // axis and clamped to [0, ng-1] otherwise -- global quantities only, so every marker has exactly one owner.  That cell lies inside the support of
@@ -337,11 +355,7 @@ __global__ void k_ibm_route(IbmP P, RouteP R, const double *__restrict__ X, cons
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
     const double s = ibm_index(P, d, pos[d]);
-    int          c = (int)floor(s + 0.5);
-    if (P.periodic[d]) {
-      c %= P.ng[d];
-      if (c < 0) c += P.ng[d];
-    } else c = min(max(c, 0), P.ng[d] - 1);
+    const int    c = ibm_owner_cell(P, d, s);
     mine = mine && c >= P.lo[d] && c < P.lo[d] + P.n[d];
     const int i     = ibm_wrap_first(P, d, ibm_first(P, s));
     int       first = -1, last = -1;
@@ -431,6 +445,170 @@ __global__ void k_ibm_stage_F(int64_t Lo, int64_t Lt, int ncomp, const double *_
   }
 }
 
+// ---- owner-rank markers: migration (fl_ibm_migrate) ------------------------------------------------------------------------------------
+// Every record and every staging array below is made of doubles: position, the marker number (< 2^27: exact) and up to 8 attributes.
+constexpr int MIG_NCNT = 32;  // cnt[0..26] markers per destination offset (13: stay), cnt[27] out of reach, cnt[28] numbers not ascending, cnt[29] spare
+
+struct DestP {
+  int peer_lo[3], peer_hi[3];      // RouteP's
+  int lo_beg[3], lo_end[3];        // GLOBAL cells [beg, end) of the block behind the low end of this one along the axis (the periodic wrap included)
+  int hi_beg[3], hi_end[3];        // ... behind the high end
+};
+
+// dest[l] = the offset code of the block that owns own marker l at its NEW position: 13 it stays, -1 neither this block nor a neighbour holds the cell.
+// Where the low and the high neighbour are one rank (two ranks on a periodic axis) the low one is taken.  cnt: per code, formed per wave (ballot and
+// popcount, the first lane of every code adds once); blockstay[b] = stayers among the block's 256 markers, the input of the compaction's scan.
+__global__ void __launch_bounds__(256) k_ibm_dest(IbmP P, DestP D, const double *__restrict__ X, const double *__restrict__ Y, const double *__restrict__ Z, const int64_t *__restrict__ gid, int *__restrict__ dest, int *__restrict__ cnt,
+                                                  int *__restrict__ blockstay)
+{
+  __shared__ int wstay[4];
+  const int64_t  l     = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int      lane  = threadIdx.x & 63;
+  const bool     valid = l < P.L;
+  int            code  = -1;
+  bool           unsorted = false;
+  if (valid) {
+    const double pos[3] = {X[l], Y[l], Z[l]};
+    int          o[3];
+    bool         reach = true;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const int c = ibm_owner_cell(P, d, ibm_index(P, d, pos[d]));
+      if (c >= P.lo[d] && c < P.lo[d] + P.n[d]) o[d] = 0;
+      else if (D.peer_lo[d] && c >= D.lo_beg[d] && c < D.lo_end[d]) o[d] = -1;
+      else if (D.peer_hi[d] && c >= D.hi_beg[d] && c < D.hi_end[d]) o[d] = 1;
+      else o[d] = 0, reach = false;
+    }
+    code = reach ? (o[2] + 1) * 9 + (o[1] + 1) * 3 + (o[0] + 1) : -1;
+    dest[l]  = code;
+    unsorted = l > 0 && gid[l - 1] >= gid[l];
+  }
+  unsigned long long todo = __ballot(valid);
+  while (todo) {  // wave-uniform: one round per distinct code in the wave
+    const int                leader = __ffsll((long long)todo) - 1;
+    const int                c      = __shfl(code, leader, 64);
+    const unsigned long long same   = __ballot(valid && code == c);
+    if (lane == leader) atomicAdd(&cnt[c < 0 ? 27 : c], __popcll(same));
+    todo &= ~same;
+  }
+  if (__ballot(unsorted) != 0ull && lane == 0) atomicOr(&cnt[28], 1);
+  const unsigned long long stay = __ballot(valid && code == 13);
+  if (lane == 0) wstay[threadIdx.x >> 6] = __popcll(stay);
+  __syncthreads();
+  if (threadIdx.x == 0) blockstay[blockIdx.x] = wstay[0] + wstay[1] + wstay[2] + wstay[3];
+}
+
+// Stayers keep their order: index = blockoff[block] (k_ibm_scan over blockstay) + the stayers of the waves before + those of the lanes before
+// (ballot).  stay[f*Ls + i], f = X, Y, Z, number, attributes.  Leavers become records of per = 4 + nattr doubles in buf, grouped by code through
+// leaveoff[code] and one cursor per code (the order inside a group is free: the receiver sorts by number).
+__global__ void __launch_bounds__(256) k_ibm_split(int64_t Lo, int64_t Ls, int nattr, const int *__restrict__ dest, const int *__restrict__ blockoff, const int *__restrict__ leaveoff, int *__restrict__ cursor, const double *__restrict__ X,
+                                                   const double *__restrict__ Y, const double *__restrict__ Z, const int64_t *__restrict__ gid, const double *__restrict__ attr, double *__restrict__ stay, double *__restrict__ buf)
+{
+  __shared__ int wstay[4];
+  const int64_t  l     = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int      lane  = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int      code  = l < Lo ? dest[l] : -1;
+  const unsigned long long stays = __ballot(code == 13);
+  if (lane == 0) wstay[wave] = __popcll(stays);
+  __syncthreads();
+  if (l >= Lo) return;
+  const double g = (double)gid[l];
+  if (code == 13) {
+    int64_t i = blockoff[blockIdx.x] + __popcll(stays & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) i += wstay[w];
+    if (i >= Ls) return;  // cannot happen: the counts come from the same dest[]
+    stay[i]          = X[l];
+    stay[Ls + i]     = Y[l];
+    stay[2 * Ls + i] = Z[l];
+    stay[3 * Ls + i] = g;
+    for (int a = 0; a < nattr; ++a) stay[(4 + a) * Ls + i] = attr[(int64_t)a * Lo + l];
+  } else if (code >= 0) {
+    const int     per = 4 + nattr;
+    const int64_t j   = leaveoff[code] + atomicAdd(&cursor[code], 1);
+    if (j >= leaveoff[code + 1]) return;  // cannot happen either
+    buf[per * j + 0] = X[l];
+    buf[per * j + 1] = Y[l];
+    buf[per * j + 2] = Z[l];
+    buf[per * j + 3] = g;
+    for (int a = 0; a < nattr; ++a) buf[per * j + 4 + a] = attr[(int64_t)a * Lo + l];
+  }
+}
+
+// Arrivals (A records of per doubles, as received) -> arr[f*A + r], r = the rank of the record's number among all arrivals (ties, which distinct
+// numbers do not make, by record index).  Rank by counting as k_ibm_sort_bins does for a bin, the numbers tiled through LDS: O(A^2).
+__global__ void __launch_bounds__(256) k_ibm_rank_arrivals(int A, int per, const double *__restrict__ buf, double *__restrict__ arr)
+{
+  __shared__ double tile[256];
+  const int    e  = blockIdx.x * 256 + threadIdx.x;
+  const double ge = e < A ? buf[(int64_t)per * e + 3] : 0.;
+  int          rank = 0;
+  for (int base = 0; base < A; base += 256) {
+    __syncthreads();
+    tile[threadIdx.x] = base + (int)threadIdx.x < A ? buf[(int64_t)per * (base + threadIdx.x) + 3] : 0.;
+    __syncthreads();
+    const int n = min(256, A - base);
+    for (int o = 0; o < n; ++o) rank += (tile[o] < ge) || (tile[o] == ge && base + o < e);
+  }
+  if (e >= A) return;
+  for (int f = 0; f < per; ++f) arr[(int64_t)f * A + rank] = buf[(int64_t)per * e + f];
+}
+
+// number of entries of the ascending key[0..n) below v (or, with_equal, not above it)
+__device__ __forceinline__ int64_t ibm_count_below(const double *__restrict__ key, int64_t n, double v, bool with_equal)
+{
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (key[mid] < v || (with_equal && key[mid] == v)) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// Stayers and sorted arrivals, both ascending in the number, into one ascending list without a sort: a stayer moves up by the arrivals below it, an
+// arrival by the stayers below it (ties would go stayer first, so the indices are a permutation whatever the numbers are).
+// pos[f*Ln + i] f = X, Y, Z; gid[i]; attr[a*Ln + i]
+__global__ void k_ibm_merge(int64_t Ls, int64_t A, int nattr, const double *__restrict__ stay, const double *__restrict__ arr, double *__restrict__ pos, int64_t *__restrict__ gid, double *__restrict__ attr)
+{
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, Ln = Ls + A;
+  if (t >= Ln) return;
+  const bool    st  = t < Ls;
+  const int64_t i   = st ? t : t - Ls, n = st ? Ls : A;
+  const double *src = st ? stay : arr;
+  const double  g   = src[3 * n + i];
+  const int64_t to  = i + (st ? ibm_count_below(arr + 3 * A, A, g, false) : ibm_count_below(stay + 3 * Ls, Ls, g, true));
+  pos[to]          = src[i];
+  pos[Ln + to]     = src[n + i];
+  pos[2 * Ln + to] = src[2 * n + i];
+  gid[to]          = (int64_t)g;
+  for (int a = 0; a < nattr; ++a) attr[(int64_t)a * Ln + to] = src[(4 + a) * n + i];
+}
+
+// ---- a body in prescribed rigid motion (fl_ibm_rigid_pose) -----------------------------------------------------------------------------
+struct PoseP {
+  double c0[3], c[3], R[9], v[3], w[3];  // reference centre, centre now, rotation matrix (row-major), velocity of the centre, angular velocity
+};
+// X = c + R (X0 - c0);  Ut = v + w x (X - c), Ut[c*L + l].  Either output may be absent.
+__global__ void k_ibm_rigid_pose(int64_t L, PoseP P, const double *__restrict__ X0, const double *__restrict__ Y0, const double *__restrict__ Z0, double *__restrict__ X, double *__restrict__ Y, double *__restrict__ Z, double *__restrict__ Ut)
+{
+  const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= L) return;
+  const double r0[3] = {X0[l] - P.c0[0], Y0[l] - P.c0[1], Z0[l] - P.c0[2]};
+  double       r[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) r[a] = P.R[3 * a] * r0[0] + P.R[3 * a + 1] * r0[1] + P.R[3 * a + 2] * r0[2];
+  if (X) {
+    X[l] = P.c[0] + r[0];
+    Y[l] = P.c[1] + r[1];
+    Z[l] = P.c[2] + r[2];
+  }
+  if (Ut) {
+    Ut[l]         = P.v[0] + (P.w[1] * r[2] - P.w[2] * r[1]);
+    Ut[L + l]     = P.v[1] + (P.w[2] * r[0] - P.w[0] * r[2]);
+    Ut[2 * L + l] = P.v[2] + (P.w[0] * r[1] - P.w[1] * r[0]);
+  }
+}
+
 }  // namespace fl
 
 using namespace fl;
@@ -454,6 +632,15 @@ struct fl_ibm {
   int64_t     maskcap = 0;
   double     *sbuf = nullptr, *rbuf = nullptr, *Ui = nullptr, *Fi = nullptr, *cbuf = nullptr;  // message records out / in, U and (F, dV) of own + ghost, counts
   int64_t     sbufcap = 0, rbufcap = 0, Uicap = 0, Ficap = 0;
+  // migration (fl_ibm_migrate): neighbours' cell ranges (exchanged once), staging buffers, the attributes of the last call
+  bool        nbr_known = false;
+  DestP       D;
+  int64_t     gidowncap = 0;
+  int        *dest = nullptr, *bstay = nullptr, *boff = nullptr, *mcnt = nullptr;  // per marker; per block of 256 (count, offset); MIG_NCNT counts + 28 offsets + 27 cursors
+  int64_t    *gidtmp = nullptr;
+  double     *stay = nullptr, *arr = nullptr, *mpos = nullptr, *attr = nullptr, *attrtmp = nullptr, *nbuf = nullptr;
+  int64_t     destcap = 0, bstaycap = 0, boffcap = 0, gidtmpcap = 0, staycap = 0, arrcap = 0, mposcap = 0, attrcap = 0, attrtmpcap = 0;
+  int         nattr = 0;
 };
 
 static int ibm_rebin(fl_ibm *m)
@@ -716,6 +903,7 @@ static int ibm_route(fl_ibm *m, int64_t Lo, const double *X, const double *Y, co
   FL_HIP(hipMemcpyAsync(m->cstart, cstart.data(), sizeof(int) * ((size_t)Lo + 1), hipMemcpyHostToDevice, s));
   if (first && m->has_gid && Lo > 0) {
     if (fl_dev_alloc(h, (void **)&m->gid_own, sizeof(int64_t) * (size_t)Lo, false)) return FL_ERR_MEM;
+    m->gidowncap = Lo;
     FL_HIP(hipMemcpyAsync(m->gid_own, gid_new, sizeof(int64_t) * (size_t)Lo, hipMemcpyDeviceToDevice, s));
   }
   // the counts of the copies, one double per offset that has a rank behind it
@@ -848,6 +1036,202 @@ extern "C" int fl_ibm_update(fl_ibm *m, const double *X, const double *Y, const 
   return ibm_rebin(m);
 }
 
+// ---- owner-rank markers: migration ----------------------------------------------------------------------------------------------------
+
+// the cell ranges of the blocks behind the six faces: every rank tells its face neighbours (lo, n) of its block, once per set
+static int ibm_neighbour_ranges(fl_ibm *m)
+{
+  fl_poisson *h = m->gp;
+  hipStream_t s = h->stream;
+  const IbmP &P = m->P;
+  DestP      &D = m->D;
+  for (int d = 0; d < 3; ++d) {
+    D.peer_lo[d] = m->R.peer_lo[d];
+    D.peer_hi[d] = m->R.peer_hi[d];
+    D.lo_beg[d] = D.lo_end[d] = D.hi_beg[d] = D.hi_end[d] = 0;
+  }
+  m->nbr_known = true;
+  if (!ibm_split(h)) return 0;
+  if (!m->nbuf && fl_dev_alloc(h, (void **)&m->nbuf, sizeof(double) * 6 * 28, true)) return FL_ERR_MEM;
+  double hb[6 * 28] = {0.};
+  for (int d = 0; d < 3; ++d) hb[d] = (double)P.lo[d], hb[3 + d] = (double)P.n[d];
+  FL_HIP(hipMemcpyAsync(m->nbuf, hb, sizeof(double) * 6, hipMemcpyHostToDevice, s));
+  const int        face[6] = {12, 14, 10, 16, 4, 22};  // ascending below: 4, 10, 12, 14, 16, 22
+  std::vector<Msg> msgs;
+  for (int code = 0; code < 27; ++code)
+    for (int f = 0; f < 6; ++f)
+      if (face[f] == code && m->peer[code] >= 0) msgs.push_back({m->peer[code], m->nbuf, nullptr, 6, code, 26 - code});
+  for (int code = 26; code >= 0; --code)
+    for (int f = 0; f < 6; ++f)
+      if (face[f] == code && m->peer[code] >= 0) msgs.push_back({m->peer[code], nullptr, m->nbuf + 6 * (1 + code), 6, code, 26 - code});
+  FL_CHK(h->comm.exchange(s, msgs));
+  FL_HIP(hipMemcpyAsync(hb, m->nbuf, sizeof(hb), hipMemcpyDeviceToHost, s));
+  FL_HIP(hipStreamSynchronize(s));
+  for (int d = 0; d < 3; ++d) {
+    const int step = d == 0 ? 1 : (d == 1 ? 3 : 9), lo = 13 - step, hi = 13 + step;
+    if (m->peer[lo] >= 0) D.lo_beg[d] = (int)hb[6 * (1 + lo) + d], D.lo_end[d] = D.lo_beg[d] + (int)hb[6 * (1 + lo) + 3 + d];
+    if (m->peer[hi] >= 0) D.hi_beg[d] = (int)hb[6 * (1 + hi) + d], D.hi_end[d] = D.hi_beg[d] + (int)hb[6 * (1 + hi) + 3 + d];
+  }
+  return 0;
+}
+
+extern "C" int fl_ibm_migrate(fl_ibm *m, const double *X, const double *Y, const double *Z, int nattr, const double *attr_dev, int64_t *L_local_new, int64_t moved[2])
+{
+  if (!m) return FL_ERR_ARG_NULL;
+  if (!m->owned || !m->has_gid) return FL_ERR_ARG_WRONGSTATE;  // has_gid was voted at create: the same on every rank
+  fl_poisson   *h  = m->gp;
+  hipStream_t   s  = h->stream;
+  const int64_t Lo = m->Lo;
+  FL_HIP(hipSetDevice(h->device));
+  const bool nattr_ok = nattr >= 0 && nattr <= 8;
+  const bool null_arg = !L_local_new || !moved || (Lo > 0 && (!X || !Y || !Z || (nattr_ok && nattr > 0 && !attr_dev)));
+  double     v[2]     = {nattr_ok ? 0. : 1., null_arg ? 1. : 0.};
+  FL_CHK(ibm_vote(h, v, 2));
+  if (v[0] > 0.) return FL_ERR_ARG_OUTOFRANGE;
+  if (v[1] > 0.) return FL_ERR_ARG_NULL;
+  if (!m->nbr_known) FL_CHK(ibm_neighbour_ranges(m));
+  // 1. where every own marker goes; the 27 counts, the two flags
+  const int nb = (int)((Lo + 255) / 256);
+  if (!m->mcnt && fl_dev_alloc(h, (void **)&m->mcnt, sizeof(int) * (MIG_NCNT + 28 + 27), true)) return FL_ERR_MEM;
+  int hc[MIG_NCNT] = {0};
+  if (Lo > 0) {
+    FL_CHK(ibm_reserve(h, &m->dest, &m->destcap, Lo));
+    FL_CHK(ibm_reserve(h, &m->bstay, &m->bstaycap, nb + 1));
+    FL_CHK(ibm_reserve(h, &m->boff, &m->boffcap, nb + 1));
+    FL_HIP(hipMemsetAsync(m->mcnt, 0, sizeof(int) * (MIG_NCNT + 28 + 27), s));
+    IbmP P = m->P;
+    P.L    = Lo;
+    hipLaunchKernelGGL(k_ibm_dest, dim3(nb), dim3(256), 0, s, P, m->D, X, Y, Z, (const int64_t *)m->gid_own, m->dest, m->mcnt, m->bstay);
+    FL_HIP(hipGetLastError());
+    FL_HIP(hipMemcpyAsync(hc, m->mcnt, sizeof(hc), hipMemcpyDeviceToHost, s));
+    FL_HIP(hipStreamSynchronize(s));
+  }
+  // 2. the votes, then the counts to and from the neighbours (ibm_route's count messages)
+  double bad[2] = {hc[28] ? 1. : 0., hc[27] > 0 ? 1. : 0.};
+  FL_CHK(ibm_vote(h, bad, 2));
+  if (bad[0] > 0.) return FL_ERR_ARG_WRONGSTATE;
+  if (bad[1] > 0.) return FL_ERR_ARG_OUTOFRANGE;
+  int     lcnt[27], loff[28], acnt[27], aoff[28];
+  int64_t nleave = 0, A = 0;
+  for (int code = 0; code < 27; ++code) {
+    lcnt[code] = (code != 13 && m->peer[code] >= 0) ? hc[code] : 0;  // a code without a peer holds nothing: k_ibm_dest never forms it
+    loff[code] = (int)nleave;
+    nleave += lcnt[code];
+    acnt[code] = 0;
+  }
+  loff[27] = (int)nleave;
+  if (ibm_split(h)) {
+    double hd[54];
+    for (int code = 0; code < 27; ++code) hd[code] = (double)lcnt[code], hd[27 + code] = 0.;
+    FL_HIP(hipMemcpyAsync(m->cbuf, hd, sizeof(hd), hipMemcpyHostToDevice, s));
+    std::vector<Msg> msgs;
+    for (int code = 0; code < 27; ++code)
+      if (m->peer[code] >= 0) msgs.push_back({m->peer[code], m->cbuf + code, nullptr, 1, code, 26 - code});
+    for (int code = 26; code >= 0; --code)
+      if (m->peer[code] >= 0) msgs.push_back({m->peer[code], nullptr, m->cbuf + 27 + code, 1, code, 26 - code});
+    FL_CHK(h->comm.exchange(s, msgs));
+    FL_HIP(hipMemcpyAsync(hd, m->cbuf, sizeof(hd), hipMemcpyDeviceToHost, s));
+    FL_HIP(hipStreamSynchronize(s));
+    for (int code = 0; code < 27; ++code) acnt[code] = m->peer[code] >= 0 ? (int)hd[27 + code] : 0;
+  }
+  for (int code = 0; code < 27; ++code) aoff[code] = (int)A, A += acnt[code];
+  aoff[27]          = (int)A;
+  const int64_t Ls = Lo - nleave, Ln = Ls + A;
+  if (Ln > (int64_t)1 << 27) return FL_ERR_ARG_OUTOFRANGE;
+  m->nattr = nattr;
+  if (nleave == 0 && A == 0) {
+    // nothing crosses a face of this block: the list stays as it is, only the attributes are kept for fl_ibm_owned_fetch
+    if (nattr > 0 && Lo > 0) {
+      FL_CHK(ibm_reserve(h, &m->attr, &m->attrcap, (int64_t)nattr * Lo));
+      FL_HIP(hipMemcpyAsync(m->attr, attr_dev, sizeof(double) * (size_t)nattr * (size_t)Lo, hipMemcpyDeviceToDevice, s));
+    }
+    *L_local_new = Lo;
+    moved[0] = moved[1] = 0;
+    return ibm_route(m, Lo, X, Y, Z, nullptr, false);
+  }
+  const int per = 4 + nattr;
+  FL_CHK(ibm_reserve(h, &m->sbuf, &m->sbufcap, per * nleave));
+  FL_CHK(ibm_reserve(h, &m->rbuf, &m->rbufcap, per * A));
+  FL_CHK(ibm_reserve(h, &m->stay, &m->staycap, per * Ls));
+  FL_CHK(ibm_reserve(h, &m->arr, &m->arrcap, per * A));
+  FL_CHK(ibm_reserve(h, &m->mpos, &m->mposcap, 3 * Ln));
+  FL_CHK(ibm_reserve(h, &m->gidtmp, &m->gidtmpcap, Ln));
+  FL_CHK(ibm_reserve(h, &m->attrtmp, &m->attrtmpcap, (int64_t)nattr * Ln));
+  // 3. + 4. stayers compacted in order, leavers packed by offset
+  if (Lo > 0) {
+    int *leaveoff = m->mcnt + MIG_NCNT, *cursor = m->mcnt + MIG_NCNT + 28;
+    FL_HIP(hipMemcpyAsync(leaveoff, loff, sizeof(loff), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_ibm_scan, dim3(1), dim3(256), 0, s, m->bstay, m->boff, nb);
+    hipLaunchKernelGGL(k_ibm_split, dim3(nb), dim3(256), 0, s, Lo, Ls, nattr, m->dest, m->boff, leaveoff, cursor, X, Y, Z, (const int64_t *)m->gid_own, attr_dev, m->stay, m->sbuf);
+    FL_HIP(hipGetLastError());
+  }
+  // 5. one exchange: a message per offset, ibm_msgs' ordering rule
+  {
+    std::vector<Msg> msgs;
+    for (int code = 0; code < 27; ++code)
+      if (m->peer[code] >= 0 && lcnt[code] > 0) msgs.push_back({m->peer[code], m->sbuf + (int64_t)per * loff[code], nullptr, (int64_t)per * lcnt[code], code, 26 - code});
+    for (int code = 26; code >= 0; --code)
+      if (m->peer[code] >= 0 && acnt[code] > 0) msgs.push_back({m->peer[code], nullptr, m->rbuf + (int64_t)per * aoff[code], (int64_t)per * acnt[code], code, 26 - code});
+    FL_CHK(h->comm.exchange(s, msgs));
+  }
+  // 6. + 7. arrivals by number, then both ascending lists into one
+  if (A > 0) hipLaunchKernelGGL(k_ibm_rank_arrivals, dim3((unsigned)((A + 255) / 256)), dim3(256), 0, s, (int)A, per, m->rbuf, m->arr);
+  if (Ln > 0) hipLaunchKernelGGL(k_ibm_merge, dim3((unsigned)((Ln + 255) / 256)), dim3(256), 0, s, Ls, A, nattr, m->stay, m->arr, m->mpos, m->gidtmp, m->attrtmp);
+  FL_HIP(hipGetLastError());
+  std::swap(m->gid_own, m->gidtmp);
+  std::swap(m->gidowncap, m->gidtmpcap);
+  std::swap(m->attr, m->attrtmp);
+  std::swap(m->attrcap, m->attrtmpcap);
+  *L_local_new = Ln;
+  moved[0]     = nleave;
+  moved[1]     = A;
+  // 8. ghost copies and bins of the new own list
+  return ibm_route(m, Ln, m->mpos, m->mpos + Ln, m->mpos + 2 * Ln, nullptr, false);
+}
+
+extern "C" int fl_ibm_owned_fetch(fl_ibm *m, int64_t cap, double *X, double *Y, double *Z, int64_t *gid, int nattr, double *attr_out)
+{
+  if (!m) return FL_ERR_ARG_NULL;
+  if (!m->owned) return FL_ERR_ARG_WRONGSTATE;
+  if (cap < m->Lo) return FL_ERR_ARG_SIZ;
+  if (nattr < 0 || nattr > m->nattr) return FL_ERR_ARG_OUTOFRANGE;
+  if (gid && !m->has_gid) return FL_ERR_ARG_WRONGSTATE;
+  if (nattr > 0 && !attr_out && m->Lo > 0) return FL_ERR_ARG_NULL;
+  fl_poisson  *h = m->gp;
+  hipStream_t  s = h->stream;
+  const size_t n = (size_t)m->Lo;
+  FL_HIP(hipSetDevice(h->device));
+  if (n == 0) return FL_SUCCESS;
+  if (X) FL_HIP(hipMemcpyAsync(X, m->X, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+  if (Y) FL_HIP(hipMemcpyAsync(Y, m->Y, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+  if (Z) FL_HIP(hipMemcpyAsync(Z, m->Z, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+  if (gid) FL_HIP(hipMemcpyAsync(gid, m->gid_own, sizeof(int64_t) * n, hipMemcpyDeviceToDevice, s));
+  if (nattr > 0) FL_HIP(hipMemcpyAsync(attr_out, m->attr, sizeof(double) * n * (size_t)nattr, hipMemcpyDeviceToDevice, s));
+  return FL_SUCCESS;
+}
+
+extern "C" int fl_ibm_rigid_pose(fl_poisson *h, int64_t L, const double *X0, const double *Y0, const double *Z0, const double centre0[3], const double centre[3], const double rotvec[3], const double velocity[3], const double omega[3],
+                                 double *X, double *Y, double *Z, double *Ut)
+{
+  if (!h || !centre0 || !centre || !rotvec || !velocity || !omega) return FL_ERR_ARG_NULL;
+  if (L < 0) return FL_ERR_ARG_OUTOFRANGE;
+  if (L == 0) return FL_SUCCESS;
+  if (!X0 || !Y0 || !Z0 || (!X != !Y) || (!X != !Z) || (!X && !Ut)) return FL_ERR_ARG_NULL;
+  PoseP P;
+  for (int a = 0; a < 3; ++a) P.c0[a] = centre0[a], P.c[a] = centre[a], P.v[a] = velocity[a], P.w[a] = omega[a];
+  // Rodrigues: R = cos(th) I + sin(th) [k]x + (1 - cos(th)) k k^T, rotvec = th k; formed on the host so that every rank multiplies by the same nine numbers
+  const double th = std::sqrt(rotvec[0] * rotvec[0] + rotvec[1] * rotvec[1] + rotvec[2] * rotvec[2]);
+  const double k[3] = {th > 0. ? rotvec[0] / th : 0., th > 0. ? rotvec[1] / th : 0., th > 0. ? rotvec[2] / th : 0.};
+  const double cs = std::cos(th), sn = std::sin(th);
+  const double K[9] = {0., -k[2], k[1], k[2], 0., -k[0], -k[1], k[0], 0.};
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) P.R[3 * a + b] = (a == b ? cs : 0.) + sn * K[3 * a + b] + (1. - cs) * k[a] * k[b];
+  FL_HIP(hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_ibm_rigid_pose, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, h->stream, L, P, X0, Y0, Z0, X, Y, Z, Ut);
+  FL_HIP(hipGetLastError());
+  return FL_SUCCESS;
+}
+
 // ---- owner-rank markers: per call (stream-ordered; the host waits only where the host transport itself does) ---------------------------
 
 static int ibm_interp_owned(fl_ibm *m, int ncomp, const double *u, double *U)
@@ -935,7 +1319,8 @@ extern "C" int fl_ibm_destroy(fl_ibm *m)
   if (m->gp) (void)hipStreamSynchronize(m->gp->stream);
   for (void *p : {(void *)m->X, (void *)m->Y, (void *)m->Z, (void *)m->w, (void *)m->i0, (void *)m->cnt, (void *)m->off, (void *)m->list, (void *)m->scratch, (void *)m->active, (void *)m->nact_dev, (void *)m->xcg[0],
                   (void *)m->xcg[1], (void *)m->xcg[2], (void *)m->gid_own, (void *)m->gid, (void *)m->mask, (void *)m->sendlist, (void *)m->cstart, (void *)m->clist, (void *)m->sbuf, (void *)m->rbuf, (void *)m->Ui,
-                  (void *)m->Fi, (void *)m->cbuf})
+                  (void *)m->Fi, (void *)m->cbuf, (void *)m->dest, (void *)m->bstay, (void *)m->boff, (void *)m->mcnt, (void *)m->gidtmp, (void *)m->stay, (void *)m->arr, (void *)m->mpos, (void *)m->attr,
+                  (void *)m->attrtmp, (void *)m->nbuf})
     if (p) (void)hipFree(p);
   delete m;
   return FL_SUCCESS;

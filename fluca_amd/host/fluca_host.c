@@ -1056,11 +1056,14 @@ static FlErrorCode NSSetUp_Body(NS ns) /* nsbasic.c:153-274, restricted to what 
   return 0;
 }
 
+static FlErrorCode ibm_move(NS ns);
+
 static FlErrorCode NSStep_Body(NS ns) /* nsbasic.c:276-299 */
 {
   if (!ns) return E_ARG_NULL;
   if (!ns->setupcalled) return E_ARG_WRONGSTATE;
   if (!ns->ops->step) return E_SUP;
+  if (ns->ibm && ns->ibm_motion) FLCHK(ibm_move(ns)); /* the body in prescribed motion at t + dt, before the forcing term is formed */
   FLCHK(ns->ops->step(ns)); /* VecCopy(sol, sol0) + the type's step */
   if (ns->reason >= 0) {
     ++ns->step;
@@ -1358,6 +1361,14 @@ static void ibm_free_own(NS ns)
     if (ns->ibm_own[q]) fl_free(ns->device, ns->ibm_own[q]);
     ns->ibm_own[q] = NULL;
   }
+  /* ... and what a moving body added */
+  if (ns->ibm_ref) fl_free(ns->device, ns->ibm_ref);
+  if (ns->ibm_mv) fl_free(ns->device, ns->ibm_mv);
+  ns->ibm_ref = ns->ibm_mv = NULL;
+  ns->ibm_cap = ns->ibm_Ucap = 0;
+  ns->ibm_motion     = NULL;
+  ns->ibm_motion_ctx = NULL;
+  ns->ibm_X[0] = ns->ibm_X[1] = ns->ibm_X[2] = NULL;
 }
 
 /* -ns_ibm_marker_distribution owner: this rank's share of the replicated arrays, gathered into arrays the NS owns -- ibm_own[0..2] positions, [3] volumes,
@@ -1420,6 +1431,8 @@ FlErrorCode NSSetImmersedBoundary(NS ns, int kind, int64_t L, const double *X_de
     ns->ibm_L  = Lloc;
     ns->ibm_dV = (const double *)ns->ibm_own[3];
     ns->ibm_Ut = (const double *)ns->ibm_own[4];
+    for (int d = 0; d < 3; ++d) ns->ibm_X[d] = (const double *)ns->ibm_own[d];
+    ns->ibm_Ucap = Lloc;
     return 0;
   }
   FLABI(fl_ibm_create(ns->poisson, kind, L, X_dev, Y_dev, Z_dev, &ns->ibm));
@@ -1428,6 +1441,107 @@ FlErrorCode NSSetImmersedBoundary(NS ns, int kind, int64_t L, const double *X_de
   ns->ibm_L  = L;
   ns->ibm_dV = dV_dev;
   ns->ibm_Ut = Utarget_dev;
+  ns->ibm_X[0] = X_dev, ns->ibm_X[1] = Y_dev, ns->ibm_X[2] = Z_dev;
+  ns->ibm_Ucap = L;
+  return 0;
+}
+
+/* room for n markers in ibm_ref (4 n) and ibm_mv (6 n); the old contents are not kept */
+static FlErrorCode ibm_motion_reserve(NS ns, int64_t n)
+{
+  if (ns->ibm_ref && ns->ibm_mv && n <= ns->ibm_cap) return 0;
+  if (ns->ibm_ref) fl_free(ns->device, ns->ibm_ref);
+  if (ns->ibm_mv) fl_free(ns->device, ns->ibm_mv);
+  ns->ibm_ref = ns->ibm_mv = NULL;
+  ns->ibm_cap = 0;
+  const int64_t cap = n + n / 4 + 64;
+  void         *a = NULL, *b = NULL;
+  FLABI(fl_malloc(ns->device, sizeof(double) * 4 * (size_t)cap, &a));
+  ns->ibm_ref = (double *)a;
+  FLABI(fl_malloc(ns->device, sizeof(double) * 6 * (size_t)cap, &b));
+  ns->ibm_mv  = (double *)b;
+  ns->ibm_cap = cap;
+  return 0;
+}
+
+FlErrorCode NSSetImmersedBoundaryMotion(NS ns, const double centre0[3], NSBodyMotionFn fn, void *ctx)
+{
+  if (!ns) return E_ARG_NULL;
+  if (!ns->setupcalled || !ns->ibm) return E_ARG_WRONGSTATE;
+  if (!fn) { /* at rest where it is: the set keeps the last positions, the target is zero */
+    if (ns->ibm_motion) ns->ibm_Ut = NULL;
+    ns->ibm_motion     = NULL;
+    ns->ibm_motion_ctx = NULL;
+    return 0;
+  }
+  if (!centre0) return E_ARG_NULL;
+  if (!ns->ibm_ref) {
+    /* the reference pose: the markers as NSSetImmersedBoundary received them, and their volumes, in arrays that follow the markers from now on */
+    const int64_t L = ns->ibm_L;
+    FLCHK(ibm_motion_reserve(ns, L));
+    if (L > 0) {
+      for (int d = 0; d < 3; ++d) FLABI(fl_vec_lincomb(ns->poisson, L, 1., ns->ibm_X[d], 0., NULL, ns->ibm_ref + d * L));
+      FLABI(fl_vec_lincomb(ns->poisson, L, 1., ns->ibm_dV, 0., NULL, ns->ibm_ref + 3 * L));
+    }
+    ns->ibm_dV = ns->ibm_ref + 3 * L;
+    if (ns->ibm_owner) { /* the copies made at NSSetImmersedBoundary are in an order the first migration ends */
+      FLABI(fl_poisson_synchronize(ns->poisson));
+      for (int q = 0; q < 5; ++q) {
+        if (ns->ibm_own[q]) fl_free(ns->device, ns->ibm_own[q]);
+        ns->ibm_own[q] = NULL;
+      }
+      ns->ibm_X[0] = ns->ibm_X[1] = ns->ibm_X[2] = NULL;
+    }
+  }
+  for (int d = 0; d < 3; ++d) ns->ibm_centre0[d] = centre0[d];
+  ns->ibm_motion     = fn;
+  ns->ibm_motion_ctx = ctx;
+  return 0;
+}
+
+/* the moving body at t + dt: pose from the callback, markers moved (and, owner-rank markers, handed from rank to rank), target velocities */
+static FlErrorCode ibm_move(NS ns)
+{
+  double centre[3] = {0., 0., 0.}, rotvec[3] = {0., 0., 0.}, vel[3] = {0., 0., 0.}, omega[3] = {0., 0., 0.};
+  FlErrorCode rc = ns->ibm_motion(ns->t + ns->dt, centre, rotvec, vel, omega, ns->ibm_motion_ctx);
+  if (ns->mesh->size > 1) { /* every rank leaves the step together */
+    double v[2] = {rc ? 1. : 0., (double)rc};
+    FLABI(fl_poisson_allreduce_sum(ns->poisson, v, 2));
+    if (!rc && v[0] > 0.) rc = (FlErrorCode)(v[1] / v[0] + (v[1] >= 0. ? 0.5 : -0.5));
+  }
+  if (rc) return rc;
+  fl_poisson *h = ns->poisson;
+  int64_t     L = ns->ibm_L;
+  double     *ref = ns->ibm_ref, *pos = ns->ibm_mv;
+  if (!ns->ibm_owner) {
+    double *Ut = ns->ibm_mv + 3 * ns->ibm_cap;
+    FLABI(fl_ibm_rigid_pose(h, L, ref, ref + L, ref + 2 * L, ns->ibm_centre0, centre, rotvec, vel, omega, pos, pos + L, pos + 2 * L, Ut));
+    FLABI(fl_ibm_update(ns->ibm, pos, pos + L, pos + 2 * L));
+    ns->ibm_Ut = Ut;
+    return 0;
+  }
+  int64_t Ln = 0, moved[2] = {0, 0};
+  FLABI(fl_ibm_rigid_pose(h, L, ref, ref + L, ref + 2 * L, ns->ibm_centre0, centre, rotvec, vel, omega, pos, pos + L, pos + 2 * L, NULL));
+  FLABI(fl_ibm_migrate(ns->ibm, L ? pos : NULL, L ? pos + L : NULL, L ? pos + 2 * L : NULL, 4, L ? ref : NULL, &Ln, moved));
+  /* the set holds positions, numbers and the four attributes now: the NS's arrays follow the new count */
+  FLCHK(ibm_motion_reserve(ns, Ln));
+  ref = ns->ibm_ref;
+  pos = ns->ibm_mv;
+  FLABI(fl_ibm_owned_fetch(ns->ibm, ns->ibm_cap, NULL, NULL, NULL, NULL, 4, ref));
+  if (Ln > ns->ibm_Ucap) {
+    void *u = NULL;
+    FLABI(fl_poisson_synchronize(h));
+    if (ns->ibm_U) fl_free(ns->device, ns->ibm_U);
+    ns->ibm_U = NULL;
+    FLABI(fl_malloc(ns->device, sizeof(double) * 3 * (size_t)ns->ibm_cap, &u));
+    ns->ibm_U    = (double *)u;
+    ns->ibm_Ucap = ns->ibm_cap;
+  }
+  double *Ut = ns->ibm_mv + 3 * ns->ibm_cap;
+  FLABI(fl_ibm_rigid_pose(h, Ln, ref, ref + Ln, ref + 2 * Ln, ns->ibm_centre0, centre, rotvec, vel, omega, NULL, NULL, NULL, Ut));
+  ns->ibm_L  = Ln;
+  ns->ibm_dV = ref + 3 * Ln;
+  ns->ibm_Ut = Ut;
   return 0;
 }
 

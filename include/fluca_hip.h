@@ -162,7 +162,7 @@ int fl_poisson_allreduce_sum(fl_poisson *h, double *host_vals, int n);
 int fl_poisson_sizes(const fl_poisson *h, int64_t out[4]);
 void fl_ksp_opts_default(fl_ksp_opts *o); /* PETSc defaults + cg/jacobi/preconditioned norm */
 const char *fl_version(void);
-#define FL_ABI_VERSION 7
+#define FL_ABI_VERSION 8
 int fl_abi_version(void); /* the FL_ABI_VERSION the library was built with */
 
 /* ---- device memory for hosts that have no allocator of their own (the C host mirror, a PETSc host without HIP Vecs) - */
@@ -461,7 +461,7 @@ int fl_ibm_owned_select(fl_poisson *grid_from, int kind, int64_t L, const double
  * axis at most).  On one rank: the bits of fl_ibm_create.
  * On such a set fl_ibm_update / fl_ibm_interp / fl_ibm_spread are collective too; L is L_local there (U, F, dV indexed by local marker):
  *   update  routes the copies anew; a marker that has left the block is the voted FL_ERR_ARG_OUTOFRANGE and the set stays as it was
- *           (markers do not migrate: re-partition with fl_ibm_owned_select and create a new set)
+ *           (fl_ibm_update never moves a marker to another rank: fl_ibm_migrate below does)
  *   interp  own + ghost markers on the owned cells, the ghosts' partial sums go back to the owners (8 bytes per copy and component), which
  *           add them in a fixed order; no all-reduce
  *   spread  F and dV of the copies go out (8 (ncomp + 1) bytes per copy), every rank spreads own + ghost markers into its own cells */
@@ -469,6 +469,33 @@ int fl_ibm_create_owned(fl_poisson *grid_from, int kind, int64_t L_local, const 
 /* out = { markers owned, ghost markers held, copies of own markers held by other ranks, bytes this rank sends per interp and component,
  * bytes this rank sends per spread of three components }.  FL_ERR_ARG_WRONGSTATE on a replicated set. */
 int fl_ibm_owned_counts(fl_ibm *m, int64_t out[5]);
+/* MIGRATION.  COLLECTIVE, owned sets created WITH marker numbers (gid) only.  X, Y, Z (device): new positions of the Lo own markers in the set's
+ * order.  attr_dev (device): nattr x Lo doubles, attr[a*Lo + l] (0 <= nattr <= 8; NULL when 0): whatever has to travel with a marker (volume,
+ * reference position ...).  A marker whose owner cell (the rule above) now lies in one of the <= 26 neighbouring blocks moves there with position,
+ * number and attributes; a position on a periodic axis travels unchanged, not wrapped.  Afterwards every rank's own markers are in ASCENDING marker
+ * number, the ghost copies are routed anew and the bins rebuilt: the state of a set created afresh on the same ranks from the global list at the new
+ * positions (fl_ibm_interp / fl_ibm_spread give that set's bits).  moved[0] / moved[1]: own markers that left / arrived on this rank;
+ * *L_local_new: the new Lo, which U, F and dV of the following calls are indexed by.  A rank without markers takes part with NULL arrays.
+ * Precondition: the own markers are in ascending number when the call is made -- lists made with fl_ibm_owned_select and gid = list index are, and a
+ * migrate leaves them so.  Errors, the same on every rank (voted; nobody waits for a rank that left) and the set stays exactly as it was:
+ *   FL_ERR_ARG_WRONGSTATE  the numbers of some rank's own markers do not ascend; a set created without numbers
+ *   FL_ERR_ARG_OUTOFRANGE  a marker's new owner is neither this rank nor one of its neighbouring blocks (ONE BLOCK PER CALL; possible only with three
+ *                          or more ranks along an axis); nattr outside 0..8
+ *   FL_ERR_ARG_NULL        pointers missing although Lo > 0
+ * A replicated set: FL_ERR_ARG_WRONGSTATE, not collective.  On one rank nothing moves and the call equals fl_ibm_update.
+ * Cost: the host sees 27 counts per rank, never a per-marker array, up to the unchanged routing step that fl_ibm_update runs too.  The arrivals of
+ * one call are ordered by counting, O(A^2) in their number A on a rank: A is meant to be the few per cent of a body that cross a rank face in one
+ * step, not a whole body. */
+int fl_ibm_migrate(fl_ibm *m, const double *X_dev, const double *Y_dev, const double *Z_dev, int nattr, const double *attr_dev, int64_t *L_local_new, int64_t moved[2]);
+/* The own markers after a migrate (or a create), in the set's order, into device arrays with room for cap >= Lo entries (else FL_ERR_ARG_SIZ):
+ * positions, numbers (gid_dev: sets with numbers only), the first nattr attributes of the last migrate (attr_out[a*Lo + l]; nattr beyond what that
+ * call carried: FL_ERR_ARG_OUTOFRANGE).  Any output may be NULL.  Stream-ordered; not collective. */
+int fl_ibm_owned_fetch(fl_ibm *m, int64_t cap, double *X_dev, double *Y_dev, double *Z_dev, int64_t *gid_dev, int nattr, double *attr_out_dev);
+/* A rigid body's markers from their reference positions (device, length L; stream-ordered, not collective): X_l = centre + R(rotvec) (X0_l - centre0)
+ * with R by Rodrigues' formula (rotvec = axis * angle, host arrays of 3), Ut[c*L + l] = velocity + omega x (X_l - centre).  X/Y/Z (all three or
+ * none) and Ut may be NULL.  The rotation matrix is formed on the host: every rank moves its markers with the same nine numbers. */
+int fl_ibm_rigid_pose(fl_poisson *grid_from, int64_t L, const double *X0_dev, const double *Y0_dev, const double *Z0_dev, const double centre0[3], const double centre[3], const double rotvec[3], const double velocity[3],
+                      const double omega[3], double *X_dev, double *Y_dev, double *Z_dev, double *Ut_dev);
 
 #ifdef __cplusplus
 }

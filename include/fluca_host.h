@@ -227,6 +227,15 @@ FlErrorCode NSSolve(NS ns);
  * NS owns, plus ghost copies of the neighbours' markers near its faces (fl_ibm_create_owned: a few bytes per copy, no all-reduce).  The option
  * is the user's choice for now: nothing measured on two or more GPUs could pick a default yet.  Another value: PETSC_ERR_ARG_UNKNOWN_TYPE. */
 FlErrorCode NSSetImmersedBoundary(NS ns, int kind, int64_t L, const double *X_dev, const double *Y_dev, const double *Z_dev, const double *dV_dev, const double *Utarget_dev);
+/* A body in prescribed rigid motion.  After NSSetImmersedBoundary: the markers given there are the body in the pose (centre0, no rotation).  At time t
+ * marker l sits at X_l(t) = centre(t) + R(rotvec(t)) (X0_l - centre0) (Rodrigues, rotvec = axis * angle) and is driven to
+ * U_l = velocity + omega x (X_l - centre); a Utarget_dev given before is no longer read.  NSStep from t to t + dt calls fn(t + dt, ...) before the
+ * forcing term, moves the markers (fl_ibm_update, or with -ns_ibm_marker_distribution owner fl_ibm_migrate: reference positions and volumes travel
+ * with a marker that changes rank, one block per step at most) and forces with them.  A non-zero return of fn ends the step with that code, on every
+ * rank (where the ranks' codes differ, a rank whose own call succeeded reports the mean of the others').  fn = NULL: the body is at rest again where
+ * it is.  Without an immersed boundary, or before NSSetUp: PETSC_ERR_ARG_WRONGSTATE.  NSSetImmersedBoundary called again clears the motion. */
+typedef FlErrorCode (*NSBodyMotionFn)(double t, double centre[3], double rotvec[3], double velocity[3], double omega[3], void *ctx);
+FlErrorCode NSSetImmersedBoundaryMotion(NS ns, const double centre0[3], NSBodyMotionFn fn, void *ctx);
 FlErrorCode NSGetSolutionArrays(NS ns, double **v_dev, double *V_dev[3], double **p_dev);
 FlErrorCode NSGetPressureHalfStep(NS ns, double **phalf_dev); /* cnl->phalf, the vector named "PressureHalfStep" (cnlinear.c:54) */
 FlErrorCode NSGetMesh(NS ns, Mesh *mesh);

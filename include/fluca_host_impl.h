@@ -89,6 +89,13 @@ struct _p_NS {
   double              *ibm_U;
   int                  ibm_owner;  /* -ns_ibm_marker_distribution: 0 replicated (default), 1 owner */
   void                *ibm_own[6]; /* owner: this rank's X, Y, Z, dV, Utarget and marker numbers (device, owned by the NS) */
+  const double        *ibm_X[3];   /* the positions NSSetImmersedBoundary was given (replicated: the caller's; owner: ibm_own[0..2]) */
+  FlErrorCode        (*ibm_motion)(double, double *, double *, double *, double *, void *); /* NSBodyMotionFn, NSSetImmersedBoundaryMotion */
+  void                *ibm_motion_ctx;
+  double               ibm_centre0[3];
+  double              *ibm_ref, *ibm_mv; /* moving body (device, owned by the NS): reference positions and volumes 4 x ibm_L; new positions 3 x ibm_L, then at
+                                          * 3 ibm_cap the target velocities 3 x ibm_L */
+  int64_t              ibm_cap, ibm_Ucap; /* markers ibm_ref / ibm_mv, ibm_U have room for */
   fl_ksp_opts          schur;    /* -ns_abf_schur_* */
   fl_ksp_opts          mom;      /* -ns_abf_momentum_* */
   int                  schur_ainv, upper_ainv; /* -ns_pc_abf_schur_ainv_type / -ns_pc_abf_upper_ainv_type (PCABFAinvType), default ID */

@@ -6,7 +6,8 @@
  *                    one GPU: rings of markers one h apart, N rings -- 102 912 markers at N = 512)
  *   -config sphere   the channel with an immersed sphere of diameter 64 h at the centre (markers on a Fibonacci lattice,
  *                    spacing ~ h: L = 12 868), direct-forcing IBM active every step
- * Prints wall time and solver work per step.  Options of the mirror apply (-ns_time_step_size, -ns_max_steps,
+ * Prints wall time and solver work per step and, with a body, the force and torque of the fluid on it and the drag coefficient
+ * (NSGetImmersedBoundaryForce; -ns_ibm_force_monitor <file> writes them to a file).  Options of the mirror apply (-ns_time_step_size, -ns_max_steps,
  * -ns_abf_schur_pc_type mg, -ns_ksp_type preonly, ...).
  *
  *   gcc -O2 examples/flow_configs.c -Iinclude -Lfluca_amd/lib -lfluca_host -lflucahip -lm -Wl,-rpath,$PWD/fluca_amd/lib
@@ -138,6 +139,8 @@ int main(int argc, char **argv)
     ABI(fl_memcpy_h2d(0, Xd, X, sizeof(double) * 4 * (size_t)L));
     const double *D = (const double *)Xd;
     CHK(NSSetImmersedBoundary(ns, FL_DELTA_PESKIN4, L, D, D + L, D + 2 * L, D + 3 * L, NULL));
+    const double centre[3] = {0.5, 0.5, 0.5}; /* a body at rest: the point the torque refers to */
+    CHK(NSSetImmersedBoundaryMotion(ns, centre, NULL, NULL));
     free(X);
   }
   printf("config %s  cells %lld x %lld x %lld  dt %g  Re %g  markers %lld\n", config, (long long)N, (long long)N, (long long)P3, 0.5 / (double)N, Re, (long long)L);
@@ -159,6 +162,19 @@ int main(int argc, char **argv)
     /* |r| / |f|: the quantity -ns_ksp_rtol bounds (with -ns_ksp_type preonly no residual is formed: one PCApply_ABF per step) */
     printf("step %lld  wall %.3f s  outer its %d  kspA its %d  kspS its %d  |r|/|f| %.2e  (|f| %.2e)\n", (long long)(s + 1), dtw, its, mi, si,
            rnorm0 > 0. ? rnorm / rnorm0 : 0., rnorm0);
+    if (sphere) {
+      /* Force of the fluid on the body during this step (NSGetImmersedBoundaryForce; outside the timed part).  NSMonitor writes the same numbers as one
+       * line per step into the file of -ns_ibm_force_monitor <file>, if that option was given.  C_d = F_x / (1/2 rho U^2 A) with the mean inflow
+       * speed U = 2/3 and the frontal area A = pi R^2 (sphere) or D x span (cylinder).  Its value against the literature is UNMEASURED: the body blocks
+       * 1/8 of the channel's height, the start is impulsive and the runs are a few steps long -- a number to watch, not one to quote or assert.
+       * (The line below avoids the word that starts the per-step line above: scripts count those.) */
+      double F[3], T[3], rho = 1.;
+      CHK(NSMonitor(ns));
+      CHK(NSGetImmersedBoundaryForce(ns, NULL, F, T));
+      CHK(NSGetDensity(ns, &rho));
+      const double hh = 1. / (double)N, RR = 32. * hh, U = 2. / 3., A = cylinder ? 2. * RR * 1. : 3.14159265358979323846 * RR * RR;
+      printf("     force on the body %+.6e %+.6e %+.6e  torque %+.6e %+.6e %+.6e  C_d %.4f\n", F[0], F[1], F[2], T[0], T[1], T[2], F[0] / (0.5 * rho * U * U * A));
+    }
     fflush(stdout);
   }
   ABI(fl_memcpy_d2h(0, v, v_dev, sizeof(double) * 3 * (size_t)sz[0]));

@@ -169,6 +169,7 @@ PROTOTYPES = {
     "fl_ibm_migrate": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "fl_ibm_owned_fetch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, C.c_int, _P]),
     "fl_ibm_rigid_pose": (C.c_int, [_P, C.c_int64, _P, _P, _P] + [C.POINTER(C.c_double)] * 5 + [_P, _P, _P, _P]),
+    "fl_ibm_force": (C.c_int, [_P, _P, _P, _P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 for _name, (_res, _args) in PROTOTYPES.items():
     _f = getattr(lib, _name)  # AttributeError if the library lacks a declared symbol

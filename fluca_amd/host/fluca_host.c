@@ -51,6 +51,10 @@ static void trace_begin(const char *name);
 static int    step_timing(void);
 static double step_clock(NS ns);
 static FlErrorCode ns_jacobian(NS ns);
+/* the bodies of the immersed boundary (NSSetImmersedBoundaryBodies) and the force monitor's context */
+static FlErrorCode ibm_force_monitor_destroy(void **ctx);
+static FlErrorCode ibm_body_to_ref(NS ns);
+static FlErrorCode ibm_body_from_ref(NS ns, int64_t Ln);
 
 /* ------------------------------------------------------------------------------------------------ registries */
 
@@ -869,6 +873,16 @@ FlErrorCode NSSetFromOptions(NS ns, int argc, char **argv)
     else if (!strcmp(s, "owner")) ns->ibm_owner = 1;
     else return E_ARG_UNKNOWN_TYPE;
   }
+  /* mirror only: force and torque on the immersed bodies, one line per step and body (NSMonitorImmersedBoundaryForce) */
+  if ((s = opt_find(argc, argv, "-ns_ibm_force_monitor"))) {
+    char *name = strdup(s);
+    if (!name) return E_MEM;
+    const FlErrorCode e = NSMonitorSet(ns, NSMonitorImmersedBoundaryForce, name, ibm_force_monitor_destroy);
+    if (e) {
+      free(name);
+      return e;
+    }
+  }
   /* sub-KSP of the Schur complement: prefix ns_ + abf_schur_ (nssol.c:19, abfpc.c:206) */
   if ((s = opt_find(argc, argv, "-ns_abf_schur_ksp_type"))) {
     if (!strcmp(s, "cg")) ns->schur.type = FL_KSP_CG;
@@ -1069,6 +1083,7 @@ static FlErrorCode NSStep_Body(NS ns) /* nsbasic.c:276-299 */
     ++ns->step;
     ns->t += ns->dt;
   }
+  ns->ibm_force_ready = ns->ibm != NULL && ns->reason >= 0; /* ibm_U holds this step's U_target - interp(v0): NSGetImmersedBoundaryForce */
   if (ns->reason < 0 && ns->errorifstepfailed) { /* :293-297 */
     NSMonitorCancel(ns);
     return 91; /* PETSC_ERR_NOT_CONVERGED: "NSStep has failed due to DIVERGED_NONLINEAR_SOLVE" */
@@ -1369,6 +1384,14 @@ static void ibm_free_own(NS ns)
   ns->ibm_motion     = NULL;
   ns->ibm_motion_ctx = NULL;
   ns->ibm_X[0] = ns->ibm_X[1] = ns->ibm_X[2] = NULL;
+  /* ... and the bodies; no force until the next step */
+  if (ns->ibm_body_own) fl_free(ns->device, ns->ibm_body_own);
+  ns->ibm_body_own = NULL;
+  ns->ibm_body     = NULL;
+  ns->ibm_nbody    = 0;
+  ns->ibm_body_cap = 0;
+  ns->ibm_force_ready = ns->ibm_have_centre = ns->ibm_have_centre0 = 0;
+  ns->ibm_mon_step    = -1;
 }
 
 /* -ns_ibm_marker_distribution owner: this rank's share of the replicated arrays, gathered into arrays the NS owns -- ibm_own[0..2] positions, [3] volumes,
@@ -1419,6 +1442,7 @@ FlErrorCode NSSetImmersedBoundary(NS ns, int kind, int64_t L, const double *X_de
   ns->ibm_U = NULL;
   ibm_free_own(ns);
   void *u = NULL;
+  ns->ibm_Lglobal = L;
   if (ns->ibm_owner) {
     /* the caller still hands over the replicated arrays; every rank keeps what the ownership rule gives it (the global index is the marker number,
      * so the forcing adds up in the replicated order) */
@@ -1446,7 +1470,7 @@ FlErrorCode NSSetImmersedBoundary(NS ns, int kind, int64_t L, const double *X_de
   return 0;
 }
 
-/* room for n markers in ibm_ref (4 n) and ibm_mv (6 n); the old contents are not kept */
+/* room for n markers in ibm_ref (5 n: the fifth row carries the body ids of NSSetImmersedBoundaryBodies) and ibm_mv (6 n); the old contents are not kept */
 static FlErrorCode ibm_motion_reserve(NS ns, int64_t n)
 {
   if (ns->ibm_ref && ns->ibm_mv && n <= ns->ibm_cap) return 0;
@@ -1456,7 +1480,7 @@ static FlErrorCode ibm_motion_reserve(NS ns, int64_t n)
   ns->ibm_cap = 0;
   const int64_t cap = n + n / 4 + 64;
   void         *a = NULL, *b = NULL;
-  FLABI(fl_malloc(ns->device, sizeof(double) * 4 * (size_t)cap, &a));
+  FLABI(fl_malloc(ns->device, sizeof(double) * 5 * (size_t)cap, &a));
   ns->ibm_ref = (double *)a;
   FLABI(fl_malloc(ns->device, sizeof(double) * 6 * (size_t)cap, &b));
   ns->ibm_mv  = (double *)b;
@@ -1472,6 +1496,10 @@ FlErrorCode NSSetImmersedBoundaryMotion(NS ns, const double centre0[3], NSBodyMo
     if (ns->ibm_motion) ns->ibm_Ut = NULL;
     ns->ibm_motion     = NULL;
     ns->ibm_motion_ctx = NULL;
+    if (centre0 && !ns->ibm_have_centre) { /* a body that never moved: the point NSGetImmersedBoundaryForce refers its torque to */
+      for (int d = 0; d < 3; ++d) ns->ibm_centre0[d] = centre0[d];
+      ns->ibm_have_centre0 = 1;
+    }
     return 0;
   }
   if (!centre0) return E_ARG_NULL;
@@ -1494,9 +1522,10 @@ FlErrorCode NSSetImmersedBoundaryMotion(NS ns, const double centre0[3], NSBodyMo
     }
   }
   for (int d = 0; d < 3; ++d) ns->ibm_centre0[d] = centre0[d];
+  ns->ibm_have_centre0 = 1;
   ns->ibm_motion     = fn;
   ns->ibm_motion_ctx = ctx;
-  return 0;
+  return ibm_body_to_ref(ns);
 }
 
 /* the moving body at t + dt: pose from the callback, markers moved (and, owner-rank markers, handed from rank to rank), target velocities */
@@ -1510,6 +1539,8 @@ static FlErrorCode ibm_move(NS ns)
     if (!rc && v[0] > 0.) rc = (FlErrorCode)(v[1] / v[0] + (v[1] >= 0. ? 0.5 : -0.5));
   }
   if (rc) return rc;
+  for (int d = 0; d < 3; ++d) ns->ibm_centre[d] = centre[d];
+  ns->ibm_have_centre = 1;
   fl_poisson *h = ns->poisson;
   int64_t     L = ns->ibm_L;
   double     *ref = ns->ibm_ref, *pos = ns->ibm_mv;
@@ -1522,12 +1553,14 @@ static FlErrorCode ibm_move(NS ns)
   }
   int64_t Ln = 0, moved[2] = {0, 0};
   FLABI(fl_ibm_rigid_pose(h, L, ref, ref + L, ref + 2 * L, ns->ibm_centre0, centre, rotvec, vel, omega, pos, pos + L, pos + 2 * L, NULL));
-  FLABI(fl_ibm_migrate(ns->ibm, L ? pos : NULL, L ? pos + L : NULL, L ? pos + 2 * L : NULL, 4, L ? ref : NULL, &Ln, moved));
+  const int nattr = ns->ibm_body_own ? 5 : 4; /* reference position, volume and, with several bodies, the body id */
+  FLABI(fl_ibm_migrate(ns->ibm, L ? pos : NULL, L ? pos + L : NULL, L ? pos + 2 * L : NULL, nattr, L ? ref : NULL, &Ln, moved));
   /* the set holds positions, numbers and the four attributes now: the NS's arrays follow the new count */
   FLCHK(ibm_motion_reserve(ns, Ln));
   ref = ns->ibm_ref;
   pos = ns->ibm_mv;
-  FLABI(fl_ibm_owned_fetch(ns->ibm, ns->ibm_cap, NULL, NULL, NULL, NULL, 4, ref));
+  FLABI(fl_ibm_owned_fetch(ns->ibm, ns->ibm_cap, NULL, NULL, NULL, NULL, nattr, ref));
+  if (nattr == 5 && (moved[0] > 0 || moved[1] > 0)) FLCHK(ibm_body_from_ref(ns, Ln)); /* the list of this rank has changed: its ids follow */
   if (Ln > ns->ibm_Ucap) {
     void *u = NULL;
     FLABI(fl_poisson_synchronize(h));
@@ -1550,6 +1583,148 @@ FlErrorCode NSGetImmersedBoundary(NS ns, fl_ibm **ibm)
   if (!ns || !ibm) return E_ARG_NULL;
   if (!ns->ibm) return E_ARG_WRONGSTATE;
   *ibm = ns->ibm;
+  return 0;
+}
+
+
+/* ---- force and torque on the bodies -------------------------------------------------------------------------------------------------- */
+
+/* owner distribution under a prescribed motion: the ids as the fifth row of ibm_ref (doubles), so that they travel through fl_ibm_migrate */
+static FlErrorCode ibm_body_to_ref(NS ns)
+{
+  const int64_t L = ns->ibm_L;
+  if (!ns->ibm_owner || !ns->ibm_ref || !ns->ibm_body_own || L == 0) return 0;
+  int32_t *ids = (int32_t *)malloc(sizeof(int32_t) * (size_t)L);
+  double  *val = (double *)malloc(sizeof(double) * (size_t)L);
+  int      rc  = (!ids || !val) ? -E_MEM : 0;
+  if (!rc) rc = fl_poisson_synchronize(ns->poisson);
+  if (!rc) rc = fl_memcpy_d2h(ns->device, ids, ns->ibm_body_own, sizeof(int32_t) * (size_t)L);
+  for (int64_t l = 0; l < L && !rc; ++l) val[l] = (double)ids[l];
+  if (!rc) rc = fl_memcpy_h2d(ns->device, ns->ibm_ref + 4 * L, val, sizeof(double) * (size_t)L);
+  free(ids);
+  free(val);
+  return rc ? -rc : 0;
+}
+/* ... and back after a migration: ibm_body_own from the fifth row of ibm_ref (Ln markers) */
+static FlErrorCode ibm_body_from_ref(NS ns, int64_t Ln)
+{
+  if (Ln > ns->ibm_body_cap) {
+    void *b = NULL;
+    FLABI(fl_poisson_synchronize(ns->poisson));
+    if (ns->ibm_body_own) fl_free(ns->device, ns->ibm_body_own);
+    ns->ibm_body_own = NULL;
+    ns->ibm_body     = NULL;
+    ns->ibm_body_cap = 0;
+    FLABI(fl_malloc(ns->device, sizeof(int32_t) * (size_t)(ns->ibm_cap + 1), &b));
+    ns->ibm_body_own = b;
+    ns->ibm_body_cap = ns->ibm_cap;
+  }
+  ns->ibm_body = (const int32_t *)ns->ibm_body_own;
+  if (Ln == 0) return 0;
+  int32_t *ids = (int32_t *)malloc(sizeof(int32_t) * (size_t)Ln);
+  double  *val = (double *)malloc(sizeof(double) * (size_t)Ln);
+  int      rc  = (!ids || !val) ? -E_MEM : 0;
+  if (!rc) rc = fl_poisson_synchronize(ns->poisson);
+  if (!rc) rc = fl_memcpy_d2h(ns->device, val, ns->ibm_ref + 4 * Ln, sizeof(double) * (size_t)Ln);
+  for (int64_t l = 0; l < Ln && !rc; ++l) ids[l] = (int32_t)val[l];
+  if (!rc) rc = fl_memcpy_h2d(ns->device, ns->ibm_body_own, ids, sizeof(int32_t) * (size_t)Ln);
+  free(ids);
+  free(val);
+  return rc ? -rc : 0;
+}
+
+FlErrorCode NSSetImmersedBoundaryBodies(NS ns, int nbody, const int32_t *body_dev)
+{
+  if (!ns) return E_ARG_NULL;
+  if (nbody < 1 || nbody > 64) return E_ARG_OUTOFRANGE;
+  if (!ns->setupcalled || !ns->ibm) return E_ARG_WRONGSTATE;
+  if (!body_dev) return E_ARG_NULL;
+  if (!ns->ibm_owner) {
+    ns->ibm_nbody = nbody;
+    ns->ibm_body  = body_dev;
+    return 0;
+  }
+  /* this rank's share: the set knows the numbers (= indices into the list) of the markers it owns now, before or after any migration */
+  const int64_t n = ns->ibm_L, L = ns->ibm_Lglobal;
+  void         *gid_dev = NULL, *own = NULL;
+  int64_t      *gid = (int64_t *)malloc(sizeof(int64_t) * (size_t)(n + 1));
+  int32_t      *all = (int32_t *)malloc(sizeof(int32_t) * (size_t)L), *mine = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n + 1));
+  int           rc  = (!gid || !all || !mine) ? -E_MEM : 0;
+  const int64_t cap = ns->ibm_cap > n ? ns->ibm_cap : n;
+  if (!rc) rc = fl_malloc(ns->device, sizeof(int64_t) * (size_t)(n + 1), &gid_dev);
+  if (!rc) rc = fl_ibm_owned_fetch(ns->ibm, n, NULL, NULL, NULL, (int64_t *)gid_dev, 0, NULL);
+  if (!rc) rc = fl_poisson_synchronize(ns->poisson);
+  if (!rc && n > 0) rc = fl_memcpy_d2h(ns->device, gid, gid_dev, sizeof(int64_t) * (size_t)n);
+  if (!rc) rc = fl_memcpy_d2h(ns->device, all, body_dev, sizeof(int32_t) * (size_t)L);
+  for (int64_t a = 0; a < n && !rc; ++a) {
+    if (gid[a] < 0 || gid[a] >= L) rc = -E_ARG_OUTOFRANGE;
+    else mine[a] = all[gid[a]];
+  }
+  if (!rc) rc = fl_malloc(ns->device, sizeof(int32_t) * (size_t)(cap + 1), &own);
+  if (!rc && n > 0) rc = fl_memcpy_h2d(ns->device, own, mine, sizeof(int32_t) * (size_t)n);
+  free(gid);
+  free(all);
+  free(mine);
+  if (gid_dev) fl_free(ns->device, gid_dev);
+  if (rc) {
+    if (own) fl_free(ns->device, own);
+    return -rc;
+  }
+  if (ns->ibm_body_own) fl_free(ns->device, ns->ibm_body_own);
+  ns->ibm_body_own = own;
+  ns->ibm_body_cap = cap;
+  ns->ibm_body     = (const int32_t *)own;
+  ns->ibm_nbody    = nbody;
+  return ibm_body_to_ref(ns);
+}
+
+/* about == NULL: the point every body's torque refers to */
+static void ibm_default_about(NS ns, double p[3])
+{
+  for (int d = 0; d < 3; ++d) p[d] = ns->ibm_have_centre ? ns->ibm_centre[d] : (ns->ibm_have_centre0 ? ns->ibm_centre0[d] : 0.);
+}
+
+FlErrorCode NSGetImmersedBoundaryForce(NS ns, const double *about, double *force, double *torque)
+{
+  if (!ns || !force) return E_ARG_NULL;
+  if (!ns->ibm || !ns->ibm_force_ready) return E_ARG_WRONGSTATE;
+  const int     nbody = ns->ibm_nbody ? ns->ibm_nbody : 1;
+  const int64_t L     = ns->ibm_L;
+  double        ab[3 * 64], f[3 * 64], t[3 * 64];
+  for (int b = 0; b < nbody; ++b) {
+    if (about) memcpy(ab + 3 * b, about + 3 * b, sizeof(double) * 3);
+    else ibm_default_about(ns, ab + 3 * b);
+  }
+  FLABI(fl_ibm_force(ns->ibm, L > 0 ? ns->ibm_U : NULL, L > 0 ? ns->ibm_dV : NULL, ns->ibm_nbody ? ns->ibm_body : NULL, nbody, ab, f, torque ? t : NULL));
+  const double s = -(ns->rho / ns->dt); /* the fluid's reaction to the forcing density (U_target - U) rho / dt */
+  for (int a = 0; a < 3 * nbody; ++a) {
+    force[a] = s * f[a];
+    if (torque) torque[a] = s * t[a];
+  }
+  return 0;
+}
+
+FlErrorCode NSMonitorImmersedBoundaryForce(NS ns, void *ctx)
+{
+  if (!ns || !ctx) return E_ARG_NULL;
+  if (!ns->ibm || !ns->ibm_force_ready || ns->ibm_mon_step == ns->step) return 0;
+  const int nbody = ns->ibm_nbody ? ns->ibm_nbody : 1;
+  double    f[3 * 64], t[3 * 64];
+  FLCHK(NSGetImmersedBoundaryForce(ns, NULL, f, t));
+  ns->ibm_mon_step = ns->step;
+  if (ns->mesh && ns->mesh->rank != 0) return 0;
+  FILE *fp = fopen((const char *)ctx, "a");
+  if (!fp) return E_FILE_OPEN;
+  int bad = 0;
+  for (int b = 0; b < nbody; ++b)
+    bad |= fprintf(fp, "%lld %.17g %d %.17g %.17g %.17g %.17g %.17g %.17g\n", (long long)ns->step, ns->t, b, f[3 * b], f[3 * b + 1], f[3 * b + 2], t[3 * b], t[3 * b + 1], t[3 * b + 2]) < 0;
+  bad |= fclose(fp) != 0;
+  return bad ? E_FILE_WRITE : 0;
+}
+static FlErrorCode ibm_force_monitor_destroy(void **ctx)
+{
+  free(*ctx);
+  *ctx = NULL;
   return 0;
 }
 

@@ -497,6 +497,28 @@ int fl_ibm_owned_fetch(fl_ibm *m, int64_t cap, double *X_dev, double *Y_dev, dou
 int fl_ibm_rigid_pose(fl_poisson *grid_from, int64_t L, const double *X0_dev, const double *Y0_dev, const double *Z0_dev, const double centre0[3], const double centre[3], const double rotvec[3], const double velocity[3],
                       const double omega[3], double *X_dev, double *Y_dev, double *Z_dev, double *Ut_dev);
 
+/* FORCE AND TORQUE ON EACH BODY, as a sum whose bits do not depend on the order of the markers, on how they are shared out between ranks or on what
+ * has migrated.  F_dev[c*L + l] (three components, the layout of fl_ibm_spread's F), dV_dev[l], body_dev[l] in 0..nbody-1
+ * (device; NULL: one body, nothing is indexed), L = the set's marker count (Lo on an owned set: ghost copies never contribute), positions = the
+ * set's own as of the last create / update / migrate.  about, force, torque: HOST arrays of 3 nbody doubles, 1 <= nbody <= 64; torque may be NULL.
+ *   force[3b+c]  = sum_l F_c,l dV_l                     torque[3b+.] = sum_l (r_l x F_l) dV_l,  r_l = X_l - about_b
+ * over the markers of body b; on a periodic axis r is the minimum image, r -= P rint(r / P), P = xf[n] - xf[0].  Every product, difference and
+ * quotient of a term is rounded once (no fused multiply-add): the torque term is ((r_y F_z) - (r_z F_y)) dV, cyclically.
+ * The sum: per group (the 3 nbody force sums; the 3 nbody torque sums) E with max |t| < 2^E over all markers of all ranks; every term t is split
+ * exactly into hi = rint(t / u1) u1, u1 = 2^(E-30), and mid = rint((t - hi) / u2) u2, u2 = 2^(E-60); the tail (<= 2^(E-61) per term) is dropped; the
+ * hi and the mid parts add up exactly in a double in any order, and the result is sum hi + sum mid, rounded once:
+ *   |result - exact sum of the terms| <= L 2^(E-61) + 1/2 ulp(result).
+ * Where u2 would be subnormal (E < -900) the group is scaled by 2^200 and the result scaled back (one more rounding if IT is subnormal).
+ * A non-finite term: the outputs of its group are NaN for every body, the call returns FL_SUCCESS.  No markers, or all terms zero: zeros.
+ * Owned set on several ranks: COLLECTIVE, every rank receives the same bits; a rank without markers takes part with NULL arrays; the two maxima
+ * travel through two all-reduces, the 12 nbody exact partial sums eight at a time through the handle's sum all-reduce (at most 8 ranks).
+ * Replicated set: not collective, every rank sums its whole list.  One rank: two kernels and one host wait.
+ * Errors (voted on an owned set, like its other errors), force / torque untouched:
+ *   FL_ERR_ARG_NULL        m, force or about missing; F or dV missing although L > 0
+ *   FL_ERR_ARG_OUTOFRANGE  nbody outside 1..64; a body id outside 0..nbody-1 (found by the first kernel)
+ *   FL_ERR_SUP             2^22 markers or more over all ranks (the exact sums are guaranteed below that) */
+int fl_ibm_force(fl_ibm *m, const double *F_dev, const double *dV_dev, const int32_t *body_dev, int nbody, const double *about, double *force, double *torque);
+
 #ifdef __cplusplus
 }
 #endif

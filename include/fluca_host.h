@@ -233,9 +233,29 @@ FlErrorCode NSSetImmersedBoundary(NS ns, int kind, int64_t L, const double *X_de
  * forcing term, moves the markers (fl_ibm_update, or with -ns_ibm_marker_distribution owner fl_ibm_migrate: reference positions and volumes travel
  * with a marker that changes rank, one block per step at most) and forces with them.  A non-zero return of fn ends the step with that code, on every
  * rank (where the ranks' codes differ, a rank whose own call succeeded reports the mean of the others').  fn = NULL: the body is at rest again where
- * it is.  Without an immersed boundary, or before NSSetUp: PETSC_ERR_ARG_WRONGSTATE.  NSSetImmersedBoundary called again clears the motion. */
+ * it is (for a body that has never moved, a centre0 given with it is kept as the default point of NSGetImmersedBoundaryForce's torque).  Without an immersed boundary, or before NSSetUp: PETSC_ERR_ARG_WRONGSTATE.  NSSetImmersedBoundary called again clears the motion. */
 typedef FlErrorCode (*NSBodyMotionFn)(double t, double centre[3], double rotvec[3], double velocity[3], double omega[3], void *ctx);
 FlErrorCode NSSetImmersedBoundaryMotion(NS ns, const double centre0[3], NSBodyMotionFn fn, void *ctx);
+/* FORCE AND TORQUE THE FLUID EXERTS ON EACH BODY during the last completed step: -(rho / dt) times fl_ibm_force's sums (include/fluca_hip.h: a sum
+ * whose bits do not depend on the rank grid, the marker distribution or what has migrated; |error| <= L 2^(E-61) + 1/2 ulp, fewer than 2^22 markers)
+ * over F = U_target - interp(v0), the array NSStep forms for the forcing term anyway.  Lazy: a step costs nothing more when this is never called.  The
+ * factor is formed once, s = -(rho / dt), and every sum is multiplied by it.  force, torque: host arrays of 3 nbody doubles (nbody = 1 until
+ * NSSetImmersedBoundaryBodies says otherwise; torque may be NULL); about: 3 nbody doubles, the points the torques refer to, or NULL = for every body the
+ * centre of the prescribed motion at the end of that step (NSSetImmersedBoundaryMotion), without a motion the centre0 given there, else the origin.
+ * COLLECTIVE.  PETSC_ERR_ARG_WRONGSTATE without an immersed boundary, before the first step, or after NSSetImmersedBoundary was called again.
+ * NOT INCLUDED: for an accelerating body the inertia of the fluid inside it, rho V_b dU_c/dt (and its moment), which direct forcing puts into these sums;
+ * the caller adds it. */
+FlErrorCode NSGetImmersedBoundaryForce(NS ns, const double *about, double *force, double *torque);
+/* Several bodies in one marker list: body_dev[l] in 0..nbody-1 (device, int32, one id per entry of the list NSSetImmersedBoundary was given; every rank
+ * hands over the whole list), 1 <= nbody <= 64.  Replicated distribution: the array is used as given and must stay alive.  -ns_ibm_marker_distribution
+ * owner: this rank's share is copied into an array the NS owns, and under a prescribed motion it travels with the markers from rank to rank (a fifth
+ * attribute of fl_ibm_migrate; a small integer is exact in a double).  All bodies share the one prescribed motion.  An id out of range shows as
+ * PETSC_ERR_ARG_OUTOFRANGE of NSGetImmersedBoundaryForce.  Before NSSetUp / NSSetImmersedBoundary: PETSC_ERR_ARG_WRONGSTATE; that call resets to one body. */
+FlErrorCode NSSetImmersedBoundaryBodies(NS ns, int nbody, const int32_t *body_dev);
+/* An NSMonitorSet callback (also: -ns_ibm_force_monitor <file>): ctx = the name of a text file (a NUL-terminated string that outlives the monitor).  Once
+ * per completed step and body, rank 0 appends the line  step t body F_x F_y F_z T_x T_y T_z  (%.17g; torques about the default points of
+ * NSGetImmersedBoundaryForce).  Collective; does nothing before the first step or when the last step has been written already. */
+FlErrorCode NSMonitorImmersedBoundaryForce(NS ns, void *ctx);
 FlErrorCode NSGetSolutionArrays(NS ns, double **v_dev, double *V_dev[3], double **p_dev);
 FlErrorCode NSGetPressureHalfStep(NS ns, double **phalf_dev); /* cnl->phalf, the vector named "PressureHalfStep" (cnlinear.c:54) */
 FlErrorCode NSGetMesh(NS ns, Mesh *mesh);

@@ -113,6 +113,16 @@ struct _p_NS {
   void *monctx[MAXNSMONITORS];
   FlErrorCode (*mondestroy[MAXNSMONITORS])(void **);
   void                *data;
+  /* NSGetImmersedBoundaryForce / NSSetImmersedBoundaryBodies (at the end: the members above keep their places) */
+  int                  ibm_force_ready;  /* a step has been completed since NSSetImmersedBoundary: ibm_U holds its U_target - interp(v0) */
+  int                  ibm_have_centre, ibm_have_centre0; /* ibm_centre: the motion's centre at the end of the last step; ibm_centre0 has been given */
+  double               ibm_centre[3];
+  int64_t              ibm_Lglobal;      /* markers of the list NSSetImmersedBoundary was given */
+  int                  ibm_nbody;        /* 0: NSSetImmersedBoundaryBodies has not been called (one body) */
+  const int32_t       *ibm_body;         /* device, one id per marker this rank holds (replicated: the caller's array; owner: ibm_body_own) */
+  void                *ibm_body_own;     /* owner: this rank's share of the ids (device, owned by the NS), room for ibm_body_cap of them */
+  int64_t              ibm_body_cap;
+  int64_t              ibm_mon_step;     /* the step NSMonitorImmersedBoundaryForce wrote last */
 };
 
 /* NSCNLINEAR's data (nslinearcnimpl.h: v0interp, phalf, B) plus, in this mirror, the solution and solver vectors the

@@ -1724,6 +1724,8 @@ int fl_solve_cheb(fl_poisson *h, const double *b, double *x, const fl_ksp_opts *
   // answer: buffer `cur`, minus the accumulated constant (null-space removal done lazily)
   launch_unpad_copy(s, g, R.cur ? X1 : X0, x, R.nullspace ? &h->scal->xshift : nullptr);
   FL_CHK(finish_stats(h, o, st));
+  // maxit = 0 without a norm: no step ran, so no scalar kernel set the reason a KSP_NORM_NONE solve ends with
+  if (o->norm_type == FL_NORM_NONE && total <= 0 && st->reason == FL_DIVERGED_ITS) st->reason = FL_CONVERGED_ITS;
   st->kernel_ms       = 0.;
   st->kernel_launches = 0;
   if (o->profile) prof.mean(nprof, &st->kernel_ms, &st->kernel_launches);  // fused: per launch = per TWO steps

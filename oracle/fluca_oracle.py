@@ -618,6 +618,7 @@ class StepOracle:
         n = g.n
         self.cshape = (n[2], n[1], n[0])
         self.fshape = [(n[2], n[1], g.nf[0]), (n[2], g.nf[1], n[0]), (g.nf[2], n[1], n[0])]
+        self._lines = {}
 
     # -- boundary data -------------------------------------------------------------------------------------------
     def _wall(self, b, t):
@@ -651,15 +652,56 @@ class StepOracle:
     def _walls(self):
         return [b for b in range(6) if self.g.bc[b] == BC_VELOCITY]
 
-    def step_once(self, v0, V0, p0):
+    def _line_matrix(self, which, d):
+        """The 1-D matrix along axis d of kappa G ("G": cells -> cells) or of T ("T": cells -> d-faces): both act along their own axis only, so
+        column i is the operator applied to the field that is 1 in layer i of that axis; read along the line through the origin of the others."""
+        key = (which, d)
+        if key not in self._lines:
+            g, n = self.g, self.g.n[d]
+            M = np.empty((g.nf[d] if which == "T" else n, n))
+            for i in range(n):
+                e = np.zeros(self.cshape)
+                self._layer(e, d, i)[...] = 1.0
+                if which == "G":
+                    out = g.apply_G(e.ravel())[d].reshape(self.cshape)
+                else:
+                    v = np.zeros(3 * g.ncell)
+                    v[d * g.ncell:(d + 1) * g.ncell] = e.ravel()
+                    out = g.apply_T(v)[d].reshape(self.fshape[d])
+                sl = [0, 0, 0]
+                sl[2 - d] = slice(None)
+                M[:, i] = out[tuple(sl)]
+            self._lines[key] = M
+        return self._lines[key]
+
+    def _along(self, M, a, d):
+        """M (1-D matrix) applied along grid axis d of an array shaped (k, j, i)"""
+        return np.moveaxis(np.tensordot(M, a, axes=([1], [2 - d])), 0, 2 - d)
+
+    def form_function(self, v0, V0, p0, scale=True):
+        """The right-hand side of the step that starts at self.t as step number self.step (NSFormFunction, cnlinearcart3d.c:2945-3060) and v0interp
+        (:2826-2829): -> momrhs, interprhs[3], W[9] = B v0 with the wall values inserted, scale.  The pressure is p0 on step 0 and self.phalf afterwards.
+
+        scale = dict(v=(3 ncell), V=[3 face arrays]): for every entry the sum of the absolute values of the terms added into it,
+        |v0| + cv |L| |v0| + |kappa G| |p| + |wall L term| + |wall C term| + |outlet term| (+ the IBM forcing as it stands) on cells and
+        |wall value| + |kappa cgst| (|pq| + |pp|) + |T| (kappa |cg| (|pq| + |pp|)) on faces -- what a rounding-level comparison of momrhs and
+        interprhs is measured against, so that cancellation between the terms does not make it unfair.  scale=False: None (nothing extra computed)."""
         g, dt = self.g, self.dt
         cv = 0.5 * self.mu * dt / self.rho
         t = self.t
         N = g.ncell
         xc = [0.5 * (g.xf[d][1:] + g.xf[d][:-1]) if g.xc[d] is None else g.xc[d] for d in range(3)]
         W = g.apply_B(v0)
-        momrhs = v0 + cv * self.L.mult(v0) - np.concatenate(g.apply_G(p0 if self.step == 0 else self.phalf))
+        pin = p0 if self.step == 0 else self.phalf
+        momrhs = v0 + cv * self.L.mult(v0) - np.concatenate(g.apply_G(pin))
         interprhs = [np.zeros(g.nface[d]) for d in range(3)]
+        sv = sV = None
+        if scale:
+            rp, col, val = self.L.arrays()
+            absL = np.add.reduceat(np.abs(val) * np.abs(v0)[col], rp[:-1])       # every row of L has its diagonal: no empty row
+            absG = [self._along(np.abs(self._line_matrix("G", d)), np.abs(pin).reshape(self.cshape), d).ravel() for d in range(3)]
+            sv = np.abs(v0) + cv * absL + np.concatenate(absG)
+            sV = [np.zeros(g.nface[d]) for d in range(3)]
         for b in self._walls():
             ax, side = b // 2, b % 2
             n, xf, c = g.n[ax], g.xf[ax], xc[ax]
@@ -675,11 +717,17 @@ class StepOracle:
                 cells = momrhs[q * N:(q + 1) * N].reshape(self.cshape)
                 self._layer(cells, ax, -1 if side else 0)[...] += (cv * cl * (vb0[q] + vb1[q])                     # L: :701, twice (:2985, :2998)
                                                                    - dt * sgn * (vb1[q] * vb0[ax] + vb0[q] * vb1[ax]) / hc)   # C: :1338, :2991
+                if scale:
+                    self._layer(sv[q * N:(q + 1) * N].reshape(self.cshape), ax, -1 if side else 0)[...] += (
+                        cv * cl * (np.abs(vb0[q]) + np.abs(vb1[q])) + dt * 0.5 * (np.abs(vb1[q] * vb0[ax]) + np.abs(vb0[q] * vb1[ax])) / hc)
             self._layer(interprhs[ax].reshape(self.fshape[ax]), ax, -1 if side else 0)[...] = vb1[ax]               # :2178, :3003-3005
+            if scale:
+                self._layer(sV[ax].reshape(self.fshape[ax]), ax, -1 if side else 0)[...] = np.abs(vb1[ax])
         # PRESSURE_OUTLET: boundary-condition vector of G in momrhs (:2976-2984 with :257-259, :285-287 -- NOT scaled by
         # dt/rho, as written) and the Rhie-Chow boundary terms of interprhs (:3013-3044)
         tq, tp = (t if self.step == 0 else t - 0.5 * dt), t + 0.5 * dt
         wG = np.zeros(3 * N)
+        swG = np.zeros(3 * N) if scale else None
         for b in [b for b in range(6) if g.bc[b] == BC_PRESSURE_OUTLET]:
             ax, side = b // 2, b % 2
             n, xf, c = g.n[ax], g.xf[ax], xc[ax]
@@ -691,14 +739,31 @@ class StepOracle:
             wc = wG[ax * N:(ax + 1) * N].reshape(self.cshape)
             self._layer(wc, ax, -1 if side else 0)[...] += g.kappa * cg * (pq - pp)
             self._layer(interprhs[ax].reshape(self.fshape[ax]), ax, -1 if side else 0)[...] += g.kappa * g.gst_bc_coeff(ax, side) * (pq - pp)
+            if scale:
+                both = np.abs(pq) + np.abs(pp)
+                self._layer(sv[ax * N:(ax + 1) * N].reshape(self.cshape), ax, -1 if side else 0)[...] += abs(cg) * np.abs(pq)
+                self._layer(swG[ax * N:(ax + 1) * N].reshape(self.cshape), ax, -1 if side else 0)[...] += g.kappa * abs(cg) * both
+                self._layer(sV[ax].reshape(self.fshape[ax]), ax, -1 if side else 0)[...] += g.kappa * abs(g.gst_bc_coeff(ax, side)) * both
         if np.any(wG != 0.0):
             Tw = g.apply_T(wG)
             interprhs = [interprhs[d] - Tw[d] for d in range(3)]
+            if scale:
+                for d in range(3):
+                    sV[d] += self._along(np.abs(self._line_matrix("T", d)), swG[d * N:(d + 1) * N].reshape(self.cshape), d).ravel()
         if self.ibm is not None:
             ib = self.ibm
             U = g.ibm_interp(ib["kind"], ib["X"], v0.reshape(3, N))
             F = (0.0 if ib.get("Ut") is None else np.asarray(ib["Ut"]).reshape(3, -1)) - U
-            momrhs = momrhs + g.ibm_spread(ib["kind"], ib["X"], ib["dV"], F).ravel()
+            spread = g.ibm_spread(ib["kind"], ib["X"], ib["dV"], F).ravel()
+            momrhs = momrhs + spread
+            if scale:
+                sv = sv + np.abs(spread)
+        return momrhs, interprhs, W, (dict(v=sv, V=sV) if scale else None)
+
+    def step_once(self, v0, V0, p0):
+        g, dt = self.g, self.dt
+        cv = 0.5 * self.mu * dt / self.rho
+        momrhs, interprhs, W, _ = self.form_function(v0, V0, p0, scale=False)
         A = g.assemble_momentum(1.0, dt, -cv, V0, W)
 
         def pcapply(fv, fV, fp):      # abfpc.c:71-101

@@ -508,23 +508,11 @@ def _mirror_run(R, n, ranks, nsteps, ibm):
 
 
 def _gather(parts, n):
-    """blocks of the ranks -> global v (3, nz, ny, nx), V[d] on the global face arrays, p"""
-    nfx = [n[0] + 1, n[1] + 1, n[2]]           # x outlet / y wall: one face more than cells; z periodic: as many
-    v = np.full((3, n[2], n[1], n[0]), np.nan)
-    p = np.full((n[2], n[1], n[0]), np.nan)
-    V = [np.full((n[2], n[1], nfx[0]), np.nan), np.full((n[2], nfx[1], n[0]), np.nan), np.full((nfx[2], n[1], n[0]), np.nan)]
-    for r in parts:
-        lo, ln = r["lo"], r["ln"]
-        sl = (slice(lo[2], lo[2] + ln[2]), slice(lo[1], lo[1] + ln[1]), slice(lo[0], lo[0] + ln[0]))
-        v[(slice(None),) + sl] = r["v"].reshape(3, ln[2], ln[1], ln[0])
-        p[sl] = r["p"].reshape(ln[2], ln[1], ln[0])
-        for d in range(3):
-            f = list(ln)
-            f[d] = r["V"][d].size // (ln[(d + 1) % 3] * ln[(d + 2) % 3])
-            fs = [slice(lo[a], lo[a] + f[a]) for a in (2, 1, 0)]
-            V[d][tuple(fs)] = r["V"][d].reshape(f[2], f[1], f[0])
-    assert not (np.isnan(v).any() or np.isnan(p).any() or any(np.isnan(a).any() for a in V)), "the blocks do not tile the grid"
-    return v, V, p
+    """blocks of the ranks -> global v (3 ncell), V[d] on the global face arrays, p (tests/step_rhs.py: the face counts come from the boundary types)"""
+    from oracle import fluca_oracle as fo
+    from tests.step_rhs import gather
+    Lx, Ly, Lz = CH_BOX
+    return gather(parts, fo.Grid.uniform(n, [(0, Lx), (0, Ly), (0, Lz)], C5_BC, 1.0))
 
 
 def test_nsstep_on_the_2x2x2_rank_grid_matches_the_oracle_step():

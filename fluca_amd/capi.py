@@ -24,6 +24,8 @@ KSP_CG, KSP_BCGS, KSP_CHEBYSHEV, KSP_GMRES = range(4)
 PC_NONE, PC_JACOBI = range(2)
 NORM_PRECONDITIONED, NORM_UNPRECONDITIONED, NORM_NATURAL, NORM_NONE = range(4)
 DELTA_PESKIN4, DELTA_ROMA3 = range(2)
+SCALAR_DIRICHLET, SCALAR_NEUMANN, SCALAR_PERIODIC = range(3)
+LIMITERS = ("superbee", "minmod", "mc", "vanleer", "vanalbada", "barthjesperson", "venkatakrishnan", "koren", "upwind", "sou", "quick")
 UNIQUE_ID_BYTES = 128
 
 ERRORS = {0: "FL_SUCCESS", -55: "FL_ERR_MEM", -56: "FL_ERR_SUP", -60: "FL_ERR_ARG_SIZ", -62: "FL_ERR_ARG_WRONG",
@@ -170,6 +172,18 @@ PROTOTYPES = {
     "fl_ibm_owned_fetch": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, C.c_int, _P]),
     "fl_ibm_rigid_pose": (C.c_int, [_P, C.c_int64, _P, _P, _P] + [C.POINTER(C.c_double)] * 5 + [_P, _P, _P, _P]),
     "fl_ibm_force": (C.c_int, [_P, _P, _P, _P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "fl_limiter_from_name": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
+    "fl_limiter_eval": (C.c_int, [C.c_int, C.c_double, C.POINTER(C.c_double)]),
+    "fl_scalar_create": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(_P)]),
+    "fl_scalar_destroy": (C.c_int, [_P]),
+    "fl_scalar_set_boundary_value": (C.c_int, [_P, C.c_int, C.c_double]),
+    "fl_scalar_set_limiter": (C.c_int, [_P, C.c_int]),
+    "fl_scalar_set_diffusivity": (C.c_int, [_P, C.c_double]),
+    "fl_scalar_set_velocity": (C.c_int, [_P, _P, _P, _P]),
+    "fl_scalar_rhs": (C.c_int, [_P, _P, _P, _P]),
+    "fl_scalar_step": (C.c_int, [_P, C.c_double, C.c_int, _P, _P]),
+    "fl_scalar_cfl": (C.c_int, [_P, C.c_double, C.POINTER(C.c_double)]),
+    "fl_scalar_stats": (C.c_int, [_P, _P, C.POINTER(C.c_double)]),
 }
 for _name, (_res, _args) in PROTOTYPES.items():
     _f = getattr(lib, _name)  # AttributeError if the library lacks a declared symbol

@@ -407,4 +407,34 @@ int build_axis_faceinterp(const Axis &a, int kind, std::vector<double> &w0, std:
   return 0;
 }
 
+// The rows of the scalar transport operator (fl_scalar.hip) for the cells 0 .. n-1 of a grid line: the second-order TVD face value of
+// FlucaFDSecondOrderTVD (fluca/src/fd/impls/secondordertvd/secondordertvd.c:187-356) needs, at face f between the cells f-1 and f,
+// alpha+ = (xf_f - xc_{f-1}) / (xc_f - xc_{f-1}) for V > 0 and alpha- = (xc_f - xf_f) / (xc_f - xc_{f-1}) otherwise, and the two-point
+// gradients of the faces f-1, f, f+1.  Whether an end is Dirichlet or Neumann does not enter: both read the distance centre -- boundary face.
+int build_axis_scalar(const Axis &a, std::vector<ScCell> &rows)
+{
+  const int64_t n = a.n;
+  struct FaceRow {
+    double ic, ap, am;
+  };
+  auto face = [&](int64_t f) -> FaceRow {
+    if (a.periodic) f = ((f % n) + n) % n;
+    else if (f < 0 || f > n) return {0., 0., 0.};
+    else if (f == 0) return {1. / (a.xcc(0) - a.xf[0]), 0., 0.};
+    else if (f == n) return {1. / (a.xf[n] - a.xcc(n - 1)), 0., 0.};
+    const double dc = a.xcc(f) - a.xcc(f - 1);
+    return {1. / dc, (a.xf[f] - a.xcc(f - 1)) / dc, (a.xcc(f) - a.xf[f]) / dc};
+  };
+  rows.assign((size_t)n, ScCell{});
+  for (int64_t i = 0; i < n; ++i) {
+    const FaceRow f0 = face(i - 1), f1 = face(i), f2 = face(i + 1), f3 = face(i + 2);
+    ScCell       &r  = rows[(size_t)i];
+    r.ic0 = f0.ic; r.ic1 = f1.ic; r.ic2 = f2.ic; r.ic3 = f3.ic;
+    r.ap0 = f1.ap; r.am0 = f1.am; r.ap1 = f2.ap; r.am1 = f2.am;
+    r.ih  = a.idx[(size_t)i];
+    r.pad = 0.;
+  }
+  return 0;
+}
+
 }  // namespace fl

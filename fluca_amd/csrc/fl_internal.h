@@ -55,6 +55,17 @@ constexpr int MOM_NTAB = 20;  // 1-D numbers per cell and axis of the momentum o
 int build_axis_momentum(const Axis &a, std::vector<double> &tab);
 int build_axis_faceinterp(const Axis &a, int kind, std::vector<double> &w0, std::vector<double> &w1, std::vector<int> &c0);
 
+// The 1-D numbers of the scalar transport operator (fl_scalar.hip) at cell a of an axis, periodic images resolved: a lane fetches them in five
+// 16-byte loads.  ic: 1 / (xc_f - xc_{f-1}) of the faces a-1 .. a+2 (a face on a non-periodic boundary: 1 / distance between the adjacent
+// centre and the face; a face beyond it: 0); ap / am: the interpolation factors alpha+ / alpha- of the faces a and a+1 (0 on a boundary face,
+// whose value is the boundary's own); ih: 1 / (xf_{a+1} - xf_a).
+struct alignas(16) ScCell {
+  double ic0, ic1, ic2, ic3;
+  double ap0, am0, ap1, am1;
+  double ih, pad;
+};
+int build_axis_scalar(const Axis &a, std::vector<ScCell> &rows);
+
 // ---- device view shared by every kernel ---------------------------------------------------------------------------
 // 1-D coefficient arrays are LOCAL (this rank's block) and pre-shifted: valid for index -1..len.
 struct GridP {

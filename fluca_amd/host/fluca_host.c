@@ -726,6 +726,7 @@ FlErrorCode NSCreate(NS *ns)
   n->max_steps = -1;
   n->max_time  = 1.7976931348623157e308;
   n->errorifstepfailed = 1;
+  n->scalar_stages = 5; /* the reference's -ts_type ssp default */
   n->bc_keep           = 1;
   fl_ksp_opts_default(&n->schur);
   fl_ksp_opts_default(&n->mom);
@@ -872,6 +873,16 @@ FlErrorCode NSSetFromOptions(NS ns, int argc, char **argv)
     if (!strcmp(s, "replicated")) ns->ibm_owner = 0;
     else if (!strcmp(s, "owner")) ns->ibm_owner = 1;
     else return E_ARG_UNKNOWN_TYPE;
+  }
+  /* passive scalars (NSAddScalar): the limiter of a scalar added without one, the stages of the SSP step */
+  if ((s = opt_find(argc, argv, "-ns_scalar_limiter"))) {
+    int l = 0;
+    if (fl_limiter_from_name(s, &l)) return E_ARG_UNKNOWN_TYPE;
+    ns->scalar_limiter = l;
+  }
+  if (opt_int64(argc, argv, "-ns_scalar_stages", &iv)) {
+    if (iv < 2 || iv > 1000) return E_ARG_OUTOFRANGE;
+    ns->scalar_stages = (int)iv;
   }
   /* mirror only: force and torque on the immersed bodies, one line per step and body (NSMonitorImmersedBoundaryForce) */
   if ((s = opt_find(argc, argv, "-ns_ibm_force_monitor"))) {
@@ -1071,6 +1082,7 @@ static FlErrorCode NSSetUp_Body(NS ns) /* nsbasic.c:153-274, restricted to what 
 }
 
 static FlErrorCode ibm_move(NS ns);
+static FlErrorCode scalars_step(NS ns);
 
 static FlErrorCode NSStep_Body(NS ns) /* nsbasic.c:276-299 */
 {
@@ -1079,6 +1091,7 @@ static FlErrorCode NSStep_Body(NS ns) /* nsbasic.c:276-299 */
   if (!ns->ops->step) return E_SUP;
   if (ns->ibm && ns->ibm_motion) FLCHK(ibm_move(ns)); /* the body in prescribed motion at t + dt, before the forcing term is formed */
   FLCHK(ns->ops->step(ns)); /* VecCopy(sol, sol0) + the type's step */
+  if (ns->reason >= 0 && ns->nscalar) FLCHK(scalars_step(ns)); /* every passive scalar over dt in the new V */
   if (ns->reason >= 0) {
     ++ns->step;
     ns->t += ns->dt;
@@ -1305,10 +1318,127 @@ FlErrorCode NSGetTime(NS ns, double *t)
 
 static void ibm_free_own(NS ns);
 
+/* ---- passive scalars (fluca_host.h) */
+#define MAXNSSCALARS 8
+static FlErrorCode scalar_get(NS ns, int id, struct NSScalar **sc)
+{
+  if (!ns) return E_ARG_NULL;
+  if (!ns->setupcalled) return E_ARG_WRONGSTATE;
+  if (id < 0 || id >= ns->nscalar) return E_ARG_OUTOFRANGE;
+  *sc = &ns->scalars[id];
+  return 0;
+}
+/* the handle, created with the boundary types as they stand and given the solution's face velocities */
+static FlErrorCode scalar_ensure(NS ns, struct NSScalar *sc)
+{
+  if (!sc->h) {
+    FLABI(fl_scalar_create(ns->poisson, sc->kind, &sc->h));
+    FLABI(fl_scalar_set_limiter(sc->h, sc->limiter));
+    FLABI(fl_scalar_set_diffusivity(sc->h, sc->gamma));
+    for (int b = 0; b < 6; ++b) FLABI(fl_scalar_set_boundary_value(sc->h, b, sc->val[b]));
+  }
+  double *V[3];
+  FLCHK(NSGetSolutionArrays(ns, NULL, V, NULL));
+  FLABI(fl_scalar_set_velocity(sc->h, V[0], V[1], V[2]));
+  return 0;
+}
+static FlErrorCode scalars_step(NS ns)
+{
+  for (int a = 0; a < ns->nscalar; ++a) {
+    struct NSScalar *sc = &ns->scalars[a];
+    FLCHK(scalar_ensure(ns, sc));
+    for (int k = 0; k < sc->substeps; ++k) FLABI(fl_scalar_step(sc->h, ns->dt / sc->substeps, ns->scalar_stages, sc->src, sc->phi));
+  }
+  return 0;
+}
+FlErrorCode NSAddScalar(NS ns, const char *name, double gamma, const char *limiter_name, int *id)
+{
+  if (!ns || !name || !id) return E_ARG_NULL;
+  if (!ns->setupcalled) return E_ARG_WRONGSTATE;
+  if (ns->mesh->size > 1) return E_SUP; /* several ranks: fl_scalar_create */
+  if (!(gamma >= 0.) || gamma > 1.7976931348623157e308 || strlen(name) > 31 || ns->nscalar >= MAXNSSCALARS) return E_ARG_OUTOFRANGE;
+  int limiter = ns->scalar_limiter;
+  if (limiter_name && fl_limiter_from_name(limiter_name, &limiter)) return E_ARG_UNKNOWN_TYPE;
+  if (!ns->scalars && !(ns->scalars = (struct NSScalar *)calloc(MAXNSSCALARS, sizeof(struct NSScalar)))) return E_MEM;
+  struct NSScalar *sc = &ns->scalars[ns->nscalar];
+  memset(sc, 0, sizeof(*sc));
+  strcpy(sc->name, name);
+  sc->gamma    = gamma;
+  sc->limiter  = limiter;
+  sc->substeps = 1;
+  Mesh_Cart *cart = (Mesh_Cart *)ns->mesh->data;
+  for (int b = 0; b < 6; ++b) sc->kind[b] = cart->bndTypes[b / 2] == MESHCART_BOUNDARY_PERIODIC ? 2 : 1;
+  int64_t sz[4];
+  FLABI(fl_poisson_sizes(ns->poisson, sz));
+  void *zero = calloc((size_t)sz[0], sizeof(double));
+  if (!zero) return E_MEM;
+  int rc = fl_malloc(ns->device, sizeof(double) * (size_t)sz[0], (void **)&sc->phi);
+  if (!rc) rc = fl_memcpy_h2d(ns->device, sc->phi, zero, sizeof(double) * (size_t)sz[0]);
+  free(zero);
+  if (rc) {
+    if (sc->phi) fl_free(ns->device, sc->phi);
+    sc->phi = NULL;
+    return -rc;
+  }
+  *id = ns->nscalar++;
+  return 0;
+}
+FlErrorCode NSSetScalarBoundaryCondition(NS ns, int id, int index, int type, double value)
+{
+  struct NSScalar *sc = NULL;
+  FLCHK(scalar_get(ns, id, &sc));
+  if (index < 0 || index > 5 || type < 0 || type > 2 || !(value - value == 0.)) return E_ARG_OUTOFRANGE;
+  if (sc->h && sc->kind[index] != type) { /* the types are the handle's: a new one with the next use */
+    FLABI(fl_scalar_destroy(sc->h));
+    sc->h = NULL;
+  }
+  sc->kind[index] = type;
+  sc->val[index]  = value;
+  if (sc->h) FLABI(fl_scalar_set_boundary_value(sc->h, index, value));
+  return 0;
+}
+FlErrorCode NSSetScalarSource(NS ns, int id, const double *src_dev)
+{
+  struct NSScalar *sc = NULL;
+  FLCHK(scalar_get(ns, id, &sc));
+  sc->src = src_dev;
+  return 0;
+}
+FlErrorCode NSSetScalarSubsteps(NS ns, int id, int n)
+{
+  struct NSScalar *sc = NULL;
+  FLCHK(scalar_get(ns, id, &sc));
+  if (n < 1) return E_ARG_OUTOFRANGE;
+  sc->substeps = n;
+  return 0;
+}
+FlErrorCode NSGetScalarArray(NS ns, int id, double **phi_dev)
+{
+  struct NSScalar *sc = NULL;
+  if (!phi_dev) return E_ARG_NULL;
+  FLCHK(scalar_get(ns, id, &sc));
+  *phi_dev = sc->phi;
+  return 0;
+}
+FlErrorCode NSGetScalarCFL(NS ns, int id, double out[2])
+{
+  struct NSScalar *sc = NULL;
+  if (!out) return E_ARG_NULL;
+  FLCHK(scalar_get(ns, id, &sc));
+  FLCHK(scalar_ensure(ns, sc));
+  FLABI(fl_scalar_cfl(sc->h, ns->dt / sc->substeps, out));
+  return 0;
+}
+
 FlErrorCode NSDestroy(NS *ns)
 {
   if (!ns || !*ns) return 0;
   NSMonitorCancel(*ns);
+  for (int a = 0; a < (*ns)->nscalar; ++a) { /* before the type's data and the Poisson handle they borrow */
+    if ((*ns)->scalars[a].h) fl_scalar_destroy((*ns)->scalars[a].h);
+    if ((*ns)->scalars[a].phi) fl_free((*ns)->device, (*ns)->scalars[a].phi);
+  }
+  free((*ns)->scalars);
   if ((*ns)->ops->destroy) (*ns)->ops->destroy(*ns);
   if ((*ns)->ibm) fl_ibm_destroy((*ns)->ibm);
   if ((*ns)->ibm_U) fl_free((*ns)->device, (*ns)->ibm_U);

@@ -1,0 +1,106 @@
+"""Passive scalar transport on top of the C-ABI (fl_scalar_*, include/fluca_hip.h): the right-hand side of the reference's transport
+equation -- second-order TVD convection with its eleven limiters, two-point diffusion, a source -- and the s-stage second-order SSP
+Runge-Kutta step of its tutorials (-ts_type ssp), one kernel launch per stage.  One rank only.
+"""
+import ctypes as C
+import weakref
+
+import torch
+
+from . import capi
+from .capi import check, lib
+from .poisson import _ptr
+
+DIRICHLET, NEUMANN, PERIODIC = capi.SCALAR_DIRICHLET, capi.SCALAR_NEUMANN, capi.SCALAR_PERIODIC
+LIMITERS = capi.LIMITERS
+
+
+def limiter_from_name(name):
+    out = C.c_int(-1)
+    check(lib.fl_limiter_from_name(name.encode(), C.byref(out)), f"fl_limiter_from_name({name!r})")
+    return out.value
+
+
+def limiter_eval(limiter, r):
+    out = C.c_double()
+    check(lib.fl_limiter_eval(int(limiter), float(r), C.byref(out)), "fl_limiter_eval")
+    return out.value
+
+
+class Scalar:
+    """bc: six kinds (DIRICHLET / NEUMANN / PERIODIC) in the order of the grid's boundaries; values: the six boundary values (a Neumann value is
+    the derivative along the +axis).  The Poisson handle lends its grid, device and stream and must outlive this one."""
+
+    def __init__(self, poisson, bc, values=None, limiter="superbee", gamma=0.0):
+        self.P = poisson
+        self.bc = tuple(int(b) for b in bc)
+        h = C.c_void_p()
+        check(lib.fl_scalar_create(poisson.h, (C.c_int * 6)(*self.bc), C.byref(h)), "fl_scalar_create")
+        self.h = h
+        poisson._children.append(weakref.ref(self))
+        self._V = None
+        for b, v in enumerate(values or ()):
+            self.set_boundary_value(b, v)
+        self.set_limiter(limiter)
+        self.set_diffusivity(gamma)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib.fl_scalar_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_boundary_value(self, boundary, value):
+        check(lib.fl_scalar_set_boundary_value(self.h, int(boundary), float(value)), "fl_scalar_set_boundary_value")
+
+    def set_limiter(self, limiter):
+        self.limiter = limiter_from_name(limiter) if isinstance(limiter, str) else int(limiter)
+        check(lib.fl_scalar_set_limiter(self.h, self.limiter), "fl_scalar_set_limiter")
+
+    def set_diffusivity(self, gamma):
+        check(lib.fl_scalar_set_diffusivity(self.h, float(gamma)), "fl_scalar_set_diffusivity")
+
+    def set_velocity(self, Vx, Vy, Vz):
+        """face velocities in the layouts of Poisson.rhs; borrowed (kept alive here) until the next call"""
+        for t, n in zip((Vx, Vy, Vz), self.P.nface):
+            assert t.numel() == n, "face array of the wrong length"
+        self._V = (Vx, Vy, Vz)
+        check(lib.fl_scalar_set_velocity(self.h, _ptr(Vx), _ptr(Vy), _ptr(Vz)), "fl_scalar_set_velocity")
+
+    def rhs(self, phi, source=None, out=None):
+        assert phi.numel() == self.P.ncell and (source is None or source.numel() == self.P.ncell)
+        out = self.P.empty() if out is None else out
+        self.P._pre()
+        check(lib.fl_scalar_rhs(self.h, _ptr(phi), _ptr(source), _ptr(out)), "fl_scalar_rhs")
+        self.P._post()
+        return out
+
+    def step(self, phi, dt, nstages=5, source=None):
+        """advance phi in place over dt"""
+        assert phi.numel() == self.P.ncell and (source is None or source.numel() == self.P.ncell)
+        self.P._pre()
+        check(lib.fl_scalar_step(self.h, float(dt), int(nstages), _ptr(source), _ptr(phi)), "fl_scalar_step")
+        self.P._post()
+        return phi
+
+    def cfl(self, dt):
+        """-> (convective, diffusive) Courant numbers of a step dt"""
+        out = (C.c_double * 2)()
+        self.P._pre()
+        check(lib.fl_scalar_cfl(self.h, float(dt), out), "fl_scalar_cfl")
+        self.P._post()
+        return out[0], out[1]
+
+    def stats(self, phi):
+        """-> (min, max, sum phi vol)"""
+        assert phi.numel() == self.P.ncell
+        out = (C.c_double * 3)()
+        self.P._pre()
+        check(lib.fl_scalar_stats(self.h, _ptr(phi), out), "fl_scalar_stats")
+        self.P._post()
+        return out[0], out[1], out[2]

@@ -519,6 +519,47 @@ int fl_ibm_rigid_pose(fl_poisson *grid_from, int64_t L, const double *X0_dev, co
  *   FL_ERR_SUP             2^22 markers or more over all ranks (the exact sums are guaranteed below that) */
 int fl_ibm_force(fl_ibm *m, const double *F_dev, const double *dV_dev, const int32_t *body_dev, int nbody, const double *about, double *force, double *torque);
 
+/* ---- passive scalar transport ------------------------------------------------------------------------------------------------------------
+ * phi (cells) carried by the face velocities V_d (the layouts of fl_poisson_rhs), the right-hand side of the reference's transport equation
+ * (FlucaFDSecondOrderTVD, scale by velocity, face -> element derivative, second derivative; fluca/tutorials/fd/ex2.c - ex4.c):
+ *   R(phi)(c) = - sum_d [V_d(f+) phi_f(f+) - V_d(f-) phi_f(f-)] / h_d(c) + Gamma sum_d [g_d(f+) - g_d(f-)] / h_d(c) + q(c)
+ * h_d(c): face-to-face width; g_d(f) = (phi_i - phi_{i-1}) / (xc_i - xc_{i-1}) at face i; phi_f the limited face value of secondordertvd.c:187-356:
+ *   V > 0:     phi_u = phi_{i-1}, phi_d = phi_i,     r = g(i-1) / g(i), alpha = (xf_i - xc_{i-1}) / (xc_i - xc_{i-1})
+ *   otherwise: phi_u = phi_i,     phi_d = phi_{i-1}, r = g(i+1) / g(i), alpha = (xc_i - xf_i) / (xc_i - xc_{i-1})
+ *   phi_f = phi_u + alpha psi(r) (phi_d - phi_u),  r = 1 where |g(i)| <= 1e-30
+ * psi: one of the reference's eleven limiters, in its registration order: superbee 0, minmod 1, mc 2, vanleer 3, vanalbada 4, barthjesperson 5,
+ * venkatakrishnan 6, koren 7, upwind 8, sou 9, quick 10.
+ * Boundaries, one kind and one value per end of an axis (bc[6] in the order of fl_bc's index): 0 Dirichlet (value), 1 Neumann (the derivative along
+ * the +AXIS, not the outward normal, as FlucaFD has it), 2 periodic (both ends, and exactly on the grid's periodic axes).  The gradient of a
+ * boundary face is (phi_0 - phi_b) / (xc_0 - xf_0) (Dirichlet; mirrored at the high end) or the value (Neumann); the face VALUE there is the
+ * boundary's own for either flow direction: phi_b, or phi_near -/+ (distance centre -- face) g.  For inflow that is what FlucaFD's ghost
+ * elimination gives; for outflow the reference reads a ghost cell it never fills, which this library does not restate.
+ * One rank only: a handle on a decomposed grid is FL_ERR_SUP (several ranks need a two-deep ghost of phi and a ring of V: not built yet). */
+typedef struct fl_scalar fl_scalar;
+/* the reference's limiter names (-flucafd_limiter); host only.  Unknown name: FL_ERR_ARG_OUTOFRANGE */
+int fl_limiter_from_name(const char *name, int *limiter);
+/* psi(r) on the host, by the same functions the kernel compiles */
+int fl_limiter_eval(int limiter, double r, double *psi);
+/* grid_from is borrowed (grid, device, stream) and must outlive the handle.  Defaults: all boundary values 0, superbee, Gamma = 0.
+ * FL_ERR_ARG_OUTOFRANGE: a kind outside 0..2; FL_ERR_ARG_WRONG: periodic flags that disagree with the grid; FL_ERR_SUP: more than one rank */
+int fl_scalar_create(fl_poisson *grid_from, const int bc[6], fl_scalar **out);
+int fl_scalar_destroy(fl_scalar *m); /* NULL is success */
+int fl_scalar_set_boundary_value(fl_scalar *m, int boundary, double value);
+int fl_scalar_set_limiter(fl_scalar *m, int limiter); /* default superbee, as the reference */
+int fl_scalar_set_diffusivity(fl_scalar *m, double gamma); /* >= 0, finite */
+/* device arrays, borrowed until the next call of this function: read by rhs / step / cfl at the time of THEIR call */
+int fl_scalar_set_velocity(fl_scalar *m, const double *Vx_dev, const double *Vy_dev, const double *Vz_dev);
+/* out = R(phi); source_dev (q, cells) may be NULL; out_dev must not be phi_dev (FL_ERR_ARG_WRONG).  FL_ERR_ARG_WRONGSTATE before a velocity is set */
+int fl_scalar_rhs(fl_scalar *m, const double *phi_dev, const double *source_dev, double *out_dev);
+/* One step of the s-stage second-order SSP Runge-Kutta method (Ketcheson; PETSc -ts_type ssp, rks2), in place, V and q frozen:
+ *   w = phi; s-1 times w += dt/(s-1) R(w); phi = ((s-1) w + phi + dt R(w)) / s.     nstages = s >= 2 (the reference's default: 5).
+ * One kernel launch per stage, 40 B/cell each (48 the last). */
+int fl_scalar_step(fl_scalar *m, double dt, int nstages, const double *source_dev, double *phi_dev);
+/* out[0] = max_c dt sum_d max(|V(f-)|, |V(f+)|) / h_d ; out[1] = max_c Gamma dt sum_d 2 / h_d^2.  Waits for the stream */
+int fl_scalar_cfl(fl_scalar *m, double dt, double out[2]);
+/* out = { min phi, max phi, sum_c phi(c) vol(c) }, the sum in a fixed order (the same bits on every call).  Waits for the stream */
+int fl_scalar_stats(fl_scalar *m, const double *phi_dev, double out[3]);
+
 #ifdef __cplusplus
 }
 #endif

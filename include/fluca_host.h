@@ -24,6 +24,7 @@
  *   pressure update of NSStep_CNLinear_Cart3d_Internal (NSUpdatePressure)                               fluca/src/ns/impl/linearcn/cnlinearcart3d.c:2846-2854
  *   options -cart_grid_x.. -cart_ranks_x.. -cart_boundary_type_x.. -ns_density -ns_viscosity
  *           -ns_time_step_size -ns_max_steps -ns_abf_schur_ksp_{type,rtol,atol,max_it,norm_type} -ns_abf_schur_pc_type   cart.c:21-43, nsopts.c:177-198, abfpc.c:206,248-249
+ *           -ns_scalar_limiter -ns_scalar_stages (passive scalars, NSAddScalar)
  *           (-ns_abf_schur_pc_type mg [-ns_abf_schur_pc_mg_levels N -ns_abf_schur_mg_levels_ksp_max_it NU]: the build's own multigrid)
  *
  * Every function returns FlErrorCode: 0 = success, otherwise the positive PETSC_ERR_* value the reference would raise.
@@ -256,6 +257,24 @@ FlErrorCode NSSetImmersedBoundaryBodies(NS ns, int nbody, const int32_t *body_de
  * per completed step and body, rank 0 appends the line  step t body F_x F_y F_z T_x T_y T_z  (%.17g; torques about the default points of
  * NSGetImmersedBoundaryForce).  Collective; does nothing before the first step or when the last step has been written already. */
 FlErrorCode NSMonitorImmersedBoundaryForce(NS ns, void *ctx);
+/* PASSIVE SCALARS (temperature, concentration, dye): phi_t + div(V phi) = Gamma lap(phi) + q by fl_scalar_* (include/fluca_hip.h) -- the
+ * reference's FlucaFDSecondOrderTVD right-hand side, advanced as its tutorials do (-ts_type ssp: the s-stage second-order SSP Runge-Kutta method).
+ * After the flow step has produced V^(n+1), NSStep advances every scalar over dt with THAT V, in n equal substeps (NSSetScalarSubsteps, default 1):
+ * the velocity is frozen over the step, so the coupling of scalar and flow is first order in time.  With no scalar registered NSStep launches
+ * nothing new.  After NSSetUp; one rank only (PETSC_ERR_SUP on a decomposed mesh).  At most 8 scalars.
+ *   NSAddScalar       name (<= 31 characters), Gamma >= 0, the limiter's name as the reference spells it (NULL: -ns_scalar_limiter, default superbee);
+ *                     the field starts at 0 (write the initial condition through NSGetScalarArray); *id = 0, 1, ...
+ *   boundary          index as NSSetBoundaryCondition's; type 0 Dirichlet, 1 Neumann (the derivative along the +AXIS), 2 periodic (exactly on the
+ *                     mesh's periodic axes: checked when the scalar is first used).  Default: periodic where the mesh is, else Neumann 0.
+ *   source            q, a device array of one value per cell, borrowed; NULL (default): none
+ *   NSGetScalarCFL    { convective, diffusive } Courant number of ONE SUBSTEP with the current V (fl_scalar_cfl)
+ * Options: -ns_scalar_limiter <name>, -ns_scalar_stages <s> (>= 2, default 5). */
+FlErrorCode NSAddScalar(NS ns, const char *name, double gamma, const char *limiter_name, int *id);
+FlErrorCode NSSetScalarBoundaryCondition(NS ns, int id, int index, int type, double value);
+FlErrorCode NSSetScalarSource(NS ns, int id, const double *src_dev);
+FlErrorCode NSSetScalarSubsteps(NS ns, int id, int n);
+FlErrorCode NSGetScalarArray(NS ns, int id, double **phi_dev);
+FlErrorCode NSGetScalarCFL(NS ns, int id, double out[2]);
 FlErrorCode NSGetSolutionArrays(NS ns, double **v_dev, double *V_dev[3], double **p_dev);
 FlErrorCode NSGetPressureHalfStep(NS ns, double **phalf_dev); /* cnl->phalf, the vector named "PressureHalfStep" (cnlinear.c:54) */
 FlErrorCode NSGetMesh(NS ns, Mesh *mesh);

@@ -123,6 +123,19 @@ struct _p_NS {
   void                *ibm_body_own;     /* owner: this rank's share of the ids (device, owned by the NS), room for ibm_body_cap of them */
   int64_t              ibm_body_cap;
   int64_t              ibm_mon_step;     /* the step NSMonitorImmersedBoundaryForce wrote last */
+  /* passive scalars (NSAddScalar): advanced by NSStep after the flow step, with the new face velocities frozen over the step */
+  int                  nscalar;
+  struct NSScalar     *scalars;          /* nscalar entries */
+  int                  scalar_stages;    /* -ns_scalar_stages (default 5, the reference's -ts_type ssp) */
+  int                  scalar_limiter;   /* -ns_scalar_limiter: the limiter of a scalar added without a name of its own (default superbee) */
+};
+struct NSScalar {
+  char          name[32];
+  fl_scalar    *h;        /* created by the first use, destroyed when a boundary TYPE changes */
+  double        gamma, val[6];
+  int           limiter, substeps, kind[6];
+  double       *phi;      /* device, owned by the NS */
+  const double *src;      /* device, borrowed; may be NULL */
 };
 
 /* NSCNLINEAR's data (nslinearcnimpl.h: v0interp, phalf, B) plus, in this mirror, the solution and solver vectors the

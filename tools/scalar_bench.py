@@ -1,0 +1,106 @@
+"""Time the passive-scalar stage kernel (fl_scalar.hip): one stage (fl_scalar_rhs: 40 B/cell compulsory) and one five-stage step (fl_scalar_step:
+4 x 40 + 48 B/cell) at N^3 with HIP events -- inputs resident, warm-up, the spread over the repeats -- and, in the same process, the box's own
+copy rate (a device-to-device copy of one field: 16 B/cell) and the fl_abf_schur_apply call with schurainv = DIAG, whose k_schur_var is the
+project's other no-LDS kernel with a five-cell window.  Counter bytes (FETCH_SIZE, WRITE_SIZE) and kernel durations come from rocprofv3 runs of
+their own over this script (--only-scalar keeps them short); profiles/README.md has the command lines.
+
+usage: python tools/scalar_bench.py [--cells 256 512] [--reps 20] [--limiter superbee] [--only-scalar] [--out FILE]"""
+import argparse
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import numpy as np
+import torch
+
+from fluca_amd.poisson import Momentum, Poisson
+from fluca_amd.scalar import DIRICHLET, NEUMANN, PERIODIC, Scalar
+from oracle import fluca_oracle as fo
+
+
+def timed(fn, reps, warm=3):
+    """-> sorted times in ms of `reps` calls, each bracketed by HIP events on the current stream"""
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return sorted(out)
+
+
+def line(what, ms, bytes_per_cell, ncell, extra=""):
+    med = statistics.median(ms)
+    return f"  {what:<44s} median {med:8.4f} ms  (min {ms[0]:.4f}, max {ms[-1]:.4f}, {len(ms)} repeats)  {bytes_per_cell:4d} B/cell compulsory -> {bytes_per_cell * ncell / med / 1e9:7.3f} TB/s{extra}"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cells", type=int, nargs="+", default=[256, 512])
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--limiter", default="superbee")
+    ap.add_argument("--only-scalar", action="store_true")
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "scalar_bench.py needs a GPU"
+    # one stream of its own for the library's kernels, torch's copies and the events that bracket them (the null stream would send the library
+    # back to the handle's own stream, and the events would time nothing)
+    stream = torch.cuda.Stream()
+    torch.cuda.set_stream(stream)
+    lines = [f"tools/scalar_bench.py --cells {' '.join(map(str, a.cells))} --reps {a.reps} --limiter {a.limiter}   ({torch.cuda.get_device_name(0)})"]
+    for n in a.cells:
+        V_, PER = fo.BC_VELOCITY, fo.BC_PERIODIC
+        xf = [np.linspace(0.0, 1.0, n + 1) for _ in range(3)]
+        P = Poisson((n, n, n), xf, [V_, V_, V_, V_, PER, PER], 1e-3)
+        P.set_stream(stream)
+        N = n ** 3
+        g = torch.Generator(device="cuda").manual_seed(3)
+        rnd = lambda m: torch.rand(m, dtype=torch.float64, device="cuda", generator=g) - 0.5
+        # a channel: Dirichlet x-, Neumann 0 at x+, Neumann in y, periodic z
+        S = Scalar(P, (DIRICHLET, NEUMANN, NEUMANN, NEUMANN, PERIODIC, PERIODIC), (1.0, 0.0, 0.0, 0.0, 0.0, 0.0), limiter=a.limiter, gamma=1e-3)
+        V = [rnd(P.nface[d]) for d in range(3)]
+        S.set_velocity(*V)
+        phi, out = rnd(N) + 0.5, torch.empty(N, dtype=torch.float64, device="cuda")
+        dt = 0.2 / n
+        lines.append(f"{n}^3 cells ({N * 8 / 2 ** 30:.2f} GiB a field), limiter {a.limiter}, Gamma 1e-3, random V and phi")
+        if not a.only_scalar:
+            copy = timed(lambda: out.copy_(phi), a.reps)
+            lines.append(line("device-to-device copy of one field", copy, 16, N))
+        stage = timed(lambda: S.rhs(phi, out=out), a.reps)
+        step = timed(lambda: S.step(phi, dt, 5), a.reps)
+        if a.only_scalar:
+            lines.append(line("one stage (fl_scalar_rhs)", stage, 40, N))
+            lines.append(line("one five-stage step (fl_scalar_step)", step, 208, N))
+        else:
+            rate = 16 * N / statistics.median(copy)
+            frac = lambda ms, b: f"  = {b * N / statistics.median(ms) / rate:5.1%} of the copy rate"
+            lines.append(line("one stage (fl_scalar_rhs)", stage, 40, N, frac(stage, 40)))
+            lines.append(line("one five-stage step (fl_scalar_step)", step, 208, N, frac(step, 208)))
+            M = Momentum(P)
+            v0 = 8.0 * rnd(3 * N)
+            M.set_state(1e-3, 1.0, 0.05, [8.0 * v for v in V], M.interp_faces(v0), v0=v0)
+            M.set_ainv_types(schur=fo.AINV_DIAG)
+            p = rnd(N)
+            sv = timed(lambda: M.schur_apply(p), a.reps)
+            lines.append(line("fl_abf_schur_apply, DIAG (k_schur_var + set-up)", sv, 40, N, f"  stage / this call = {statistics.median(stage) / statistics.median(sv):.3f}"))
+            M.close()
+        S.close()
+        P.close()
+        del V, phi, out
+        torch.cuda.empty_cache()
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -175,6 +175,7 @@ PROTOTYPES = {
     "fl_limiter_from_name": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     "fl_limiter_eval": (C.c_int, [C.c_int, C.c_double, C.POINTER(C.c_double)]),
     "fl_scalar_create": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(_P)]),
+    "fl_scalar_create_ranks": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(_P)]),
     "fl_scalar_destroy": (C.c_int, [_P]),
     "fl_scalar_set_boundary_value": (C.c_int, [_P, C.c_int, C.c_double]),
     "fl_scalar_set_limiter": (C.c_int, [_P, C.c_int]),

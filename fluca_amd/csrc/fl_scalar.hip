@@ -9,7 +9,15 @@
 // compulsory traffic (48 in the stage that also reads phi^n).  The sweep is k_schur_var's (fl_schur_var.hip): no LDS, a lane owns one cell of
 // a 64-cell row segment, the rows dealt so that an XCD works through one band of y plane after plane.  What differs: w is read from the caller's
 // UNPADDED array -- a cell outside the line is its periodic image (fetched from where it lives) or is replaced by the boundary rule, so no
-// copy into a padded vector and no ghost fill stand between two stages, and a stage is one launch.  One rank only (fl_scalar_create).
+// copy into a padded vector and no ghost fill stand between two stages, and a stage is one launch.
+//
+// Several ranks (fl_scalar_create_ranks, k_scalar_stage_ring): the same sweep over the rank's block.  Behind an end of an axis where a neighbouring
+// rank sits, the cells -2, -1 / n, n+1 of w come from a GHOST SLAB -- two planes of the neighbour's outermost cells, [layer][line in the plane],
+// the plane's fast index the block's fastest in-plane axis (the y and z slabs are read x-contiguously by a wave) -- and the boundary rule does not
+// apply: the cell is an interior cell.  The window is a star, so no edge or corner cells travel: at most six slabs, one exchange per stage.  The
+// velocity of the face n the next rank owns is the handle's hiface plane (fl_fill_hifaces).  A stage that is not the last of a step stores the cells
+// it writes within two layers of a rank face into that boundary's send slab as well, so one exchange and one launch stand between two stages.
+// The exchange is NOT overlapped with the sweep: that would take a second launch over a shell that is a few per cent of the block (as k_schur_var_ring).
 #include "fl_device.h"
 #include "fl_handle.h"
 #include "fl_limiter.h"
@@ -48,15 +56,44 @@ __device__ __forceinline__ double sc_face(bool up, double Pm, double Pp, double 
   return pu + al * limiter<L>(r) * (pd - pu);
 }
 
+// Several ranks: what differs from the one-rank sweep is where the cells outside the block come from.  One end of an axis of a rank's block:
+// nlo / nhi a neighbouring rank sits behind the low / high end, r the four layers received across them (np: lines of the plane, pr: this lane's line)
+struct ScEnds {
+  bool          nlo, nhi;
+  const double *r;
+  int64_t       np, pr;
+};
+// w at cell m of the line: behind an end with a neighbouring rank the cell -2, -1 / n, n+1 is layer m + 2 / m - n + 2 of e.r; elsewhere as
+// sc_ld.  Branches, not a selected address: along y and z they are wave-uniform, along x only the waves at the ends of a row take them.
+__device__ __forceinline__ double sc_ld_ring(const double *__restrict__ w, int64_t c0, int64_t cs, int m, int n, bool wraps, const ScEnds &e)
+{
+  if (m < 0 && e.nlo) return e.r[(m + 2) * e.np + e.pr];
+  if (m >= n && e.nhi) return e.r[(m - n + 2) * e.np + e.pr];
+  return sc_ld(w, c0, cs, m, n, wraps);
+}
+
 // The contribution of one axis to R at cell a of a line: [ -(V1 f1 - V0 f0) + Gamma (g(a+1) - g(a)) ] / h_a, with V0 / V1 the velocities
 // of the faces a / a+1.  klo / khi, vlo / vhi: kind and value of the boundaries at the ends of the axis (unused where it wraps).
-template <int L>
+// RING (k_scalar_stage_ring): the five cells may come from the slabs of e, and an end with a neighbouring rank is no physical boundary -- the cell
+// behind it is an interior cell.  Only the five loads and the predicates lo0 / lo1 / hi0 / hi1 differ; the arithmetic is this one piece of source.
+template <int L, bool RING>
 __device__ __forceinline__ double sc_axis(const ScCell &T, const double *__restrict__ w, int a, int n, bool wraps, int klo, int khi, double vlo, double vhi, double dlo, double dhi,
-                                          int64_t c0, int64_t cs, double V0, double V1, double gamma)
+                                          int64_t c0, int64_t cs, double V0, double V1, double gamma, const ScEnds &e)
 {
-  double       P0 = sc_ld(w, c0, cs, a - 2, n, wraps), P1 = sc_ld(w, c0, cs, a - 1, n, wraps), P3 = sc_ld(w, c0, cs, a + 1, n, wraps), P4 = sc_ld(w, c0, cs, a + 2, n, wraps);
+  double P0, P1, P3, P4;
+  bool   lo0, lo1, hi0, hi1;
+  if constexpr (RING) {
+    P0 = sc_ld_ring(w, c0, cs, a - 2, n, wraps, e), P1 = sc_ld_ring(w, c0, cs, a - 1, n, wraps, e), P3 = sc_ld_ring(w, c0, cs, a + 1, n, wraps, e), P4 = sc_ld_ring(w, c0, cs, a + 2, n, wraps, e);
+  } else {
+    P0 = sc_ld(w, c0, cs, a - 2, n, wraps), P1 = sc_ld(w, c0, cs, a - 1, n, wraps), P3 = sc_ld(w, c0, cs, a + 1, n, wraps), P4 = sc_ld(w, c0, cs, a + 2, n, wraps);
+  }
   const double P2 = w[c0 + a * cs];
-  const bool   lo0 = !wraps && a == 0, lo1 = !wraps && a == 1, hi0 = !wraps && a == n - 1, hi1 = !wraps && a == n - 2;
+  if constexpr (RING) {
+    const bool plo = !wraps && !e.nlo, phi = !wraps && !e.nhi;
+    lo0 = plo && a == 0, lo1 = plo && a == 1, hi0 = phi && a == n - 1, hi1 = phi && a == n - 2;
+  } else {
+    lo0 = !wraps && a == 0, lo1 = !wraps && a == 1, hi0 = !wraps && a == n - 1, hi1 = !wraps && a == n - 2;
+  }
   // Dirichlet: the boundary value stands where the cell beyond the boundary would (the table's 1 / distance is that of centre -- face)
   if (klo == 0) {
     if (lo0) P1 = vlo;
@@ -104,6 +141,7 @@ __global__ void __launch_bounds__(256, sc_minblocks(L)) k_scalar_stage(ScGrid g,
   const bool   fixed_seg = ((int64_t)nlb * nw) % nseg == 0;
   const int    seg0 = (int)(((int64_t)lb * nw + wv) % nseg), i0 = min(seg0 * 64 + lane, g.nx - 1);
   const ScCell X0 = g.c[0][i0];
+  const ScEnds none = {false, false, nullptr, 0, 0};  // (one rank: not read)
   for (int64_t it = (int64_t)lb * nw + wv; it < nitem; it += (int64_t)nlb * nw) {
     const int seg = (int)(it % nseg), row = (int)(it / nseg);
     const int j = j0 + row % nj, k = row / nj, i = seg * 64 + lane;
@@ -111,15 +149,107 @@ __global__ void __launch_bounds__(256, sc_minblocks(L)) k_scalar_stage(ScGrid g,
     const int64_t urow = ((int64_t)k * g.ny + j) * g.nx, c = urow + i;
     const int     ip = (i + 1 == g.nx && wx) ? 0 : i + 1, jp = (j + 1 == g.ny && wy) ? 0 : j + 1, kp = (k + 1 == g.nz && wz) ? 0 : k + 1;
     const int64_t vxr = ((int64_t)k * g.ny + j) * fx, vyr = (int64_t)k * fy * g.nx + i;
-    double acc = sc_axis<L>(fixed_seg ? X0 : g.c[0][i], w, i, g.nx, wx, g.kind[0], g.kind[1], g.val[0], g.val[1], g.dlo[0], g.dhi[0], urow, 1, Vx[vxr + i], Vx[vxr + ip], g.gamma);
-    acc += sc_axis<L>(g.c[1][j], w, j, g.ny, wy, g.kind[2], g.kind[3], g.val[2], g.val[3], g.dlo[1], g.dhi[1], (int64_t)k * nxy + i, g.nx, Vy[vyr + (int64_t)j * g.nx],
-                      Vy[vyr + (int64_t)jp * g.nx], g.gamma);
-    acc += sc_axis<L>(g.c[2][k], w, k, g.nz, wz, g.kind[4], g.kind[5], g.val[4], g.val[5], g.dlo[2], g.dhi[2], (int64_t)j * g.nx + i, nxy, Vz[c], Vz[(int64_t)kp * nxy + (int64_t)j * g.nx + i],
-                      g.gamma);
+    double acc = sc_axis<L, false>(fixed_seg ? X0 : g.c[0][i], w, i, g.nx, wx, g.kind[0], g.kind[1], g.val[0], g.val[1], g.dlo[0], g.dhi[0], urow, 1, Vx[vxr + i], Vx[vxr + ip], g.gamma, none);
+    acc += sc_axis<L, false>(g.c[1][j], w, j, g.ny, wy, g.kind[2], g.kind[3], g.val[2], g.val[3], g.dlo[1], g.dhi[1], (int64_t)k * nxy + i, g.nx, Vy[vyr + (int64_t)j * g.nx],
+                      Vy[vyr + (int64_t)jp * g.nx], g.gamma, none);
+    acc += sc_axis<L, false>(g.c[2][k], w, k, g.nz, wz, g.kind[4], g.kind[5], g.val[4], g.val[5], g.dlo[2], g.dhi[2], (int64_t)j * g.nx + i, nxy, Vz[c], Vz[(int64_t)kp * nxy + (int64_t)j * g.nx + i],
+                      g.gamma, none);
     if (q) acc += __builtin_nontemporal_load(q + c);
     double r = c1 * w[c] + c2 * acc;
     if (HASN) r += c0 * __builtin_nontemporal_load(phin + c);
     __builtin_nontemporal_store(r, out + c);
+  }
+}
+
+// What a rank's block of several reads and writes beside its own arrays (all wave-uniform: scalar registers).  recv / send: the slabs received and
+// sent, ONE array each -- 31 separate pointers and flags cost the kernel scalar registers it does not have -- of four layers per axis, the axes one
+// after the other: layers 0, 1 of axis d belong to its low end, 2, 3 to its high end (so a cell m outside the line is layer m + 2 or m - n + 2 of
+// recv, and the cells 0, 1 / n-2, n-1 are the layers 0, 1 / 2, 3 of send).  vhi[d]: the velocity of the face n of axis d where the next rank owns it (the
+// handle's hiface plane).  pack: the boundaries (bits as nb) whose send layers this stage fills -- 0 in the last stage of a step and in fl_scalar_rhs.
+struct ScRing {
+  const double *recv, *vhi[3];
+  double       *send;
+  int           pack;
+};
+
+// k_scalar_stage on one rank's block of several; nb: bit 2 d / 2 d + 1 = a neighbouring rank behind the low / high end of axis d.  g: the block (per: the
+// periodic axes the rank holds alone), the tables cut to its rows.  A cell within two layers of a rank face is also stored into that face's send
+// layers (what the peer reads as its cells n, n+1 / -2, -1).
+template <int L, bool HASN>
+__global__ void __launch_bounds__(256, sc_minblocks(L)) k_scalar_stage_ring(ScGrid g, ScRing rg, int nb, double c0, double c1, double c2, const double *phin, const double *__restrict__ w,
+                                                                          const double *__restrict__ Vx, const double *__restrict__ Vy, const double *__restrict__ Vz,
+                                                                          const double *__restrict__ q, double *out)
+{
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+  const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, nlb = gridDim.x >> 3;
+  const int band = (g.ny + 7) / 8, j0 = xcd * band, j1 = min(j0 + band, g.ny);
+  if (j0 >= j1) return;
+  const int     nseg = (g.nx + 63) / 64, nj = j1 - j0;
+  const int64_t nitem = (int64_t)nseg * nj * g.nz, nxy = (int64_t)g.nx * g.ny, nyz = (int64_t)g.ny * g.nz, nxz = (int64_t)g.nx * g.nz;
+  const bool    wx = g.per & 1, wy = g.per & 2, wz = g.per & 4;
+  const bool    lx = nb & 1, hx = nb & 2, ly = nb & 4, hy = nb & 8, lz = nb & 16, hz = nb & 32;
+  const int     fx = (wx || hx) ? g.nx : g.nx + 1, fy = (wy || hy) ? g.ny : g.ny + 1;  // the faces the block owns along x / y
+  const bool    fixed_seg = ((int64_t)nlb * nw) % nseg == 0;
+  const int     seg0 = (int)(((int64_t)lb * nw + wv) % nseg), i0 = min(seg0 * 64 + lane, g.nx - 1);
+  const ScCell  X0 = g.c[0][i0];
+  for (int64_t it = (int64_t)lb * nw + wv; it < nitem; it += (int64_t)nlb * nw) {
+    const int seg = (int)(it % nseg), row = (int)(it / nseg);
+    const int j = j0 + row % nj, k = row / nj, i = seg * 64 + lane;
+    if (i >= g.nx) continue;
+    const int64_t urow = ((int64_t)k * g.ny + j) * g.nx, c = urow + i;
+    const int64_t prx = (int64_t)k * g.ny + j, pry = (int64_t)k * g.nx + i, prz = (int64_t)j * g.nx + i;  // this cell's line in the planes across x / y / z
+    const int     ip = (i + 1 == g.nx && wx) ? 0 : i + 1, jp = (j + 1 == g.ny && wy) ? 0 : j + 1, kp = (k + 1 == g.nz && wz) ? 0 : k + 1;
+    const int64_t vxr = prx * fx, vyr = (int64_t)k * fy * g.nx + i;
+    // the face behind the last cell where the next rank owns it: the hiface plane
+    const double *v1x = (hx && i + 1 == g.nx) ? rg.vhi[0] + prx : Vx + vxr + ip, *v1y = (hy && j + 1 == g.ny) ? rg.vhi[1] + pry : Vy + vyr + (int64_t)jp * g.nx,
+                 *v1z = (hz && k + 1 == g.nz) ? rg.vhi[2] + prz : Vz + (int64_t)kp * nxy + prz;
+    // (of the x row a wave with a fixed segment keeps the first six numbers; ap1, am1 and ih -- two 16-byte loads -- are fetched with every row: kept
+    // as well, they are the registers that the slab reads and the pack need, and one of them went to scratch)
+    ScCell TX = g.c[0][i];
+    if (fixed_seg) { TX.ic0 = X0.ic0; TX.ic1 = X0.ic1; TX.ic2 = X0.ic2; TX.ic3 = X0.ic3; TX.ap0 = X0.ap0; TX.am0 = X0.am0; }
+    double acc = sc_axis<L, true>(TX, w, i, g.nx, wx, g.kind[0], g.kind[1], g.val[0], g.val[1], g.dlo[0], g.dhi[0], urow, 1, Vx[vxr + i], *v1x, g.gamma,
+                                  ScEnds{lx, hx, rg.recv, nyz, prx});
+    acc += sc_axis<L, true>(g.c[1][j], w, j, g.ny, wy, g.kind[2], g.kind[3], g.val[2], g.val[3], g.dlo[1], g.dhi[1], (int64_t)k * nxy + i, g.nx, Vy[vyr + (int64_t)j * g.nx], *v1y, g.gamma,
+                            ScEnds{ly, hy, rg.recv + 4 * nyz, nxz, pry});
+    acc += sc_axis<L, true>(g.c[2][k], w, k, g.nz, wz, g.kind[4], g.kind[5], g.val[4], g.val[5], g.dlo[2], g.dhi[2], prz, nxy, Vz[c], *v1z, g.gamma, ScEnds{lz, hz, rg.recv + 4 * (nyz + nxz), nxy, prz});
+    if (q) acc += __builtin_nontemporal_load(q + c);
+    double r = c1 * w[c] + c2 * acc;
+    if (HASN) r += c0 * __builtin_nontemporal_load(phin + c);
+    __builtin_nontemporal_store(r, out + c);
+    // the fused pack: the next stage's exchange sends these slabs as they are
+    if (rg.pack) {
+      // (the lines are formed again from the row's numbers in scalar registers: kept from the top of the loop they cost six vector registers)
+      const int     js = __builtin_amdgcn_readfirstlane(j), ks = __builtin_amdgcn_readfirstlane(k);
+      const int64_t prx = (int64_t)ks * g.ny + js, pry = (int64_t)ks * g.nx + i, prz = (int64_t)js * g.nx + i;
+      double *const sx = rg.send, *const sy = sx + 4 * nyz, *const sz = sy + 4 * nxz;
+      if ((rg.pack & 1) && i < 2) sx[i * nyz + prx] = r;
+      if ((rg.pack & 2) && i >= g.nx - 2) sx[(i - g.nx + 4) * nyz + prx] = r;
+      if ((rg.pack & 4) && j < 2) sy[j * nxz + pry] = r;
+      if ((rg.pack & 8) && j >= g.ny - 2) sy[(j - g.ny + 4) * nxz + pry] = r;
+      if ((rg.pack & 16) && k < 2) sz[k * nxy + prz] = r;
+      if ((rg.pack & 32) && k >= g.nz - 2) sz[(k - g.nz + 4) * nxy + prz] = r;
+    }
+  }
+}
+
+// The send layers of the caller's phi (the first stage of a step, fl_scalar_rhs), in the layout the fused pack writes: blockIdx.y = boundary, all six
+// in one launch (a boundary without a neighbouring rank returns at once).
+__global__ void __launch_bounds__(256) k_scalar_pack(int nx, int ny, int nz, int nb, const double *__restrict__ phi, double *__restrict__ send)
+{
+  const int b = blockIdx.y, d = b >> 1;
+  if (!((nb >> b) & 1)) return;
+  const int64_t nyz = (int64_t)ny * nz, nxz = (int64_t)nx * nz, nxy = (int64_t)nx * ny;
+  const int     n = d == 0 ? nx : (d == 1 ? ny : nz), a0 = (b & 1) ? n - 2 : 0;
+  const int64_t np = d == 0 ? nyz : (d == 1 ? nxz : nxy);
+  double       *out = send + (d == 0 ? 0 : (d == 1 ? 4 * nyz : 4 * (nyz + nxz))) + (b & 1 ? 2 * np : 0);
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < 2 * np; t += (int64_t)gridDim.x * blockDim.x) {
+    const int     a = a0 + (int)(t / np);
+    const int64_t pr = t % np;
+    int64_t       c;
+    if (d == 0) c = pr * nx + a;                                 // pr = k ny + j
+    else if (d == 1) c = ((pr / nx) * ny + a) * nx + pr % nx;   // pr = k nx + i
+    else c = (int64_t)a * nxy + pr;                              // pr = j nx + i
+    out[t] = phi[c];
   }
 }
 
@@ -206,6 +336,51 @@ __global__ void __launch_bounds__(256) k_scalar_cfl(int nx, int ny, int nz, int 
   }
 }
 
+// k_scalar_cfl on one rank's block of several (per: the periodic axes the rank holds alone; nb as in k_scalar_stage_ring): the face behind the last
+// cell of an axis the next rank owns is read from the hiface plane vhi[d]
+struct ScHiface {
+  const double *v[3];
+};
+__global__ void __launch_bounds__(256) k_scalar_cfl_ring(int nx, int ny, int nz, int per, int nb, ScHiface vhi, double dt, double gamma, const double *__restrict__ hx,
+                                                         const double *__restrict__ hy, const double *__restrict__ hz, const double *__restrict__ Vx, const double *__restrict__ Vy,
+                                                         const double *__restrict__ Vz, double *__restrict__ partial)
+{
+  __shared__ double red[8];
+  const int64_t     N = (int64_t)nx * ny * nz, nxy = (int64_t)nx * ny;
+  const bool        wx = per & 1, wy = per & 2, wz = per & 4, nhx = nb & 2, nhy = nb & 8, nhz = nb & 32;
+  const int         fx = (wx || nhx) ? nx : nx + 1, fy = (wy || nhy) ? ny : ny + 1;
+  double            ca = 0., cd = 0.;
+  for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < N; c += (int64_t)gridDim.x * 256) {
+    const int     i = (int)(c % nx);
+    const int64_t t = c / nx;
+    const int     j = (int)(t % ny), k = (int)(t / ny);
+    const int     ip = (i + 1 == nx && wx) ? 0 : i + 1, jp = (j + 1 == ny && wy) ? 0 : j + 1, kp = (k + 1 == nz && wz) ? 0 : k + 1;
+    const int64_t vxr = ((int64_t)k * ny + j) * fx, vyr = (int64_t)k * fy * nx + i;
+    const double  x1 = (nhx && i + 1 == nx) ? vhi.v[0][(int64_t)k * ny + j] : Vx[vxr + ip], y1 = (nhy && j + 1 == ny) ? vhi.v[1][(int64_t)k * nx + i] : Vy[vyr + (int64_t)jp * nx],
+                 z1 = (nhz && k + 1 == nz) ? vhi.v[2][(int64_t)j * nx + i] : Vz[(int64_t)kp * nxy + (int64_t)j * nx + i];
+    const double ax = fmax(fabs(Vx[vxr + i]), fabs(x1)), ay = fmax(fabs(Vy[vyr + (int64_t)j * nx]), fabs(y1)), az = fmax(fabs(Vz[c]), fabs(z1));
+    const double a = hx[i], b = hy[j], d = hz[k];
+    ca = fmax(ca, dt * (ax / a + ay / b + az / d));
+    cd = fmax(cd, gamma * dt * (2. / (a * a) + 2. / (b * b) + 2. / (d * d)));
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    ca = fmax(ca, __shfl_down(ca, o, 64));
+    cd = fmax(cd, __shfl_down(cd, o, 64));
+  }
+  if (lane == 0) {
+    red[wv]     = ca;
+    red[4 + wv] = cd;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partial[3 * blockIdx.x]     = 0.;
+    partial[3 * blockIdx.x + 1] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    partial[3 * blockIdx.x + 2] = fmax(fmax(red[4], red[5]), fmax(red[6], red[7]));
+  }
+}
+
 }  // namespace fl
 
 using namespace fl;
@@ -255,6 +430,11 @@ struct fl_scalar {
   double       *work[2] = {nullptr, nullptr};         // the two stage vectors of fl_scalar_step
   double       *partial = nullptr;                    // 3 * SC_REDUCE_BLOCKS
   std::vector<double> partial_host;
+  const double *hwl[3] = {nullptr, nullptr, nullptr};  // hw cut to the rank's cells
+  // one rank's block of several (fl_scalar_create_ranks): nb as k_scalar_stage_ring takes it; the layers received and sent (ScRing)
+  bool    ring = false;
+  int     nb = 0;
+  double *slab_recv = nullptr, *slab_send = nullptr;
 };
 
 constexpr int SC_REDUCE_BLOCKS = 1024;
@@ -295,12 +475,40 @@ struct StageArgs {
   double        c0, c1, c2;
   const double *phin, *w, *q;
   double       *out;
+  bool          pack;  // several ranks: the stage fills the send slabs for the stage after it
 };
+
+// a neighbouring rank behind boundary b whose cells arrive through the exchange (sv_ring_side of fl_schur_var.hip)
+bool sc_ring_side(const fl_poisson *h, int b) { return h->multi && h->nbr[b] >= 0 && !h->wrap_local[b / 2]; }
+
+ScRing ring_args(const fl_scalar *m, bool pack)
+{
+  ScRing rg;
+  rg.recv = m->slab_recv;
+  rg.send = m->slab_send;
+  rg.pack = pack ? m->nb : 0;
+  for (int d = 0; d < 3; ++d) rg.vhi[d] = (m->nb >> (2 * d + 1)) & 1 ? m->h->hiface[d] : nullptr;
+  return rg;
+}
+
+// where the two layers of boundary b start in slab_recv / slab_send
+size_t slab_offset(const fl_poisson *h, int b)
+{
+  size_t o = 0;
+  for (int d = 0; d < b / 2; ++d) o += 4 * (size_t)fl_plane_size(h, d);
+  return o + (b % 2 ? 2 * (size_t)fl_plane_size(h, b / 2) : 0);
+}
 
 template <int L>
 void launch_stage(const fl_scalar *m, const StageArgs &a)
 {
   const dim3 grid(8 * scalar_plan(m->g.nx, m->g.ny, m->g.nz, L).per_xcd);
+  if (m->ring) {
+    const ScRing rg = ring_args(m, a.pack);
+    if (a.phin) hipLaunchKernelGGL((k_scalar_stage_ring<L, true>), grid, dim3(256), 0, m->h->stream, m->g, rg, m->nb, a.c0, a.c1, a.c2, a.phin, a.w, m->V[0], m->V[1], m->V[2], a.q, a.out);
+    else hipLaunchKernelGGL((k_scalar_stage_ring<L, false>), grid, dim3(256), 0, m->h->stream, m->g, rg, m->nb, a.c0, a.c1, a.c2, a.phin, a.w, m->V[0], m->V[1], m->V[2], a.q, a.out);
+    return;
+  }
   if (a.phin) hipLaunchKernelGGL((k_scalar_stage<L, true>), grid, dim3(256), 0, m->h->stream, m->g, a.c0, a.c1, a.c2, a.phin, a.w, m->V[0], m->V[1], m->V[2], a.q, a.out);
   else hipLaunchKernelGGL((k_scalar_stage<L, false>), grid, dim3(256), 0, m->h->stream, m->g, a.c0, a.c1, a.c2, a.phin, a.w, m->V[0], m->V[1], m->V[2], a.q, a.out);
 }
@@ -318,7 +526,8 @@ int scalar_init(fl_scalar *m, fl_poisson *h, const int bc[6])
   g.nx = h->g.nx; g.ny = h->g.ny; g.nz = h->g.nz;
   for (int d = 0; d < 3; ++d) {
     const Axis &A = h->ax[d];
-    g.per |= A.periodic ? 1 << d : 0;
+    // (several ranks: the periodic axes this rank holds alone -- a periodic axis split over ranks is a rank face at both ends)
+    g.per |= (h->multi ? h->wrap_local[d] : A.periodic) ? 1 << d : 0;
     g.kind[2 * d] = bc[2 * d];
     g.kind[2 * d + 1] = bc[2 * d + 1];
     g.dlo[d] = A.xcc(0) - A.xf[0];
@@ -331,7 +540,10 @@ int scalar_init(fl_scalar *m, fl_poisson *h, const int bc[6])
     FL_HIP(hipMalloc((void **)&m->hw[d], sizeof(double) * hw.size()));
     FL_HIP(hipMemcpy(m->tab[d], rows.data(), sizeof(ScCell) * rows.size(), hipMemcpyHostToDevice));
     FL_HIP(hipMemcpy(m->hw[d], hw.data(), sizeof(double) * hw.size(), hipMemcpyHostToDevice));
-    g.c[d] = (const ScCell *)m->tab[d];
+    // h->ax[d] is the GLOBAL axis: the rank's rows are the one-rank rows of its cells, bit for bit (one rank: lo = 0)
+    const int64_t lo = h->multi ? h->dec.lo[d] : 0;
+    g.c[d]    = (const ScCell *)m->tab[d] + lo;
+    m->hwl[d] = m->hw[d] + lo;
   }
   FL_HIP(hipMalloc((void **)&m->partial, sizeof(double) * 3 * SC_REDUCE_BLOCKS));
   m->partial_host.resize((size_t)3 * SC_REDUCE_BLOCKS);
@@ -363,24 +575,111 @@ extern "C" int fl_scalar_destroy(fl_scalar *m)
   }
   for (double *p : {m->work[0], m->work[1], m->partial})
     if (p) (void)hipFree(p);
+  for (double *p : {m->slab_recv, m->slab_send})
+    if (p) (void)hipFree(p);
   delete m;
   return FL_SUCCESS;
 }
+
+namespace {
+
+// the checks of the boundary kinds both constructors make, against the GLOBAL axes
+int scalar_check_bc(const fl_poisson *h, const int bc[6])
+{
+  for (int b = 0; b < 6; ++b)
+    if (bc[b] < 0 || bc[b] > 2) return FL_ERR_ARG_OUTOFRANGE;
+  for (int d = 0; d < 3; ++d)
+    if ((bc[2 * d] == 2) != h->ax[d].periodic || (bc[2 * d + 1] == 2) != h->ax[d].periodic) return FL_ERR_ARG_WRONG;
+  return FL_SUCCESS;
+}
+
+int scalar_new(fl_poisson *h, const int bc[6], bool ring, fl_scalar **out)
+{
+  fl_scalar *m  = new fl_scalar();
+  int        rc = scalar_init(m, h, bc);
+  if (!rc && ring) {
+    for (int b = 0; b < 6; ++b) m->nb |= sc_ring_side(h, b) ? 1 << b : 0;
+    const size_t bytes = sizeof(double) * slab_offset(h, 6);
+    if (hipMalloc((void **)&m->slab_recv, bytes) != hipSuccess || hipMalloc((void **)&m->slab_send, bytes) != hipSuccess) rc = FL_ERR_GPU;
+  }
+  m->ring = ring;
+  if (rc) {
+    fl_scalar_destroy(m);
+    return rc;
+  }
+  *out = m;
+  return FL_SUCCESS;
+}
+
+// Several ranks: the phi slabs of the stage about to run, from the send layers (filled by k_scalar_pack or by the stage before) into the peers' receive
+// slabs.  ONE pair of slabs per boundary is enough: the transports are stream-ordered on either side (RCCL's Send / Recv; the host-staged callbacks
+// copy out of the send slab and into the receive slab on the handle's stream), so the receive of stage k + 1 is posted in stream order AFTER the
+// kernel that read stage k's slab, and the kernel that overwrites a send slab after the exchange that shipped it.
+int ring_exchange(fl_scalar *m)
+{
+  fl_poisson *h = m->h;
+  fl_halo_msg plan[12];
+  const int   np = fl_halo_messages(h, false, plan);
+  std::vector<Msg> msgs;
+  for (int a = 0; a < np; ++a) {
+    const int sb = plan[a].send_boundary, rb = plan[a].recv_boundary;
+    if (!((m->nb >> sb) & 1) || !((m->nb >> rb) & 1)) return FL_ERR_ARG_WRONGSTATE;
+    msgs.push_back({plan[a].peer, m->slab_send + slab_offset(h, sb), m->slab_recv + slab_offset(h, rb), 2 * (int64_t)fl_plane_size(h, sb / 2), plan[a].sendtag + 256,
+                    plan[a].recvtag + 256});
+  }
+  return h->comm.exchange(h->stream, msgs);
+}
+
+// the send slabs of the caller's phi, then the exchange
+int ring_pack_exchange(fl_scalar *m, const double *phi)
+{
+  size_t most = 0;
+  for (int b = 0; b < 6; ++b)
+    if ((m->nb >> b) & 1) most = std::max(most, 2 * (size_t)fl_plane_size(m->h, b / 2));
+  if (most) hipLaunchKernelGGL(k_scalar_pack, dim3((unsigned)std::min<size_t>((most + 255) / 256, 1024), 6), dim3(256), 0, m->h->stream, m->g.nx, m->g.ny, m->g.nz, m->nb, phi, m->slab_send);
+  FL_HIP(hipGetLastError());
+  return ring_exchange(m);
+}
+
+// what every collective call starts with: the velocity of the faces the next rank owns.  With the call, not with fl_scalar_set_velocity: the
+// handle's hiface planes are shared with fl_poisson_rhs, and a plane refreshed with the call is never stale.
+int ring_velocity(fl_scalar *m) { return m->ring ? fl_fill_hifaces(m->h, m->V) : 0; }
+
+}  // namespace
 
 extern "C" int fl_scalar_create(fl_poisson *grid_from, const int bc[6], fl_scalar **out)
 {
   if (!grid_from || !bc || !out) return FL_ERR_ARG_NULL;
   *out = nullptr;
+  FL_CHK(scalar_check_bc(grid_from, bc));
+  if (grid_from->multi) return FL_ERR_SUP;  // one rank's block of several: fl_scalar_create_ranks (collective)
+  return scalar_new(grid_from, bc, false, out);
+}
+
+extern "C" int fl_scalar_create_ranks(fl_poisson *grid_from, const int bc[6], fl_scalar **out)
+{
+  if (!grid_from || !bc || !out) return FL_ERR_ARG_NULL;
+  if (!grid_from->multi) return fl_scalar_create(grid_from, bc, out);
+  *out = nullptr;
+  fl_poisson *h = grid_from;
+  FL_CHK(scalar_check_bc(h, bc));
+  if (h->loopback) return FL_ERR_SUP;
+  if (h->comm.kind == Comm::NONE) return FL_ERR_ARG_WRONGSTATE;
+  // Voted, so that every rank returns an error and none holds a handle its peers would wait for: 2 = a block with one cell along a split axis (the
+  // neighbour's second layer would not be its own cell), 1 = this rank could not build its handle (tables, slabs: made BEFORE the vote)
+  const int n[3] = {h->g.nx, h->g.ny, h->g.nz};
+  bool      thin = false;
   for (int b = 0; b < 6; ++b)
-    if (bc[b] < 0 || bc[b] > 2) return FL_ERR_ARG_OUTOFRANGE;
-  for (int d = 0; d < 3; ++d)
-    if ((bc[2 * d] == 2) != grid_from->ax[d].periodic || (bc[2 * d + 1] == 2) != grid_from->ax[d].periodic) return FL_ERR_ARG_WRONG;
-  if (grid_from->multi) return FL_ERR_SUP;  // several ranks: a two-deep ghost of phi and a ring of V (as k_schur_var_ring has) are not built
-  fl_scalar *m  = new fl_scalar();
-  const int  rc = scalar_init(m, grid_from, bc);
-  if (rc) {
+    if (sc_ring_side(h, b) && n[b / 2] < 2) thin = true;
+  FL_HIP(hipSetDevice(h->device));
+  fl_scalar *m    = nullptr;
+  const int  rc   = thin ? FL_SUCCESS : scalar_new(h, bc, true, &m);
+  double     vote = thin ? 2. : (rc ? 1. : 0.);
+  const int  vrc  = fl_allreduce_max(h, &vote);
+  if (vrc || vote != 0.) {
     fl_scalar_destroy(m);
-    return rc;
+    if (vrc) return vrc;
+    return vote == 2. ? FL_ERR_ARG_OUTOFRANGE : (rc ? rc : FL_ERR_GPU);
   }
   *out = m;
   return FL_SUCCESS;
@@ -425,7 +724,28 @@ extern "C" int fl_scalar_rhs(fl_scalar *m, const double *phi_dev, const double *
   if (phi_dev == out_dev) return FL_ERR_ARG_WRONG;  // neighbours still read phi
   if (!m->V[0]) return FL_ERR_ARG_WRONGSTATE;
   FL_HIP(hipSetDevice(m->h->device));
-  STAGE[m->limiter](m, StageArgs{0., 0., 1., nullptr, phi_dev, source_dev, out_dev});
+  if (m->ring) {
+    FL_CHK(ring_velocity(m));
+    FL_CHK(ring_pack_exchange(m, phi_dev));
+  }
+  STAGE[m->limiter](m, StageArgs{0., 0., 1., nullptr, phi_dev, source_dev, out_dev, false});
+  FL_HIP(hipGetLastError());
+  return FL_SUCCESS;
+}
+
+// Not part of the public C-ABI (tools/scalar_bench.py --ring): the launch of fl_scalar_rhs ALONE on a handle of fl_scalar_create_ranks -- no exchange, the
+// slabs and the hiface planes as the last collective call left them -- so that one rank can time k_scalar_stage_ring while its peers idle.  pack != 0:
+// the stage also fills the send slabs, as every stage of a step but the last does.
+extern "C" int fldbg_scalar_stage_only(fl_scalar *m, const double *phi_dev, const double *source_dev, double *out_dev, int pack)
+{
+  if (!m || !phi_dev || !out_dev) return FL_ERR_ARG_NULL;
+  if (phi_dev == out_dev) return FL_ERR_ARG_WRONG;
+  if (!m->V[0]) return FL_ERR_ARG_WRONGSTATE;
+  if (m->ring)
+    for (int d = 0; d < 3; ++d)
+      if (((m->nb >> (2 * d + 1)) & 1) && !m->h->hiface[d]) return FL_ERR_ARG_WRONGSTATE;  // (no collective call yet)
+  FL_HIP(hipSetDevice(m->h->device));
+  STAGE[m->limiter](m, StageArgs{0., 0., 1., nullptr, phi_dev, source_dev, out_dev, m->ring && pack != 0});
   FL_HIP(hipGetLastError());
   return FL_SUCCESS;
 }
@@ -442,12 +762,18 @@ extern "C" int fl_scalar_step(fl_scalar *m, double dt, int nstages, const double
     if (!m->work[a]) FL_HIP(hipMalloc((void **)&m->work[a], sizeof(double) * (size_t)m->h->ncell));
   const int     s = nstages;
   const double *w = phi_dev;
+  // several ranks: V is frozen during the step (one exchange of its high faces); phi's slabs are packed by a kernel once, then by the stages
+  if (m->ring) {
+    FL_CHK(ring_velocity(m));
+    FL_CHK(ring_pack_exchange(m, phi_dev));
+  }
   for (int st = 0; st < s - 1; ++st) {
     double *o = m->work[st & 1];
-    STAGE[m->limiter](m, StageArgs{0., 1., dt / (s - 1), nullptr, w, source_dev, o});
+    STAGE[m->limiter](m, StageArgs{0., 1., dt / (s - 1), nullptr, w, source_dev, o, m->ring});
+    if (m->ring) FL_CHK(ring_exchange(m));
     w = o;
   }
-  STAGE[m->limiter](m, StageArgs{1. / s, (s - 1.) / s, dt / s, phi_dev, w, source_dev, phi_dev});
+  STAGE[m->limiter](m, StageArgs{1. / s, (s - 1.) / s, dt / s, phi_dev, w, source_dev, phi_dev, false});
   FL_HIP(hipGetLastError());
   return FL_SUCCESS;
 }
@@ -458,13 +784,24 @@ extern "C" int fl_scalar_cfl(fl_scalar *m, double dt, double out[2])
   if (!m->V[0]) return FL_ERR_ARG_WRONGSTATE;
   FL_HIP(hipSetDevice(m->h->device));
   const int nb = reduce_blocks(m);
-  hipLaunchKernelGGL(k_scalar_cfl, dim3(nb), dim3(256), 0, m->h->stream, m->g.nx, m->g.ny, m->g.nz, m->g.per, dt, m->g.gamma, m->hw[0], m->hw[1], m->hw[2], m->V[0], m->V[1], m->V[2],
-                     m->partial);
+  if (m->ring) {
+    FL_CHK(ring_velocity(m));
+    ScHiface vh;
+    for (int d = 0; d < 3; ++d) vh.v[d] = (m->nb >> (2 * d + 1)) & 1 ? m->h->hiface[d] : nullptr;
+    hipLaunchKernelGGL(k_scalar_cfl_ring, dim3(nb), dim3(256), 0, m->h->stream, m->g.nx, m->g.ny, m->g.nz, m->g.per, m->nb, vh, dt, m->g.gamma, m->hwl[0], m->hwl[1], m->hwl[2], m->V[0],
+                       m->V[1], m->V[2], m->partial);
+  } else
+    hipLaunchKernelGGL(k_scalar_cfl, dim3(nb), dim3(256), 0, m->h->stream, m->g.nx, m->g.ny, m->g.nz, m->g.per, dt, m->g.gamma, m->hwl[0], m->hwl[1], m->hwl[2], m->V[0], m->V[1], m->V[2],
+                       m->partial);
   FL_CHK(fetch_partials(m, nb));
   out[0] = out[1] = 0.;
   for (int b = 0; b < nb; ++b) {
     out[0] = std::max(out[0], m->partial_host[(size_t)3 * b + 1]);
     out[1] = std::max(out[1], m->partial_host[(size_t)3 * b + 2]);
+  }
+  if (m->ring) {  // a maximum is the same number in any order: the same bits on every rank and every rank grid
+    FL_CHK(fl_allreduce_max(m->h, &out[0]));
+    FL_CHK(fl_allreduce_max(m->h, &out[1]));
   }
   return FL_SUCCESS;
 }
@@ -474,7 +811,7 @@ extern "C" int fl_scalar_stats(fl_scalar *m, const double *phi_dev, double out[3
   if (!m || !phi_dev || !out) return FL_ERR_ARG_NULL;
   FL_HIP(hipSetDevice(m->h->device));
   const int nb = reduce_blocks(m);
-  hipLaunchKernelGGL(k_scalar_stats, dim3(nb), dim3(256), 0, m->h->stream, m->g.nx, m->g.ny, m->g.nz, m->hw[0], m->hw[1], m->hw[2], phi_dev, m->partial);
+  hipLaunchKernelGGL(k_scalar_stats, dim3(nb), dim3(256), 0, m->h->stream, m->g.nx, m->g.ny, m->g.nz, m->hwl[0], m->hwl[1], m->hwl[2], phi_dev, m->partial);
   FL_CHK(fetch_partials(m, nb));
   out[0] = m->partial_host[0];
   out[1] = m->partial_host[1];
@@ -483,6 +820,13 @@ extern "C" int fl_scalar_stats(fl_scalar *m, const double *phi_dev, double out[3
     out[0] = std::min(out[0], m->partial_host[(size_t)3 * b]);
     out[1] = std::max(out[1], m->partial_host[(size_t)3 * b + 1]);
     out[2] += m->partial_host[(size_t)3 * b + 2];
+  }
+  if (m->ring) {  // min as the negated maximum; the sum: the ranks' block-ordered sums added in the all-reduce's fixed order
+    double neg = -out[0];
+    FL_CHK(fl_allreduce_max(m->h, &neg));
+    out[0] = -neg;
+    FL_CHK(fl_allreduce_max(m->h, &out[1]));
+    FL_CHK(fl_allreduce_sum(m->h, &out[2]));
   }
   return FL_SUCCESS;
 }

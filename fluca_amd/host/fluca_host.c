@@ -1332,7 +1332,7 @@ static FlErrorCode scalar_get(NS ns, int id, struct NSScalar **sc)
 static FlErrorCode scalar_ensure(NS ns, struct NSScalar *sc)
 {
   if (!sc->h) {
-    FLABI(fl_scalar_create(ns->poisson, sc->kind, &sc->h));
+    FLABI(fl_scalar_create_ranks(ns->poisson, sc->kind, &sc->h)); /* collective on a several-rank mesh; one rank: fl_scalar_create */
     FLABI(fl_scalar_set_limiter(sc->h, sc->limiter));
     FLABI(fl_scalar_set_diffusivity(sc->h, sc->gamma));
     for (int b = 0; b < 6; ++b) FLABI(fl_scalar_set_boundary_value(sc->h, b, sc->val[b]));
@@ -1355,7 +1355,6 @@ FlErrorCode NSAddScalar(NS ns, const char *name, double gamma, const char *limit
 {
   if (!ns || !name || !id) return E_ARG_NULL;
   if (!ns->setupcalled) return E_ARG_WRONGSTATE;
-  if (ns->mesh->size > 1) return E_SUP; /* several ranks: fl_scalar_create */
   if (!(gamma >= 0.) || gamma > 1.7976931348623157e308 || strlen(name) > 31 || ns->nscalar >= MAXNSSCALARS) return E_ARG_OUTOFRANGE;
   int limiter = ns->scalar_limiter;
   if (limiter_name && fl_limiter_from_name(limiter_name, &limiter)) return E_ARG_UNKNOWN_TYPE;

@@ -1,6 +1,8 @@
 """Passive scalar transport on top of the C-ABI (fl_scalar_*, include/fluca_hip.h): the right-hand side of the reference's transport
 equation -- second-order TVD convection with its eleven limiters, two-point diffusion, a source -- and the s-stage second-order SSP
-Runge-Kutta step of its tutorials (-ts_type ssp), one kernel launch per stage.  One rank only.
+Runge-Kutta step of its tutorials (-ts_type ssp), one kernel launch per stage.  On a Poisson handle that is one rank's block of several
+(fl_scalar_create_ranks) the arrays are that block, construction and rhs / step / cfl / stats are collective, and two layers of phi cross
+every rank face once per stage.
 """
 import ctypes as C
 import weakref
@@ -35,7 +37,11 @@ class Scalar:
         self.P = poisson
         self.bc = tuple(int(b) for b in bc)
         h = C.c_void_p()
-        check(lib.fl_scalar_create(poisson.h, (C.c_int * 6)(*self.bc), C.byref(h)), "fl_scalar_create")
+        # one rank's block of several: the collective constructor
+        d = poisson.decomp
+        several = d is not None and d.ranks[0] * d.ranks[1] * d.ranks[2] > 1
+        create, name = (lib.fl_scalar_create_ranks, "fl_scalar_create_ranks") if several else (lib.fl_scalar_create, "fl_scalar_create")
+        check(create(poisson.h, (C.c_int * 6)(*self.bc), C.byref(h)), name)
         self.h = h
         poisson._children.append(weakref.ref(self))
         self._V = None

@@ -534,7 +534,8 @@ int fl_ibm_force(fl_ibm *m, const double *F_dev, const double *dV_dev, const int
  * boundary face is (phi_0 - phi_b) / (xc_0 - xf_0) (Dirichlet; mirrored at the high end) or the value (Neumann); the face VALUE there is the
  * boundary's own for either flow direction: phi_b, or phi_near -/+ (distance centre -- face) g.  For inflow that is what FlucaFD's ghost
  * elimination gives; for outflow the reference reads a ghost cell it never fills, which this library does not restate.
- * One rank only: a handle on a decomposed grid is FL_ERR_SUP (several ranks need a two-deep ghost of phi and a ring of V: not built yet). */
+ * Several ranks: fl_scalar_create_ranks below; the arrays are then the rank's block -- cells in DMStag ownership, faces in the layout of
+ * fl_poisson_rhs -- and rhs / step / cfl / stats are collective. */
 typedef struct fl_scalar fl_scalar;
 /* the reference's limiter names (-flucafd_limiter); host only.  Unknown name: FL_ERR_ARG_OUTOFRANGE */
 int fl_limiter_from_name(const char *name, int *limiter);
@@ -543,6 +544,14 @@ int fl_limiter_eval(int limiter, double r, double *psi);
 /* grid_from is borrowed (grid, device, stream) and must outlive the handle.  Defaults: all boundary values 0, superbee, Gamma = 0.
  * FL_ERR_ARG_OUTOFRANGE: a kind outside 0..2; FL_ERR_ARG_WRONG: periodic flags that disagree with the grid; FL_ERR_SUP: more than one rank */
 int fl_scalar_create(fl_poisson *grid_from, const int bc[6], fl_scalar **out);
+/* The handle of one rank's block of several (as fl_ibm_create_owned stands beside fl_ibm_create); on a one-rank grid_from it IS fl_scalar_create.
+ * Collective on a decomposed grid_from, and so are fl_scalar_rhs / _step / _cfl / _stats on the handle it makes: two layers of phi cross every
+ * rank face once per stage (2 planes x 8 B per face), the velocity of the faces the next rank owns once per call.  bc and the periodic flags are
+ * checked as by fl_scalar_create, against the GLOBAL axes; a kind or value at an end behind which a rank sits is accepted and unused.
+ * FL_ERR_ARG_WRONGSTATE: no transport attached (fl_poisson_comm_init*); FL_ERR_SUP: loopback mode; FL_ERR_ARG_OUTOFRANGE: some rank's block has fewer
+ * than 2 cells along an axis with a neighbouring rank (voted: every rank returns it, none holds a handle).  A rank that cannot allocate its
+ * tables or slabs takes part in the same vote: it returns its own error, its peers FL_ERR_GPU, and none holds a handle. */
+int fl_scalar_create_ranks(fl_poisson *grid_from, const int bc[6], fl_scalar **out);
 int fl_scalar_destroy(fl_scalar *m); /* NULL is success */
 int fl_scalar_set_boundary_value(fl_scalar *m, int boundary, double value);
 int fl_scalar_set_limiter(fl_scalar *m, int limiter); /* default superbee, as the reference */
@@ -555,9 +564,12 @@ int fl_scalar_rhs(fl_scalar *m, const double *phi_dev, const double *source_dev,
  *   w = phi; s-1 times w += dt/(s-1) R(w); phi = ((s-1) w + phi + dt R(w)) / s.     nstages = s >= 2 (the reference's default: 5).
  * One kernel launch per stage, 40 B/cell each (48 the last). */
 int fl_scalar_step(fl_scalar *m, double dt, int nstages, const double *source_dev, double *phi_dev);
-/* out[0] = max_c dt sum_d max(|V(f-)|, |V(f+)|) / h_d ; out[1] = max_c Gamma dt sum_d 2 / h_d^2.  Waits for the stream */
+/* out[0] = max_c dt sum_d max(|V(f-)|, |V(f+)|) / h_d ; out[1] = max_c Gamma dt sum_d 2 / h_d^2.  Waits for the stream.  Several ranks: the maxima
+ * over all ranks, the same bits on every rank and on every rank grid */
 int fl_scalar_cfl(fl_scalar *m, double dt, double out[2]);
-/* out = { min phi, max phi, sum_c phi(c) vol(c) }, the sum in a fixed order (the same bits on every call).  Waits for the stream */
+/* out = { min phi, max phi, sum_c phi(c) vol(c) }, the sum in a fixed order (the same bits on every call).  Waits for the stream.  Several ranks: over
+ * all ranks; the sum is each rank's block-ordered sum added over the ranks -- the same bits on every call and on every rank, NOT the same bits
+ * across rank grids (another split sums in another order) */
 int fl_scalar_stats(fl_scalar *m, const double *phi_dev, double out[3]);
 
 #ifdef __cplusplus

@@ -261,7 +261,8 @@ FlErrorCode NSMonitorImmersedBoundaryForce(NS ns, void *ctx);
  * reference's FlucaFDSecondOrderTVD right-hand side, advanced as its tutorials do (-ts_type ssp: the s-stage second-order SSP Runge-Kutta method).
  * After the flow step has produced V^(n+1), NSStep advances every scalar over dt with THAT V, in n equal substeps (NSSetScalarSubsteps, default 1):
  * the velocity is frozen over the step, so the coupling of scalar and flow is first order in time.  With no scalar registered NSStep launches
- * nothing new.  After NSSetUp; one rank only (PETSC_ERR_SUP on a decomposed mesh).  At most 8 scalars.
+ * nothing new and exchanges nothing.  After NSSetUp.  On a several-rank mesh the arrays are the rank's block (cells in DMStag ownership), the first
+ * use of a scalar (NSStep, NSGetScalarCFL) and NSGetScalarCFL are collective (fl_scalar_create_ranks).  At most 8 scalars.
  *   NSAddScalar       name (<= 31 characters), Gamma >= 0, the limiter's name as the reference spells it (NULL: -ns_scalar_limiter, default superbee);
  *                     the field starts at 0 (write the initial condition through NSGetScalarArray); *id = 0, 1, ...
  *   boundary          index as NSSetBoundaryCondition's; type 0 Dirichlet, 1 Neumann (the derivative along the +AXIS), 2 periodic (exactly on the

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libflucahip.so")
-SOURCES = ["fl_coeff.cpp", "fl_kernels.hip", "fl_api.hip", "fl_knobs.cpp", "fl_place.hip", "fl_halo.hip", "fl_comm.hip", "fl_ksp.hip", "fl_cheb2.hip", "fl_layout.hip", "fl_ibm.hip", "fl_momentum.hip", "fl_mg.hip", "fl_schur_var.hip", "fl_scalar.hip"]
+SOURCES = ["fl_coeff.cpp", "fl_kernels.hip", "fl_api.hip", "fl_knobs.cpp", "fl_place.hip", "fl_halo.hip", "fl_comm.hip", "fl_ksp.hip", "fl_cheb2.hip", "fl_layout.hip", "fl_ibm.hip", "fl_momentum.hip", "fl_mg.hip", "fl_schur_var.hip", "fl_scalar.hip", "fl_buoyancy.hip"]
 HEADERS = ["fl_internal.h", "fl_knobs.h", "fl_handle.h", "fl_device.h", "fl_stencil.h", "fl_mom_tile.h", "fl_mom_tile3.h", "fl_limiter.h", os.path.join("..", "..", "include", "fluca_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
@@ -151,6 +151,7 @@ def build_host(force=False, verbose=False):
     build_example(force, verbose)
     build_example(force, verbose, name="cavity_flow_3d")
     build_example(force, verbose, name="flow_configs")
+    build_example(force, verbose, name="heated_cavity_3d")
     return HOST_LIB
 
 

@@ -156,6 +156,7 @@ PROTOTYPES = {
     "fl_momentum_face_interp_scaled": (C.c_int, [_P, C.c_double, _P, _P, _P]),
     "fl_boundary_add_cells": (C.c_int, [_P, C.c_int, C.c_double, _P, _P]),
     "fl_momentum_rhs": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P]),
+    "fl_momentum_add_buoyancy": (C.c_int, [_P, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, _P]),
     "fl_momentum_interp_faces": (C.c_int, [_P, _P, _P, _P]),
     "fl_momentum_interp_faces_ends": (C.c_int, [_P, _P, _P, _P]),
     "fl_abf_jacobian_mult": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
@@ -185,6 +186,7 @@ PROTOTYPES = {
     "fl_scalar_step": (C.c_int, [_P, C.c_double, C.c_int, _P, _P]),
     "fl_scalar_cfl": (C.c_int, [_P, C.c_double, C.POINTER(C.c_double)]),
     "fl_scalar_stats": (C.c_int, [_P, _P, C.POINTER(C.c_double)]),
+    "fl_scalar_boundary_flux": (C.c_int, [_P, _P, C.POINTER(C.c_double)]),
 }
 for _name, (_res, _args) in PROTOTYPES.items():
     _f = getattr(lib, _name)  # AttributeError if the library lacks a declared symbol

@@ -48,6 +48,16 @@ void  launch_cg_Bq(hipStream_t, const GridP &, bool, const PlanA &, int xu, bool
                    int nhist, double *sums = nullptr);
 void  launch_stream_ref(hipStream_t, int, int, int64_t, const double *, const double *, const double *, double *, double *, double *);
 void  launch_stream_par(hipStream_t, int, int, int, int, int, int64_t, const double *, const double *, const double *, double *, double *, double *);
+// fl_buoyancy.hip: the Boussinesq term of momrhs.  The table travels as kernel arguments: phi[s] the scalars, a[d][s] the acceleration per unit of
+// scalar s along axis d, ref[s] the references
+constexpr int BUOY_MAXS = 8, BUOY_THREADS = 512;
+struct BuoyArgs {
+  const double *phi[BUOY_MAXS];
+  double        a[3][BUOY_MAXS], ref[BUOY_MAXS];
+};
+int  buoyancy_blocks(int64_t ncell, int ncu);
+int  device_cus(int device);  // compute units of the device (asked once per device), 0 if the runtime does not say
+void launch_buoyancy(hipStream_t, int nblocks, int64_t ncell, int ns, int act, const BuoyArgs &, double dt, double *momrhs);
 
 // ------------------------------------------------------------------------------------------------ transports (fl_comm.hip)
 

@@ -381,6 +381,73 @@ __global__ void __launch_bounds__(256) k_scalar_cfl_ring(int nx, int ny, int nz,
   }
 }
 
+// The fluxes through the physical boundaries of the block, all (at most six) planes in one launch: the blocks first[b] .. first[b + 1] - 1 work on
+// boundary b (none where the end is periodic or a neighbouring rank sits behind it), one lane per face, grid-stride within the boundary's blocks.
+// partial[3 B + 1], [3 B + 2]: block B's sums of V phi_f A and of -Gamma g A, with phi_f and g of the boundary rule exactly as sc_axis forms them
+// at the cells 0 and n - 1.  The x planes read V and phi with a stride of a row: a plane, not a field -- the kernel is latency-sized.
+struct ScFluxPlan {
+  int first[7];
+};
+__global__ void __launch_bounds__(256) k_scalar_flux(ScGrid g, ScFluxPlan pl, int fx, int fy, const double *__restrict__ hx, const double *__restrict__ hy, const double *__restrict__ hz,
+                                                     const double *__restrict__ phi, const double *__restrict__ Vx, const double *__restrict__ Vy, const double *__restrict__ Vz,
+                                                     double *__restrict__ partial)
+{
+  __shared__ double red[8];
+  int               b = 0;
+  while (b < 5 && (int)blockIdx.x >= pl.first[b + 1]) ++b;
+  const int     d = b >> 1, side = b & 1, lb = blockIdx.x - pl.first[b], nlb = pl.first[b + 1] - pl.first[b];
+  const int64_t nxy = (int64_t)g.nx * g.ny;
+  const int     n = d == 0 ? g.nx : (d == 1 ? g.ny : g.nz), a = side ? n - 1 : 0, f = side ? n : 0;
+  const int64_t np = d == 0 ? (int64_t)g.ny * g.nz : (d == 1 ? (int64_t)g.nx * g.nz : nxy);
+  const ScCell  T = g.c[d][a];
+  const int     kind = g.kind[b];
+  const double  val = g.val[b], dist = side ? g.dhi[d] : g.dlo[d];
+  double        sc = 0., sd = 0.;
+  for (int64_t t = (int64_t)lb * 256 + threadIdx.x; t < np; t += (int64_t)nlb * 256) {
+    int64_t c, v;
+    double  A;
+    const double *V;
+    if (d == 0) {  // t = k ny + j
+      c = t * g.nx + a, v = t * fx + f, V = Vx;
+      A = hy[t % g.ny] * hz[t / g.ny];
+    } else if (d == 1) {  // t = k nx + i
+      const int64_t k = t / g.nx, i = t % g.nx;
+      c = (k * g.ny + a) * g.nx + i, v = (k * fy + f) * g.nx + i, V = Vy;
+      A = hx[i] * hz[k];
+    } else {  // t = j nx + i
+      c = (int64_t)a * nxy + t, v = (int64_t)f * nxy + t, V = Vz;
+      A = hx[t % g.nx] * hy[t / g.nx];
+    }
+    const double P = phi[c];
+    double       F, G;
+    if (kind == 0) {
+      F = val;
+      G = side ? (val - P) * T.ic2 : (P - val) * T.ic1;
+    } else {
+      F = side ? P + dist * val : P - dist * val;
+      G = val;
+    }
+    sc += (V[v] * F) * A;
+    sd -= (g.gamma * G) * A;
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    sc += __shfl_down(sc, o, 64);
+    sd += __shfl_down(sd, o, 64);
+  }
+  if (lane == 0) {
+    red[wv]     = sc;
+    red[4 + wv] = sd;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partial[3 * blockIdx.x]     = 0.;
+    partial[3 * blockIdx.x + 1] = (red[0] + red[1]) + (red[2] + red[3]);
+    partial[3 * blockIdx.x + 2] = (red[4] + red[5]) + (red[6] + red[7]);
+  }
+}
+
 }  // namespace fl
 
 using namespace fl;
@@ -827,6 +894,45 @@ extern "C" int fl_scalar_stats(fl_scalar *m, const double *phi_dev, double out[3
     out[0] = -neg;
     FL_CHK(fl_allreduce_max(m->h, &out[1]));
     FL_CHK(fl_allreduce_sum(m->h, &out[2]));
+  }
+  return FL_SUCCESS;
+}
+
+// One launch over the boundary planes, at most SC_FLUX_BLOCKS blocks per boundary (their partial sums share the handle's slab with the other
+// reductions), the blocks of a boundary added in block order on the host.
+constexpr int SC_FLUX_BLOCKS = 64;
+extern "C" int fl_scalar_boundary_flux(fl_scalar *m, const double *phi_dev, double out[12])
+{
+  if (!m || !phi_dev || !out) return FL_ERR_ARG_NULL;
+  if (!m->V[0]) return FL_ERR_ARG_WRONGSTATE;
+  static_assert(6 * SC_FLUX_BLOCKS <= SC_REDUCE_BLOCKS, "the partial sums of six boundaries fit the slab");
+  FL_HIP(hipSetDevice(m->h->device));
+  const ScGrid &g = m->g;
+  ScFluxPlan    pl;
+  pl.first[0] = 0;
+  for (int b = 0; b < 6; ++b) {
+    // a physical boundary of THIS block: not periodic, and no neighbouring rank behind it
+    const bool    physical = g.kind[b] != 2 && !((m->nb >> b) & 1);
+    const int64_t np = fl_plane_size(m->h, b / 2);
+    pl.first[b + 1] = pl.first[b] + (physical ? (int)std::min<int64_t>((np + 255) / 256, SC_FLUX_BLOCKS) : 0);
+  }
+  for (int a = 0; a < 12; ++a) out[a] = 0.;
+  const int nblk = pl.first[6];
+  if (nblk) {
+    const bool hx = (m->nb >> 1) & 1, hy = (m->nb >> 3) & 1;
+    const int  fx = ((g.per & 1) || hx) ? g.nx : g.nx + 1, fy = ((g.per & 2) || hy) ? g.ny : g.ny + 1;
+    hipLaunchKernelGGL(k_scalar_flux, dim3(nblk), dim3(256), 0, m->h->stream, g, pl, fx, fy, m->hwl[0], m->hwl[1], m->hwl[2], phi_dev, m->V[0], m->V[1], m->V[2], m->partial);
+    FL_CHK(fetch_partials(m, nblk));
+    for (int b = 0; b < 6; ++b)
+      for (int k = pl.first[b]; k < pl.first[b + 1]; ++k) {
+        out[2 * b] += m->partial_host[(size_t)3 * k + 1];
+        out[2 * b + 1] += m->partial_host[(size_t)3 * k + 2];
+      }
+  } else
+    FL_HIP(hipStreamSynchronize(m->h->stream));
+  if (m->ring) {  // (the all-reduce carries eight numbers at a time)
+    FL_CHK(fl_poisson_allreduce_sum(m->h, out, 8));
+    FL_CHK(fl_poisson_allreduce_sum(m->h, out + 8, 4));
   }
   return FL_SUCCESS;
 }

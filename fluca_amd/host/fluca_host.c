@@ -884,6 +884,18 @@ FlErrorCode NSSetFromOptions(NS ns, int argc, char **argv)
     if (iv < 2 || iv > 1000) return E_ARG_OUTOFRANGE;
     ns->scalar_stages = (int)iv;
   }
+  /* mirror only: gravity of the Boussinesq term (NSSetGravity), three numbers separated by commas */
+  if ((s = opt_find(argc, argv, "-ns_gravity"))) {
+    double g[3];
+    int    k = 0;
+    for (const char *q = s; k < 3; ++k) {
+      char *end;
+      g[k] = strtod(q, &end);
+      if (end == q || *end != (k < 2 ? ',' : '\0')) return E_ARG_WRONG;
+      q = end + 1;
+    }
+    FLCHK(NSSetGravity(ns, g));
+  }
   /* mirror only: force and torque on the immersed bodies, one line per step and body (NSMonitorImmersedBoundaryForce) */
   if ((s = opt_find(argc, argv, "-ns_ibm_force_monitor"))) {
     char *name = strdup(s);
@@ -1083,6 +1095,7 @@ static FlErrorCode NSSetUp_Body(NS ns) /* nsbasic.c:153-274, restricted to what 
 
 static FlErrorCode ibm_move(NS ns);
 static FlErrorCode scalars_step(NS ns);
+static int         buoyancy_active(NS ns);
 
 static FlErrorCode NSStep_Body(NS ns) /* nsbasic.c:276-299 */
 {
@@ -1141,6 +1154,12 @@ static FlErrorCode NSView_Body(NS ns, FlucaViewer viewer) /* nsbasic.c:353-374 *
   FLCHK(FlucaViewerASCIIPrintf(viewer, "Current time step: %d, Current time: %g\n", (int)ns->step, ns->t));
   FLCHK(FlucaViewerASCIIPushTab(viewer));
   const FlErrorCode rc = ns->ops->view ? ns->ops->view(ns, viewer) : 0; /* PetscTryTypeMethod */
+  if (!rc && buoyancy_active(ns)) { /* mirror only, and only while the term is there: the output without it is the reference's */
+    FLCHK(FlucaViewerASCIIPrintf(viewer, "Gravity: (%g, %g, %g)\n", ns->gravity[0], ns->gravity[1], ns->gravity[2]));
+    for (int a = 0; a < ns->nscalar; ++a)
+      if (ns->scalars[a].beta != 0.)
+        FLCHK(FlucaViewerASCIIPrintf(viewer, "Buoyant scalar %s: beta %g, reference %g\n", ns->scalars[a].name, ns->scalars[a].beta, ns->scalars[a].phi_ref));
+  }
   FLCHK(FlucaViewerASCIIPopTab(viewer));
   return rc;
 }
@@ -1426,6 +1445,66 @@ FlErrorCode NSGetScalarCFL(NS ns, int id, double out[2])
   FLCHK(scalar_get(ns, id, &sc));
   FLCHK(scalar_ensure(ns, sc));
   FLABI(fl_scalar_cfl(sc->h, ns->dt / sc->substeps, out));
+  return 0;
+}
+FlErrorCode NSGetScalarBoundaryFlux(NS ns, int id, double out[12])
+{
+  struct NSScalar *sc = NULL;
+  if (!out) return E_ARG_NULL;
+  FLCHK(scalar_get(ns, id, &sc));
+  FLCHK(scalar_ensure(ns, sc));
+  FLABI(fl_scalar_boundary_flux(sc->h, sc->phi, out));
+  return 0;
+}
+
+/* ---- scalars that drive the flow: the Boussinesq term (fluca_host.h) */
+FlErrorCode NSSetGravity(NS ns, const double g[3])
+{
+  if (!ns || !g) return E_ARG_NULL;
+  for (int d = 0; d < 3; ++d)
+    if (!(g[d] - g[d] == 0.)) return E_ARG_OUTOFRANGE;
+  for (int d = 0; d < 3; ++d) ns->gravity[d] = g[d];
+  return 0;
+}
+FlErrorCode NSGetGravity(NS ns, double g[3])
+{
+  if (!ns || !g) return E_ARG_NULL;
+  for (int d = 0; d < 3; ++d) g[d] = ns->gravity[d];
+  return 0;
+}
+FlErrorCode NSSetScalarBuoyancy(NS ns, int id, double beta, double phi_ref)
+{
+  struct NSScalar *sc = NULL;
+  FLCHK(scalar_get(ns, id, &sc));
+  if (!(beta - beta == 0.) || !(phi_ref - phi_ref == 0.)) return E_ARG_OUTOFRANGE;
+  sc->beta    = beta;
+  sc->phi_ref = phi_ref;
+  return 0;
+}
+/* the term is there: gravity is not zero and some scalar has beta != 0 */
+static int buoyancy_active(NS ns)
+{
+  if (ns->gravity[0] == 0. && ns->gravity[1] == 0. && ns->gravity[2] == 0.) return 0;
+  for (int a = 0; a < ns->nscalar; ++a)
+    if (ns->scalars[a].beta != 0.) return 1;
+  return 0;
+}
+/* momrhs += dt sum_s (-beta_s g) (phi_s - phi_ref_s) over the scalars with beta != 0, in the order of their ids: one launch, or none */
+static FlErrorCode buoyancy_add(NS ns, double *momrhs)
+{
+  if (!buoyancy_active(ns)) return 0;
+  const double *phi[MAXNSSCALARS];
+  double        accel[3 * MAXNSSCALARS], ref[MAXNSSCALARS];
+  int           n = 0;
+  for (int a = 0; a < ns->nscalar; ++a) {
+    const struct NSScalar *sc = &ns->scalars[a];
+    if (sc->beta == 0.) continue;
+    phi[n] = sc->phi;
+    ref[n] = sc->phi_ref;
+    for (int d = 0; d < 3; ++d) accel[3 * n + d] = -sc->beta * ns->gravity[d];
+    ++n;
+  }
+  FLABI(fl_momentum_add_buoyancy(ns->momentum, n, phi, accel, ref, ns->dt, momrhs));
   return 0;
 }
 
@@ -2408,6 +2487,9 @@ static FlErrorCode NSFormFunction_CNLinear(NS ns, const NSVec *x, NSVec *f)
     FLABI(fl_vec_lincomb(h, 3 * ns->ibm_L, -1., ns->ibm_U, 1., ns->ibm_Ut, ns->ibm_U)); /* U_target - U (z = NULL: target 0) */
     FLABI(fl_ibm_spread(ns->ibm, 3, ns->ibm_U, ns->ibm_dV, f->v));
   }
+  /* Boussinesq buoyancy of the active scalars as they stand when the step begins (phi^n: explicit, first order in time); nothing is launched without
+   * gravity or without an active scalar.  The forcing above is formed from v0 alone: the buoyancy of the step is not anticipated at the markers. */
+  FLCHK(buoyancy_add(ns, f->v));
   /* PRESSURE_OUTLET: the boundary-condition vector of G in momrhs (:2976-2984, :219-423) and the Rhie-Chow boundary terms
    * of interprhs (:3013-3044).  As written in the reference, the G vector is NOT scaled by dt/rho in momrhs. */
   {

@@ -441,3 +441,17 @@ class Momentum:
         check(lib.fl_momentum_rhs(self.h, float(dt), float(rho), float(mu), _ptr(v0), _ptr(p), _ptr(vbc), _ptr(out)), "fl_momentum_rhs")
         self.p._post()
         return out
+
+    def add_buoyancy(self, momrhs, phis, accel, refs, dt):
+        """momrhs[d N + c] += dt sum_s accel[s][d] (phis[s][c] - refs[s]) in place, one launch for all scalars (fl_momentum_add_buoyancy);
+        accel: nscalar x 3, accel[s][d] = -beta_s g_d.  A component whose coefficients are all zero is not touched."""
+        ns = len(phis)
+        assert momrhs.numel() == 3 * self.p.ncell and all(t.numel() == self.p.ncell for t in phis)
+        a = [float(v) for row in accel for v in row]
+        assert len(a) == 3 * ns and len(refs) == ns
+        ptrs = (C.c_void_p * max(ns, 1))(*[_ptr(t) for t in phis])
+        self.p._pre()
+        check(lib.fl_momentum_add_buoyancy(self.h, ns, ptrs, (C.c_double * max(3 * ns, 1))(*a), (C.c_double * max(ns, 1))(*[float(r) for r in refs]), float(dt), _ptr(momrhs)),
+              "fl_momentum_add_buoyancy")
+        self.p._post()
+        return momrhs

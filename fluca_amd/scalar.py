@@ -110,3 +110,14 @@ class Scalar:
         check(lib.fl_scalar_stats(self.h, _ptr(phi), out), "fl_scalar_stats")
         self.P._post()
         return out[0], out[1], out[2]
+
+    def boundary_flux(self, phi):
+        """-> (6, 2) array: per boundary the convective flux sum V phi_f A and the diffusive flux sum -Gamma g A through it, both along the +axis
+        (fl_scalar_boundary_flux); a periodic end gives 0, 0"""
+        import numpy as np
+        assert phi.numel() == self.P.ncell
+        out = (C.c_double * 12)()
+        self.P._pre()
+        check(lib.fl_scalar_boundary_flux(self.h, _ptr(phi), out), "fl_scalar_boundary_flux")
+        self.P._post()
+        return np.array(list(out), dtype=np.float64).reshape(6, 2)

@@ -395,6 +395,16 @@ int fl_momentum_interp_faces_ends(fl_momentum *m, const double *v_dev, const dou
  * L, C and G combined by the caller, (mu dt/2 rho)(vbcL(t) + vbcL(t+dt)) - dt vbcC - vbcG -- they are zero for periodic
  * boundaries and homogeneous walls.  kappa is the handle's dt/rho. */
 int fl_momentum_rhs(fl_momentum *m, double dt, double rho, double mu, const double *v0_dev, const double *p_dev, const double *vbc_dev, double *momrhs_dev);
+/* Boussinesq buoyancy (no reference counterpart), ONE launch for all active scalars:
+ * momrhs[d*N + c] += dt * sum_{s < nscalar} accel[3*s + d] * (phi_dev[s][c] - phi_ref[s]),   d = 0..2, c over the N cells of the handle's block.
+ * accel[3*s + d] = -beta_s * g_d: the acceleration per unit of scalar s along axis d (rho = rho0 (1 - beta (phi - phi_ref))).
+ * A component d whose nscalar coefficients are all zero is neither read nor written (its bits stay, a -0.0 included).
+ * Pointwise: on a rank's block of several it needs no communication and gives the one-rank bits.
+ * phi_dev is a HOST array of nscalar device pointers.  Per cell and component: x_s = phi_s - ref_s, t = a_0 x_0, t = fma(a_s, x_s, t) for s = 1 .. in
+ * ascending order, momrhs = fma(dt, t, momrhs).  8 nscalar + 16 (components with a non-zero coefficient) bytes per cell.
+ * FL_ERR_ARG_NULL: a missing handle, array or phi_dev[s]; FL_ERR_ARG_OUTOFRANGE: nscalar outside 1..8, a non-finite coefficient, reference or dt
+ * (all checked before the handle is used).  All coefficients zero: success, nothing is launched. */
+int fl_momentum_add_buoyancy(fl_momentum *m, int nscalar, const double *const phi_dev[], const double accel[], const double phi_ref[], double dt, double *momrhs_dev);
 
 /* ---- the whole preconditioner application ---------------------------------------------------- */
 /* MatMult of the 3 x 3 block Jacobian the preconditioner belongs to (MatNest of cnlinearcart3d.c:2885-2941), for an outer
@@ -571,6 +581,16 @@ int fl_scalar_cfl(fl_scalar *m, double dt, double out[2]);
  * all ranks; the sum is each rank's block-ordered sum added over the ranks -- the same bits on every call and on every rank, NOT the same bits
  * across rank grids (another split sums in another order) */
 int fl_scalar_stats(fl_scalar *m, const double *phi_dev, double out[3]);
+/* The flux of phi through the six boundaries of the domain (the heat flux through a wall: the Nusselt number's numerator):
+ * out[2*b] = sum over the faces of boundary b of V_d(f) phi_f(f) A(f)   (convective), out[2*b+1] = sum of -Gamma g_d(f) A(f)   (diffusive),
+ * b = 0..5 in the order of bc[6]; both are fluxes ALONG THE +AXIS (the convention of the Neumann value), not along the outward normal.
+ * phi_f and g on a boundary face are those of the boundary rule above (Dirichlet: phi_b and (phi_0 - phi_b)/(xc_0 - xf_0), mirrored at the high
+ * end; Neumann: phi_near -/+ dist*g and the value).  A periodic end gives exactly 0, 0.  A(f) = the product of the two in-plane face-to-face widths.
+ * With these, sum_c R(phi)(c) vol(c) = sum_d [(out[4d] + out[4d+1]) - (out[4d+2] + out[4d+3])] + sum_c q(c) vol(c) up to rounding.
+ * Waits for the stream.  FL_ERR_ARG_WRONGSTATE before a velocity is set.  Several ranks: collective; a rank that does not touch boundary b
+ * adds nothing to it; each rank's sums in a fixed order, the ranks through fl_allreduce_sum -- the same bits on every call and rank, not across rank grids
+ * (the contract of fl_scalar_stats' sum). */
+int fl_scalar_boundary_flux(fl_scalar *m, const double *phi_dev, double out[12]);
 
 #ifdef __cplusplus
 }

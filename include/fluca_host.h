@@ -24,7 +24,7 @@
  *   pressure update of NSStep_CNLinear_Cart3d_Internal (NSUpdatePressure)                               fluca/src/ns/impl/linearcn/cnlinearcart3d.c:2846-2854
  *   options -cart_grid_x.. -cart_ranks_x.. -cart_boundary_type_x.. -ns_density -ns_viscosity
  *           -ns_time_step_size -ns_max_steps -ns_abf_schur_ksp_{type,rtol,atol,max_it,norm_type} -ns_abf_schur_pc_type   cart.c:21-43, nsopts.c:177-198, abfpc.c:206,248-249
- *           -ns_scalar_limiter -ns_scalar_stages (passive scalars, NSAddScalar)
+ *           -ns_scalar_limiter -ns_scalar_stages (passive scalars, NSAddScalar); -ns_gravity gx,gy,gz (NSSetGravity)
  *           (-ns_abf_schur_pc_type mg [-ns_abf_schur_pc_mg_levels N -ns_abf_schur_mg_levels_ksp_max_it NU]: the build's own multigrid)
  *
  * Every function returns FlErrorCode: 0 = success, otherwise the positive PETSC_ERR_* value the reference would raise.
@@ -276,6 +276,22 @@ FlErrorCode NSSetScalarSource(NS ns, int id, const double *src_dev);
 FlErrorCode NSSetScalarSubsteps(NS ns, int id, int n);
 FlErrorCode NSGetScalarArray(NS ns, int id, double **phi_dev);
 FlErrorCode NSGetScalarCFL(NS ns, int id, double out[2]);
+/* SCALARS THAT DRIVE THE FLOW (Boussinesq; no reference counterpart): with a gravity g != 0 and a scalar whose beta != 0 the right-hand side of the
+ * step (NSFormFunction, hence NSStep) gains  momrhs += dt sum_s (-beta_s g) (phi_s - phi_ref_s),  rho = rho0 (1 - beta (phi - phi_ref)): ONE launch for
+ * all active scalars (fl_momentum_add_buoyancy), added directly after the immersed-boundary term.  phi is the scalars' field as it stands when the step
+ * begins (phi^n): the term is explicit and first order in time, like the scalar-flow coupling above.  The immersed-boundary forcing keeps its rule
+ * (U_target - interp(v0)): the buoyancy of the step is NOT anticipated at the markers.  With g = 0 or every beta = 0 nothing is launched and every
+ * result keeps its bits.  Pointwise, so no communication on several ranks.
+ *   NSSetGravity / NSGetGravity   g[3], finite (E_ARG_OUTOFRANGE otherwise); default 0; any time.  Option: -ns_gravity gx,gy,gz (three numbers: E_ARG_WRONG otherwise)
+ *   NSSetScalarBuoyancy           beta and phi_ref of scalar id, finite; default beta = 0: passive.  After NSSetUp, like the other scalar calls
+ *   NSGetScalarBoundaryFlux       fl_scalar_boundary_flux with the current phi and the solution's face velocities: out[2 b] the convective, out[2 b + 1] the
+ *                                 diffusive flux through boundary b, both along the +AXIS (a hot wall at x = 0 and a cold wall at x = 1 both give a positive
+ *                                 diffusive flux).  Collective, like NSGetScalarCFL.
+ * NSView prints gravity and the (beta, phi_ref) pairs only while the term is active. */
+FlErrorCode NSSetGravity(NS ns, const double g[3]);
+FlErrorCode NSGetGravity(NS ns, double g[3]);
+FlErrorCode NSSetScalarBuoyancy(NS ns, int id, double beta, double phi_ref);
+FlErrorCode NSGetScalarBoundaryFlux(NS ns, int id, double out[12]);
 FlErrorCode NSGetSolutionArrays(NS ns, double **v_dev, double *V_dev[3], double **p_dev);
 FlErrorCode NSGetPressureHalfStep(NS ns, double **phalf_dev); /* cnl->phalf, the vector named "PressureHalfStep" (cnlinear.c:54) */
 FlErrorCode NSGetMesh(NS ns, Mesh *mesh);

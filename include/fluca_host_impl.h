@@ -128,6 +128,7 @@ struct _p_NS {
   struct NSScalar     *scalars;          /* nscalar entries */
   int                  scalar_stages;    /* -ns_scalar_stages (default 5, the reference's -ts_type ssp) */
   int                  scalar_limiter;   /* -ns_scalar_limiter: the limiter of a scalar added without a name of its own (default superbee) */
+  double               gravity[3];       /* NSSetGravity / -ns_gravity (default 0): with a scalar whose beta != 0 the Boussinesq term of the right-hand side */
 };
 struct NSScalar {
   char          name[32];
@@ -136,6 +137,7 @@ struct NSScalar {
   int           limiter, substeps, kind[6];
   double       *phi;      /* device, owned by the NS */
   const double *src;      /* device, borrowed; may be NULL */
+  double        beta, phi_ref; /* NSSetScalarBuoyancy: rho = rho0 (1 - beta (phi - phi_ref)); beta = 0 (default): passive */
 };
 
 /* NSCNLINEAR's data (nslinearcnimpl.h: v0interp, phalf, B) plus, in this mirror, the solution and solver vectors the

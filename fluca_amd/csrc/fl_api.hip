@@ -301,13 +301,28 @@ extern "C" int fl_poisson_rhs(fl_poisson *h, const double *Vx, const double *Vy,
   return FL_SUCCESS;
 }
 
+// The route fl_poisson_project takes for these pointers (host arithmetic; fldbg_project_path reports it).  The last line restates the `pairs`
+// rule of launch_project_all, which stays where it is: the text of fl_kernels.hip is tied to the counter passes bench.py quotes
+// (fluca_amd/provenance.py).  tests/test_gpu_caller_arrays.py holds both branches to the same bits.
+enum { PROJECT_SIX_DIRECT = 0, PROJECT_SIX_PADDED = 1, PROJECT_ALL_PAIRS = 2, PROJECT_ALL_SINGLE = 3 };
+static int project_path(const fl_poisson *h, const double *p_dev, double *const v[3], double *const V[3])
+{
+  // all six arrays (PCApply_ABF's call), one rank: k_project_six reads the caller's p itself -- no padded copy, no ghost layers
+  if (!h->multi && project_six_usable(h->g, p_dev, v, V)) return PROJECT_SIX_DIRECT;
+  if (project_six_usable(h->g, nullptr, v, V)) return PROJECT_SIX_PADDED;  // several ranks: the same kernel on the padded p
+  int pairs = h->g.nx % 2 == 0;  // any subset of the six arrays, one pass over p: 16-byte accesses for even rows and aligned bases
+  for (int d = 0; d < 3; ++d)
+    if ((v[d] && (reinterpret_cast<uintptr_t>(v[d]) & 15)) || (d > 0 && V[d] && (reinterpret_cast<uintptr_t>(V[d]) & 15))) pairs = 0;
+  return pairs ? PROJECT_ALL_PAIRS : PROJECT_ALL_SINGLE;
+}
+
 extern "C" int fl_poisson_project(fl_poisson *h, const double *p_dev, double *vx, double *vy, double *vz, double *Vx, double *Vy, double *Vz)
 {
   if (!h || !p_dev) return FL_ERR_ARG_NULL;
   FL_HIP(hipSetDevice(h->device));
   double *v[3] = {vx, vy, vz}, *V[3] = {Vx, Vy, Vz};
-  // all six arrays (PCApply_ABF's call), one rank: k_project_six reads the caller's p itself -- no padded copy, no ghost layers
-  if (!h->multi && project_six_usable(h->g, p_dev, v, V)) {
+  const int path = project_path(h, p_dev, v, V);
+  if (path == PROJECT_SIX_DIRECT) {
     int per = 0;
     for (int d = 0; d < 3; ++d) per |= h->wrap_local[d] ? (1 << d) : 0;
     launch_project_six(h->stream, h->g, p_dev, true, per, v, V);
@@ -317,13 +332,24 @@ extern "C" int fl_poisson_project(fl_poisson *h, const double *p_dev, double *vx
   FL_CHK(fl_ensure_vec(h, &h->w0));
   launch_pad_copy(h->stream, h->g, p_dev, h->w0);
   FL_CHK(fl_fill_ghosts(h, h->w0));
-  if (project_six_usable(h->g, nullptr, v, V)) {  // several ranks: the same kernel on the padded p
+  if (path == PROJECT_SIX_PADDED) {
     launch_project_six(h->stream, h->g, h->w0, false, 0, v, V);
     FL_HIP(hipGetLastError());
     return FL_SUCCESS;
   }
-  launch_project_all(h->stream, h->g, h->w0, v, V);  // any subset of the six arrays, one pass over p
+  launch_project_all(h->stream, h->g, h->w0, v, V);  // any subset of the six arrays, one pass over p; decides on the pairs itself
   FL_HIP(hipGetLastError());
+  return FL_SUCCESS;
+}
+
+// Not part of the public C-ABI (tests/test_gpu_caller_arrays.py): which route fl_poisson_project takes for these pointers -- 0 k_project_six on
+// the caller's p, 1 k_project_six on the padded p, 2 k_project_all with 16-byte accesses to the caller's arrays, 3 k_project_all with 8-byte
+// accesses.  Host arithmetic on the pointers' values only: nothing is read, written or launched.
+extern "C" int fldbg_project_path(fl_poisson *h, const double *p_dev, double *vx, double *vy, double *vz, double *Vx, double *Vy, double *Vz, int *path)
+{
+  if (!h || !p_dev || !path) return FL_ERR_ARG_NULL;
+  double *v[3] = {vx, vy, vz}, *V[3] = {Vx, Vy, Vz};
+  *path = project_path(h, p_dev, v, V);
   return FL_SUCCESS;
 }
 

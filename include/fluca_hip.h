@@ -33,6 +33,13 @@
  *   y-face(i,j,k) -> (k*fy + j)*nx + i ,  fy likewise      (DMStag: the extra face belongs to the last rank)
  *   z-face(i,j,k) -> (k*ny + j)*nx + i ,  k in [0,fz)
  *   Face f of an axis lies between cells f-1 and f.
+ *   Alignment: a device array needs the 8-byte alignment of a double and no more -- a sub-vector of a larger allocation (a block of a nest
+ *   vector, component d of a 3N array) may be passed as it is.  A base on a 16-byte boundary together with an even nx selects faster paths
+ *   (16-byte accesses) that give the same results, bit for bit.
+ *   Extent: an entry point reads and writes nothing outside the owned extents listed above (cells: nx*ny*nz, faces: the counts of
+ *   fl_poisson_sizes, a velocity: 3 such arrays back to back) of the arrays it is handed; what stands right before or behind an array in
+ *   memory is neither read into a result nor written.  (tests/test_gpu_caller_arrays.py holds the entry points it lists to both: all but
+ *   fl_ibm_rigid_pose, the body ids of fl_ibm_force and the owner-rank marker calls fl_ibm_owned_select / create_owned / migrate / owned_fetch.)
  */
 #ifndef FLUCA_HIP_H
 #define FLUCA_HIP_H

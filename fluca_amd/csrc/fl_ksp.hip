@@ -1641,6 +1641,9 @@ int fl_solve_cheb(fl_poisson *h, const double *b, double *x, const fl_ksp_opts *
   const int nhist = o->maxit + 2;
   FL_CHK(fl_ensure_hist(h, nhist));
   hipStream_t s = h->stream;
+  // without a monitored norm no kernel writes h->hist, and finish_stats hands iters + 1 entries of it to the caller: zeros (what KSPLogResidualHistory
+  // records under KSP_NORM_NONE, and what a fresh handle's buffer holds), not the norms -- or the NaN -- an earlier solve on the handle left there
+  if (o->norm_type == FL_NORM_NONE && o->history && o->nhistory > 0) FL_HIP(hipMemsetAsync(h->hist, 0, sizeof(double) * (size_t)nhist, s));
   double emin = o->emin, emax = o->emax;
   if (emin == 0. && emax == 0.) {
     const double lam = fl_gershgorin_bound(h, jac);

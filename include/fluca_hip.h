@@ -157,7 +157,12 @@ typedef struct fl_momentum fl_momentum;
 /* bc[6] as fl_bc.  kappa = dt/rho (MatScale at cnlinearcart3d.c:2890,2907).  device = HIP device ordinal. */
 int fl_poisson_create(const fl_grid *grid, const int bc[6], double kappa, const fl_decomp *decomp, int device, fl_poisson **out);
 int fl_poisson_destroy(fl_poisson *h);
-/* Run on a caller-owned hipStream_t (pass as void*); NULL = the handle's own stream. */
+/* Run on a caller-owned hipStream_t (pass as void*); NULL = the handle's own stream.  Everything the handle and the handles that borrow it
+ * (fl_momentum, fl_scalar, fl_ibm, the multigrid levels) enqueue from now on goes to that stream.  The call orders NOTHING: the new stream does
+ * not wait for the old one, and work the handle has enqueued on the old stream may still be in flight -- kernels, and the tables a solve
+ * uploads asynchronously on first use (the smoother's coefficient sequences), which launches on the new stream would then read.  THE CALLER
+ * SYNCHRONISES FIRST: fl_poisson_synchronize(h) (or its own wait for the old stream) before every switch; a switch on an idle handle changes no
+ * result, bit for bit (tests/test_gpu_handle_history.py). */
 int fl_poisson_set_stream(fl_poisson *h, void *hip_stream);
 int fl_poisson_synchronize(fl_poisson *h);
 /* every rank of the handle's communicator has reached this call when it returns (MPI_Barrier on the object's comm) */

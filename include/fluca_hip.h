@@ -39,7 +39,26 @@
  *   Extent: an entry point reads and writes nothing outside the owned extents listed above (cells: nx*ny*nz, faces: the counts of
  *   fl_poisson_sizes, a velocity: 3 such arrays back to back) of the arrays it is handed; what stands right before or behind an array in
  *   memory is neither read into a result nor written.  (tests/test_gpu_caller_arrays.py holds the entry points it lists to both: all but
- *   fl_ibm_rigid_pose, the body ids of fl_ibm_force and the owner-rank marker calls fl_ibm_owned_select / create_owned / migrate / owned_fetch.)
+ *   the body ids of fl_ibm_force and the owner-rank marker calls fl_ibm_owned_select / create_owned / migrate / owned_fetch.)
+ *
+ * Stream order.  EVERY CALL IS ORDERED ON THE HANDLE'S STREAM LIKE A KERNEL LAUNCH (fl_poisson_set_stream; the handles that borrow a fl_poisson
+ * share its stream): it reads its device arrays after everything enqueued on that stream before it and writes them before everything enqueued
+ * after it.  A producer on that stream may still be pending when the call is made; the caller may overwrite an input in stream order as soon as
+ * the call has returned.  The handle's own stream is non-blocking: work on the NULL stream is not ordered against it.  Unless a function says
+ * otherwise it ENQUEUES AND RETURNS -- the host does not wait for the stream (the first use on a handle may allocate and upload a table) -- and
+ * of a device array nothing is looked at after the call's own stream position.  A host array handed to such a call (an array of device
+ * pointers, coefficients, a struct) is read before the call returns: its values travel with the launch and the caller may free or overwrite it at
+ * once.  Where the handle keeps a COPY of a device array (the caller may overwrite it in stream order right after) or BORROWS a pointer (the
+ * memory is read when later calls run), the function says so.
+ * These calls WAIT for the handle's stream, i.e. everything enqueued before them has finished when they return:
+ *   fl_poisson_synchronize, fl_poisson_barrier, fl_poisson_allreduce_sum, fl_poisson_upload_fence, fl_memcpy_h2d, fl_memcpy_d2h (device-wide),
+ *   fl_poisson_comm_oneshot_error, fl_vec_dot, fl_vec_mdot, fl_poisson_solve, fl_momentum_solve, fl_abf_apply, fl_momentum_gershgorin,
+ *   fl_momentum_chebyshev_interval, fl_ibm_update, fl_ibm_force, fl_ibm_owned_select, fl_ibm_create_owned, fl_ibm_migrate, fl_scalar_cfl,
+ *   fl_scalar_stats, fl_scalar_boundary_flux.
+ * Create, destroy, allocation (fl_malloc, fl_free, fl_malloc_host, fl_free_host), communicator set-up and fl_poisson_tune_placement MAY wait.
+ * tests/stream_order.py restates this as a table, one row per function; tests/test_gpu_caller_arrays.py and tests/test_gpu_stream_order.py make
+ * every call behind a delay queued on the stream, with its inputs still to be produced and overwritten right after, and hold the results to the
+ * bits of the same calls on an idle stream.
  */
 #ifndef FLUCA_HIP_H
 #define FLUCA_HIP_H
@@ -165,7 +184,7 @@ int fl_poisson_destroy(fl_poisson *h);
  * result, bit for bit (tests/test_gpu_handle_history.py). */
 int fl_poisson_set_stream(fl_poisson *h, void *hip_stream);
 int fl_poisson_synchronize(fl_poisson *h);
-/* every rank of the handle's communicator has reached this call when it returns (MPI_Barrier on the object's comm) */
+/* every rank of the handle's communicator has reached this call when it returns (MPI_Barrier on the object's comm).  Waits for the stream. */
 int fl_poisson_barrier(fl_poisson *h);
 /* in-place sum of n <= 8 HOST doubles over the ranks of the handle's communicator (MPIU_Allreduce(..., MPI_SUM, comm) of a few scalars; a
  * flag "does any rank ..." is a sum of 0 / 1).  Blocking; a no-op on one rank.  Every rank must call it. */
@@ -191,12 +210,15 @@ int fl_free_host(void *host);
 int fl_poisson_upload(fl_poisson *h, void *dev, const void *host, size_t bytes);
 int fl_poisson_upload_fence(fl_poisson *h);
 
-/* y = a x + b z (z_dev may be NULL; y may alias x or z) and result = sum x y over all ranks (blocking; every rank passes its
- * owned entries) -- for hosts that run an outer iteration over device vectors and have no vector library of their own. */
+/* y = a x + b z (z_dev may be NULL; y may alias x or z) -- for hosts that run an outer iteration over device vectors and have no vector
+ * library of their own.  Enqueues and returns. */
 int fl_vec_lincomb(fl_poisson *h, int64_t n, double a, const double *x_dev, double b, const double *z_dev, double *y_dev);
+/* result (host) = sum x y over all ranks (every rank passes its owned entries).  Blocking: waits for the stream. */
 int fl_vec_dot(fl_poisson *h, int64_t n, const double *x_dev, const double *y_dev, double *result);
-/* VecMDot / VecMAXPY: out[i] = x . y_i (one host wait for all k) and x += sum_i alpha_i y_i; ys_dev is a HOST array of k device
- * pointers.  Classical Gram-Schmidt of the outer GMRES reads its work vector once per pass instead of once per basis vector. */
+/* VecMDot / VecMAXPY: out[i] = x . y_i (host array; one host wait for all k: fl_vec_mdot waits for the stream) and x += sum_i alpha_i y_i
+ * (fl_vec_maxpy enqueues and returns).  ys_dev is a HOST array of k device pointers, alphas a HOST array of k coefficients: both are read
+ * before the call returns (copied into the launches), the caller may free or overwrite them at once; the vectors they point to are read in the
+ * call's stream position.  Classical Gram-Schmidt of the outer GMRES reads its work vector once per pass instead of once per basis vector. */
 int fl_vec_mdot(fl_poisson *h, int64_t n, const double *x_dev, const double *const *ys_dev, int k, double *out);
 int fl_vec_maxpy(fl_poisson *h, int64_t n, double *x_dev, const double *alphas, const double *const *ys_dev, int k);
 
@@ -261,6 +283,8 @@ int fl_poisson_vector_bytes(fl_poisson *h, int64_t *bytes_out);
 /* ---- operator -------------------------------------------------------------------------------- */
 int fl_poisson_apply(fl_poisson *h, const double *x_dev, double *y_dev);  /* y = S x */
 int fl_poisson_diagonal(fl_poisson *h, double *d_dev);                    /* MatGetDiagonal(S) */
+/* KSPSolve(kspS, b, x), zero initial guess.  Waits for the stream: stats and opts->history are host values, complete when the call returns; b's
+ * producer on the handle's stream may be pending when the call is made.  (FL_KSP_CHEBYSHEV with check_every < 0 and FL_NORM_NONE polls nothing.) */
 int fl_poisson_solve(fl_poisson *h, const double *b_dev, double *x_dev, const fl_ksp_opts *opts, fl_ksp_stats *stats);
 /* Upper bound of the spectrum of M S (M = 1/diag for pc = FL_PC_JACOBI, identity otherwise) from the 1-D operator tables:
  * what the Chebyshev solver / smoother multiplies by (0.1, 1.1) when emin = emax = 0.  Host-only, no GPU work. */
@@ -368,15 +392,19 @@ int fl_momentum_create(fl_poisson *grid_from, fl_momentum **out);
 int fl_momentum_destroy(fl_momentum *m);
 /* V0_dev[d]: face-normal velocity of the previous step on the d-faces (sol0's NS_FIELD_FACE_NORMAL_VELOCITY);
  * v0interp_dev[c*3+d]: component c of cnl->v0interp on the d-faces.  Face layouts as at the top of this file.
- * Copies the twelve fields (the caller may reuse its buffers) and sets cI = 1, cC = dt, cL = -mu dt / (2 rho). */
+ * Copies the twelve fields in stream order (the caller may overwrite its buffers in stream order as soon as the call has returned; V0_dev and
+ * v0interp_dev themselves are host arrays of pointers, read before the call returns) and sets cI = 1, cC = dt, cL = -mu dt / (2 rho).  Enqueues
+ * and returns: the tables a later fl_momentum_apply reads are rebuilt in stream order, behind every product already enqueued. */
 int fl_momentum_set_state(fl_momentum *m, double dt, double rho, double mu, const double *const V0_dev[3], const double *const v0interp_dev[9]);
 /* The same state, handed over together with the cell-centred velocity it was interpolated from: v0_dev = sol0's NS_FIELD_VELOCITY
  * (3 * cells, component-major), v0interp = B v0 + vbc (cnlinearcart3d.c:2826-2829; vbc is non-zero on boundary faces only, :1749-1932).
  * The operator then forms v0interp on the inner faces from v0 inside its kernel (bit-identical to fl_momentum_interp_faces) and reads the
  * nine stored fields only on the faces at the ends of this rank's block: 96 B per cell and product instead of 144.  A v0interp that is
- * NOT B v0 on inner faces gives a different operator than fl_momentum_set_state -- use that entry point then. */
+ * NOT B v0 on inner faces gives a different operator than fl_momentum_set_state -- use that entry point then.
+ * v0_dev is COPIED like the twelve fields (into the handle's padded velocity, in stream order): the caller may overwrite it right after. */
 int fl_momentum_set_state_v0(fl_momentum *m, double dt, double rho, double mu, const double *const V0_dev[3], const double *const v0interp_dev[9], const double *v0_dev);
-/* A = cI I + cC C + cL L with explicit coefficients (other time integrators; L or C alone in the parity tests) */
+/* A = cI I + cC C + cL L with explicit coefficients (other time integrators; L or C alone in the parity tests).  Enqueues and returns: the scaled
+ * tables are rebuilt in stream order; a product enqueued before the call keeps the coefficients it was launched with. */
 int fl_momentum_set_coefficients(fl_momentum *m, double cI, double cC, double cL);
 int fl_momentum_apply(fl_momentum *m, const double *v_dev, double *y_dev); /* y = A v      (MatMult) */
 int fl_momentum_diagonal(fl_momentum *m, double *d_dev);                   /* MatGetDiagonal(A) */
@@ -384,7 +412,7 @@ int fl_momentum_diagonal(fl_momentum *m, double *d_dev);                   /* Ma
  * opts->type: FL_KSP_BCGS (left-preconditioned KSPBCGS, preconditioned norm), FL_KSP_GMRES (PETSc's default type for kspA; restart
  * opts->gmres_restart) or FL_KSP_CHEBYSHEV (KSPCHEBYSHEV's three-term recurrence fused into the product: 144 B per cell and step where a
  * BiCGStab iteration moves 552 -- the method of choice while the operator is diffusion-dominated, e.g. nu dt / h^2 > 1; interval from
- * opts->emin / emax = -ksp_chebyshev_eigenvalues, or with PCJACOBI fl_momentum_chebyshev_interval). */
+ * opts->emin / emax = -ksp_chebyshev_eigenvalues, or with PCJACOBI fl_momentum_chebyshev_interval).  Waits for the stream, like fl_poisson_solve. */
 int fl_momentum_solve(fl_momentum *m, const double *b_dev, double *x_dev, const fl_ksp_opts *opts, fl_ksp_stats *stats);
 /* V_d = rhs_d + (T v)_d on the d-faces: MatMult(abf->negT, vstar, Vstar); VecAYPX(Vstar, -1, interprhs), abfpc.c:73-74.
  * T = ComputeFaceNormalVelocityInterpolationOperator_Private, cnlinearcart3d.c:1934-2140.  rhs_dev (or any entry) may
@@ -414,6 +442,8 @@ int fl_momentum_rhs(fl_momentum *m, double dt, double rho, double mu, const doub
  * Pointwise: on a rank's block of several it needs no communication and gives the one-rank bits.
  * phi_dev is a HOST array of nscalar device pointers.  Per cell and component: x_s = phi_s - ref_s, t = a_0 x_0, t = fma(a_s, x_s, t) for s = 1 .. in
  * ascending order, momrhs = fma(dt, t, momrhs).  8 nscalar + 16 (components with a non-zero coefficient) bytes per cell.
+ * phi_dev[], accel[] and phi_ref[] are HOST arrays read before the call returns (they travel with the launch): the caller may free or overwrite
+ * them at once; the fields phi_dev[s] point to are read in the call's stream position.  Enqueues and returns.
  * FL_ERR_ARG_NULL: a missing handle, array or phi_dev[s]; FL_ERR_ARG_OUTOFRANGE: nscalar outside 1..8, a non-finite coefficient, reference or dt
  * (all checked before the handle is used).  All coefficients zero: success, nothing is launched. */
 int fl_momentum_add_buoyancy(fl_momentum *m, int nscalar, const double *const phi_dev[], const double accel[], const double phi_ref[], double dt, double *momrhs_dev);
@@ -427,7 +457,7 @@ int fl_abf_jacobian_mult(fl_momentum *m, const double *v_dev, const double *cons
  *   v* = A^-1 momrhs ; V* = interprhs + T v* ; p = S^-1 (contrhs - D V*) ; v = v* - kappa G p ; V = V* - kappa Gst p
  * v_dev (3*cells, component-major), V_dev[3] (faces) and p_dev (cells) are outputs; interprhs_dev / contrhs_dev may be
  * NULL = 0.  stats[0] = KSPSolve(kspA), stats[1] = KSPSolve(kspS).  A non-converged inner solve is reported in stats,
- * not as an error (PETSc's behaviour without -ksp_error_if_not_converged). */
+ * not as an error (PETSc's behaviour without -ksp_error_if_not_converged).  Waits for the stream (two solves). */
 int fl_abf_apply(fl_momentum *m, const fl_ksp_opts *momentum_opts, const fl_ksp_opts *schur_opts, const double *momrhs_dev, const double *const interprhs_dev[3], const double *contrhs_dev, double *v_dev,
                  double *const V_dev[3], double *p_dev, fl_ksp_stats stats[2]);
 /* PCABFAinvType (flucans.h:99-103): the approximation of A^-1 inside the Schur complement (PCABFSetSchurComplementAinvType,
@@ -442,10 +472,11 @@ int fl_abf_schur_apply(fl_momentum *m, const double *p_dev, double *y_dev);
 /* MatGetRowSum(A) into 3*cells doubles (component-major), like fl_momentum_diagonal */
 int fl_momentum_rowsum(fl_momentum *m, double *out_dev);
 /* Gershgorin radius of the Jacobi-scaled momentum operator: max over the rows of (sum of |a_ij|, j != i) / |a_ii|, over all ranks.  Every
- * eigenvalue of D^-1 A lies in the disc of this radius around 1.  One product-sized launch and a host wait per state (cached). */
+ * eigenvalue of D^-1 A lies in the disc of this radius around 1.  One product-sized launch and a host wait per state (cached): waits for the stream. */
 int fl_momentum_gershgorin(fl_momentum *m, double *radius);
 /* The interval FL_KSP_CHEBYSHEV on kspA uses when opts->emin = emax = 0 (PCJACOBI): emax = 1 + g, emin = max(1 - g, 0.9 / mean_i a_ii) -- the
- * second is where the spectrum of a viscous-dominated A = I + dt C - (mu dt / 2 rho) L ends (fl_momentum.hip says why). */
+ * second is where the spectrum of a viscous-dominated A = I + dt C - (mu dt / 2 rho) L ends (fl_momentum.hip says why).  Waits for the stream
+ * (once per state). */
 int fl_momentum_chebyshev_interval(fl_momentum *m, double *emin, double *emax);
 
 /* ---- immersed boundary (build-defined; no reference function) -------------------------------- */
@@ -454,7 +485,10 @@ typedef enum { FL_DELTA_PESKIN4 = 0, FL_DELTA_ROMA3 = 1 } fl_delta_kind;
  * function is evaluated in index space (marker position -> continuous cell-centre index, piecewise linear through the centres) and
  * spreading divides by the volume of the target cell; on uniform axes that is the textbook delta_h.  A position on a
  * periodic axis is taken modulo the period: a marker any number of periods beyond either end counts as its image in the box.  The caller keeps
- * positions within reach of an int: (X - x0) / h, in cells, must stay below 2^31 in size. */
+ * positions within reach of an int: (X - x0) / h, in cells, must stay below 2^31 in size.
+ * The marker arrays are COPIED into the set in stream order (a producer of X, Y, Z on the handle's stream may be pending); fl_ibm_create (set-up)
+ * and fl_ibm_update then wait for the stream -- the host reads the number of occupied bins -- so the caller may do with its arrays what it likes
+ * once the call has returned.  fl_ibm_interp and fl_ibm_spread do not wait: launches only. */
 int fl_ibm_create(fl_poisson *grid_from, int kind, int64_t L, const double *X_dev, const double *Y_dev, const double *Z_dev, fl_ibm **out);
 int fl_ibm_update(fl_ibm *m, const double *X_dev, const double *Y_dev, const double *Z_dev);
 /* U[c*L + l] = sum_x u[c*ncell + x] delta_h(x - X_l) h^3 */
@@ -513,7 +547,8 @@ int fl_ibm_migrate(fl_ibm *m, const double *X_dev, const double *Y_dev, const do
  * positions, numbers (gid_dev: sets with numbers only), the first nattr attributes of the last migrate (attr_out[a*Lo + l]; nattr beyond what that
  * call carried: FL_ERR_ARG_OUTOFRANGE).  Any output may be NULL.  Stream-ordered; not collective. */
 int fl_ibm_owned_fetch(fl_ibm *m, int64_t cap, double *X_dev, double *Y_dev, double *Z_dev, int64_t *gid_dev, int nattr, double *attr_out_dev);
-/* A rigid body's markers from their reference positions (device, length L; stream-ordered, not collective): X_l = centre + R(rotvec) (X0_l - centre0)
+/* A rigid body's markers from their reference positions (device, length L; stream-ordered, not collective; enqueues and returns; the five host
+ * arrays of 3 are read before the call returns): X_l = centre + R(rotvec) (X0_l - centre0)
  * with R by Rodrigues' formula (rotvec = axis * angle, host arrays of 3), Ut[c*L + l] = velocity + omega x (X_l - centre).  X/Y/Z (all three or
  * none) and Ut may be NULL.  The rotation matrix is formed on the host: every rank moves its markers with the same nine numbers. */
 int fl_ibm_rigid_pose(fl_poisson *grid_from, int64_t L, const double *X0_dev, const double *Y0_dev, const double *Z0_dev, const double centre0[3], const double centre[3], const double rotvec[3], const double velocity[3],
@@ -523,6 +558,7 @@ int fl_ibm_rigid_pose(fl_poisson *grid_from, int64_t L, const double *X0_dev, co
  * has migrated.  F_dev[c*L + l] (three components, the layout of fl_ibm_spread's F), dV_dev[l], body_dev[l] in 0..nbody-1
  * (device; NULL: one body, nothing is indexed), L = the set's marker count (Lo on an owned set: ghost copies never contribute), positions = the
  * set's own as of the last create / update / migrate.  about, force, torque: HOST arrays of 3 nbody doubles, 1 <= nbody <= 64; torque may be NULL.
+ * Waits for the stream (force and torque are host values): about is read, and F, dV and the ids are consumed, before the call returns.
  *   force[3b+c]  = sum_l F_c,l dV_l                     torque[3b+.] = sum_l (r_l x F_l) dV_l,  r_l = X_l - about_b
  * over the markers of body b; on a periodic axis r is the minimum image, r -= P rint(r / P), P = xf[n] - xf[0].  Every product, difference and
  * quotient of a term is rounded once (no fused multiply-add): the torque term is ((r_y F_z) - (r_z F_y)) dV, cyclically.
@@ -575,12 +611,16 @@ int fl_scalar_create(fl_poisson *grid_from, const int bc[6], fl_scalar **out);
  * tables or slabs takes part in the same vote: it returns its own error, its peers FL_ERR_GPU, and none holds a handle. */
 int fl_scalar_create_ranks(fl_poisson *grid_from, const int bc[6], fl_scalar **out);
 int fl_scalar_destroy(fl_scalar *m); /* NULL is success */
+/* The three setters below change host values that travel with every later launch: no GPU work, and a launch already enqueued keeps what it
+ * was launched with. */
 int fl_scalar_set_boundary_value(fl_scalar *m, int boundary, double value);
 int fl_scalar_set_limiter(fl_scalar *m, int limiter); /* default superbee, as the reference */
 int fl_scalar_set_diffusivity(fl_scalar *m, double gamma); /* >= 0, finite */
-/* device arrays, borrowed until the next call of this function: read by rhs / step / cfl at the time of THEIR call */
+/* device arrays, BORROWED until the next call of this function: read by rhs / step / cfl / boundary_flux when THEIR kernels run, in stream order
+ * (no GPU work here; the caller overwrites them only behind the last such call it has enqueued) */
 int fl_scalar_set_velocity(fl_scalar *m, const double *Vx_dev, const double *Vy_dev, const double *Vz_dev);
-/* out = R(phi); source_dev (q, cells) may be NULL; out_dev must not be phi_dev (FL_ERR_ARG_WRONG).  FL_ERR_ARG_WRONGSTATE before a velocity is set */
+/* out = R(phi); source_dev (q, cells) may be NULL; out_dev must not be phi_dev (FL_ERR_ARG_WRONG).  FL_ERR_ARG_WRONGSTATE before a velocity is set.
+ * On one rank fl_scalar_rhs and fl_scalar_step enqueue and return (several ranks: collective, a host-staged transport waits). */
 int fl_scalar_rhs(fl_scalar *m, const double *phi_dev, const double *source_dev, double *out_dev);
 /* One step of the s-stage second-order SSP Runge-Kutta method (Ketcheson; PETSc -ts_type ssp, rks2), in place, V and q frozen:
  *   w = phi; s-1 times w += dt/(s-1) R(w); phi = ((s-1) w + phi + dt R(w)) / s.     nstages = s >= 2 (the reference's default: 5).

@@ -162,3 +162,54 @@ def regime_fields(n, kind, X, periodic, xf, block=None):
 def ulp_factor(n):
     """K of the derived bound |U - U_ref| <= K u max|u| (tests/test_ibm_regimes.py): 60 (max n_d + 2) + 70"""
     return 60 * (max(n) + 2) + 70
+
+
+# ---- a body in prescribed rigid motion (fl_ibm_rigid_pose) ----------------------------------------------------------------------------------
+
+U53 = 2.0 ** -53
+
+
+def rigid_pose(X0, centre0, centre, rotvec, velocity, omega):
+    """X_l = centre + R(rotvec) (X0_l - centre0) by Rodrigues' rotation of each vector, r' = r cos th + (k x r) sin th + k (k . r)(1 - cos th),
+    rotvec = th k, and Ut_l = velocity + omega x (X_l - centre), in long double (1 - cos th as 2 sin^2(th / 2): no cancellation at a small angle).
+    X0: (3, L).  -> X (3, L), Ut (3, L) long double and the bounds bX, bU (3, L) double a correctly built fp64 evaluation stays within:
+
+    u = 2^-53.  The library forms the nine entries of R on the host in double: th = sqrt(sum of three squares), relative error <= 3 u; k = rotvec / th,
+    <= 4 u; cos and sin of the rounded th, off by <= 3 u th from the argument and <= 2 u from the library: (3 th + 2) u each, absolutely.  An entry is
+    [a == b] cos + sin K_ab + (1 - cos) k_a k_b, every factor at most 1 (1 - cos: 2) in size: (3 th + 7) u for the second term, (3 th + 24) u for the
+    third (one subtraction and two products of values up to 2, 4 u twice for k), 3 u for the two additions -- (9 th + 36) u =: KR u per entry.
+    On the device r0 = X0 - centre0 (u |r0_b| each), r_a = sum_b R_ab r0_b (a dot product of three: 3 u sum |R_ab r0_b|, fused or not), with |R_ab| <= 1:
+        |r_a - exact| <= (KR + 1 + 3) u S0,   S0 = sum_b |r0_b|,   and |r_a| <= S0
+    X_a = centre_a + r_a, one more rounding of a value <= |centre_a| + S0:             bX = ((KR + 5) S0 + |centre_a|) u
+    Ut_a = v_a + (w_b r_c - w_c r_b): the products inherit r's error and round once, the difference and the sum round once each:
+                                                                                        bU = ((KR + 7) (|w_b| + |w_c|) S0 + |v_a|) u
+    both times 1 + 2^-10 for the terms of second order and this reference's own rounding (2^-64 relative per operation)."""
+    X0 = np.asarray(X0, dtype=np.float64).astype(LD)
+    c0, c, rv, v, w = [np.asarray(a, dtype=np.float64).astype(LD) for a in (centre0, centre, rotvec, velocity, omega)]
+    th = np.sqrt(rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2])
+    r0 = X0 - c0[:, None]
+    if th > 0:
+        k = rv / th
+        cs, sn, vers = np.cos(th), np.sin(th), 2 * np.sin(th / 2) ** 2
+        kxr = np.stack([k[1] * r0[2] - k[2] * r0[1], k[2] * r0[0] - k[0] * r0[2], k[0] * r0[1] - k[1] * r0[0]])
+        kr = k[0] * r0[0] + k[1] * r0[1] + k[2] * r0[2]
+        r = r0 * cs + kxr * sn + k[:, None] * (kr * vers)[None, :]
+    else:
+        r = r0.copy()
+    X = c[:, None] + r
+    Ut = v[:, None] + np.stack([w[1] * r[2] - w[2] * r[1], w[2] * r[0] - w[0] * r[2], w[0] * r[1] - w[1] * r[0]])
+    KR = 9.0 * float(th) + 36.0
+    S0 = np.abs(r0).sum(axis=0).astype(np.float64)
+    slack = 1 + 2.0 ** -10
+    cabs, vabs, wabs = [np.abs(np.asarray(a, dtype=np.float64)) for a in (centre, velocity, omega)]
+    bX = np.stack([((KR + 5) * S0 + cabs[a]) * U53 * slack for a in range(3)])
+    bU = np.stack([((KR + 7) * (wabs[(a + 1) % 3] + wabs[(a + 2) % 3]) * S0 + vabs[a]) * U53 * slack for a in range(3)])
+    return X, Ut, bX, bU
+
+
+def rigid_pose_within(got, want, bound):
+    """largest |got - want| / bound over the entries (long double difference; a zero bound admits only the exact value)"""
+    err = np.abs(np.asarray(got, dtype=np.float64).astype(LD) - want).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.where(err == 0, 0.0, err / np.asarray(bound, dtype=np.float64))
+    return float(q.max()) if q.size else 0.0

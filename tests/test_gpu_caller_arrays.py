@@ -6,8 +6,8 @@ What the host decides from a pointer's low bits (all of it)
 fl_poisson_project), unpadded_pairs (k_cg_init reading b, k_cg_finish writing x), mom_apply_t (k_mom2 / k_mom3 storing y), mom_pw (k_mom_pw3
 reading b) and the buoyancy kernel's mask (tests/test_gpu_buoyancy.py).  Each takes its 16-byte branch for an aligned base AND an even nx.
 
-Every case runs on arrays of their own (the ordinary call), then in placement A (the control: aligned, guarded), then B (8 bytes off), D (packed)
-and, where named, C (alternating), and asserts:
+Every case runs on arrays of their own (the ordinary call), then PENDING (below), then in placement A (the control: aligned, guarded), then B (8 bytes
+off), D (packed) and, where named, C (alternating), and asserts:
   1. Arena.check: no guard word, no input and no array the call may not write changed by a bit; every output entry lost its sentinel;
   2. every result is finite;
   3. the result against the reference and at the tolerance of the entry point's own test (named beside each check) -- no tolerance is new here;
@@ -18,6 +18,13 @@ and, where named, C (alternating), and asserts:
   6. fl_poisson_project took the route the placement calls for (fldbg_project_path); for the two-way dispatches the phase the arena asserted
      together with the parity of nx names the branch, and each run prints both.
 
+  7. the PENDING run (drive): the same call on the same handle behind a delay queued on the handle's stream (tests/stream_order.py: DELAY_MS of
+     torch.cuda._sleep, no host callback), its inputs still poison when the call is made -- their producer, a device-to-device copy, is queued on the
+     stream behind the delay -- and poisoned again in stream order right after; arrays the header calls copied are poisoned as soon as they are
+     handed over (T.release), borrowed ones after the last call that reads them.  Poison is NaN; marker positions, which become cell indices, are
+     another valid marker set instead.  Every result is finite and has the ordinary run's bits, and where every entry point of the case is `async`
+     in tests/stream_order.py the delay had not ended when call(T) returned: the host did not wait.  Each run prints the host time of call(T).
+
 Grids: the smallest at which each branch is live (GRIDS below), at most 3510 cells.  IBM runs on the same shapes with walls and, on G4, its
 periodic x (the kernels know walls and periodic axes, and a periodic axis needs twice the support in cells: fl_ibm_create), the scalar on the same shapes
 with the boundary set of tests/scalar_cases.py that has the same periodic axes.  G1 and G5 have one multigrid level: CG + multigrid runs there
@@ -26,14 +33,15 @@ as tests/test_gpu_mg.py::test_one_level_hierarchy_keeps_the_outer_residual holds
 Covered: fl_poisson_apply, _diagonal, _rhs, _project, _gst_bc, _solve (five solvers); fl_boundary_set_faces, _add_faces, _add_cells;
 fl_pressure_update; fl_momentum_set_state, _set_state_v0, _apply, _diagonal, _rowsum, _solve (four), _face_interp, _face_interp_scaled,
 _interp_faces, _interp_faces_ends, _rhs, _add_buoyancy; fl_abf_jacobian_mult, _apply, _schur_apply; fl_vec_lincomb, _dot, _mdot, _maxpy;
-fl_layout_{from,to}_dmstag_{local,global}; fl_ibm_create, _update, _interp, _spread, _force (one body); fl_scalar_set_velocity, _rhs, _step,
-_stats, _cfl, _boundary_flux.
-NOT covered, and so not held to the contract by this file: the int32 body ids of fl_ibm_force, fl_ibm_rigid_pose, and the owner-rank marker
-calls fl_ibm_owned_select, fl_ibm_create_owned, fl_ibm_migrate, fl_ibm_owned_fetch.  The ids and the owner-rank calls' index arrays are
-integers, which the fp64 arena does not hold, and fl_ibm_rigid_pose has no stand-alone reference among the tests to take a tolerance from;
-their own tests use arrays of their own."""
+fl_layout_{from,to}_dmstag_{local,global}; fl_ibm_create, _update, _interp, _spread, _force (one body), _rigid_pose; fl_scalar_set_velocity, _rhs,
+_step, _stats, _cfl, _boundary_flux.
+NOT covered, and so not held to the contract by this file: the int32 body ids of fl_ibm_force and the owner-rank marker calls
+fl_ibm_owned_select, fl_ibm_create_owned, fl_ibm_migrate, fl_ibm_owned_fetch.  The ids and the owner-rank calls' index arrays are integers,
+which the fp64 arena does not hold; their own tests use arrays of their own.  The owner-rank calls are collective and wait by design: they are
+not run pending either (tests/stream_order.py).  Sequences of calls queued behind ONE delay: tests/test_gpu_stream_order.py."""
 import ctypes as C
 import math
+import time
 
 import numpy as np
 import pytest
@@ -45,6 +53,7 @@ from tests import scalar_cases as sc
 from tests import scalar_ranks as rk
 from tests import scalar_reference as sref
 from tests import step_rhs as sr
+from tests import stream_order as so
 from tests.caller_arrays import SENTINEL, SENTINEL_BITS, Arena
 from tests.gpu_common import CAVITY, CAVITY_BOX, O, PER, V, dev, make_pair, mean_free_rhs
 
@@ -119,16 +128,64 @@ def _dev(a):
     return torch.from_numpy(np.array(a, dtype=np.float64).reshape(-1)).to("cuda")
 
 
-def drive(label, spec, inputs, call, written, placements=ABD, partial=(), flips=(), verify=None, nx=None):
-    """call(T) on the ordinary arrays and in every placement (flips: further runs in A with these arrays 8 bytes off); T[name] is the array.
-    call returns further host results or None.  -> the results of every run, by run name"""
+class Pending(Ordinary):
+    """arrays of their own whose inputs are still to be PRODUCED when the call is made: every "in" / "inout" array starts as poison (NaN, or the valid
+    other input the case names for what becomes an index or a branch), produce() copies the true inputs in through staging tensors on the device -- in
+    stream order, behind the delay --, release(names) puts the poison back in stream order (the caller reuses its buffers), snapshot() clones the
+    results in stream order"""
+    placement = "pending"
+
+    def __init__(self, spec, inputs, poison):
+        self.spec = spec
+        self.src = {n: _dev(inputs[n]) for n, l, r in spec if r != "out"}
+        self.poison = {n: (_dev(poison[n]) if n in poison else torch.full((l,), float("nan"), dtype=torch.float64, device="cuda")) for n, l, r in spec if r != "out"}
+        for n, l, r in spec:
+            assert r == "out" or (self.poison[n].numel() == l and not torch.equal(self.poison[n], self.src[n]) or l == 0), (n, "the poison must differ from the input")
+        self.stage = {n: p.clone() for n, p in self.poison.items()}         # the staging tensors are themselves complete only behind the delay
+        self.t = {n: (torch.full((l,), SENTINEL, dtype=torch.float64, device="cuda") if r == "out" else self.poison[n].clone()) for n, l, r in spec}
+        self.snap = {}
+
+    def fill_staging(self):
+        for n, src in self.src.items():
+            self.stage[n].copy_(src)
+
+    def produce(self):
+        """the producer: the arrays from the staging tensors, which fill_staging() completed earlier on the SAME stream -- a producer that ran anywhere
+        else would hand on the staging tensors' poison"""
+        for n in self.src:
+            self.t[n].copy_(self.stage[n])
+
+    def release(self, *names):
+        for n in names:
+            self.t[n].copy_(self.poison[n])
+
+    def snapshot(self, names):
+        self.snap = {n: self.t[n].clone() for n in names}
+
+    def get(self, name):
+        return self.snap[name].cpu().numpy().copy()
+
+
+def drive(label, spec, inputs, call, written, placements=ABD, partial=(), flips=(), verify=None, nx=None, P=None, fns=(), poison=None, ranks=False):
+    """call(T) on the ordinary arrays, PENDING (below) and in every placement (flips: further runs in A with these arrays 8 bytes off); T[name] is
+    the array.  call returns further host results or None.  -> the results of every run, by run name.
+    P, fns: the handle whose stream the calls run on and the entry points call(T) makes (rows of tests/stream_order.py).  The pending run, on the same
+    handle right after the ordinary one (first-use allocations and tables exist): everything under torch.cuda.stream(P.stream); on that stream a
+    delay, an event, the copies that complete the staging tensors, the producer of every input (array <- staging tensor), then call(T); the moment it returns, has the delay ended? (it must not have where all of fns are
+    `async`: else the entry point waited, or the run proved nothing); then, in stream order, the results are cloned and every "in" array is poisoned
+    again.  A case that hands an array over and uses the handle later calls T.release(names) between the two (a no-op in every other run).  The
+    results must be finite and have the ordinary run's bits (tests/test_gpu_handle_history.py: a repeat on one handle is bitwise the same).
+    ranks: one rank of several -- the peers and a host-staged transport make a call wait, so the delay is not asserted."""
     for n, l, r in spec:
         assert r == "out" or np.asarray(inputs[n]).size == l, (label, n)
-    runs = [("ordinary", ())] + [(p, ()) for p in placements] + [("A", tuple(f)) for f in flips]
+    assert P is not None and fns and all(f in so.TABLE for f in fns), (label, fns)
+    runs = [("ordinary", ()), ("pending", ())] + [(p, ()) for p in placements] + [("A", tuple(f)) for f in flips]
     out, base = {}, None
     for placement, flip in runs:
         if placement == "ordinary":
             T = Ordinary(spec, inputs)
+        elif placement == "pending":
+            T = Pending(spec, inputs, poison or {})
         else:
             T = Arena(spec, placement, "cuda", flip=flip)
             for n, l, r in spec:
@@ -139,8 +196,30 @@ def drive(label, spec, inputs, call, written, placements=ABD, partial=(), flips=
         ph = {n: T.phase(n) for n, _, _ in spec}
         pairs = "" if nx is None else f", nx {'even' if nx % 2 == 0 else 'odd'}: 16-byte branch for {[n for n in ph if nx % 2 == 0 and ph[n] == 0]}"
         print(f"{label} [{tag}] phases {ph}{pairs}")
-        extra = call(T) or {}
-        if placement != "ordinary":
+        kind = "async" if so.all_async(fns) and not ranks else "waits"
+        if placement == "pending":
+            torch.cuda.synchronize()
+            with torch.cuda.stream(P.stream):               # the handle's own stream is the current one: _pre / _post order it against itself
+                e_delay = so.Delay.queue()
+                T.fill_staging()
+                T.produce()
+                t0 = time.perf_counter()
+                extra = call(T) or {}
+                ended = e_delay.query()
+                ms = (time.perf_counter() - t0) * 1e3
+                T.snapshot(written)
+                T.release(*[n for n, _, r in spec if r == "in"])
+            P.stream.synchronize()
+            print(f"{label} [{tag}] class {kind}: host time of call(T) {ms:.3f} ms, the delay had {'ENDED' if ended else 'not ended'} when it returned"
+                  + ("" if kind == "async" else " (not asserted)"))
+            assert kind != "async" or not ended, (label, fns, f"call(T) took {ms:.3f} ms on the host and returned after the {so.DELAY_MS} ms delay: an async entry point waited")
+        else:
+            if not hasattr(T, "release"):
+                T.release = lambda *names: None
+            t0 = time.perf_counter()
+            extra = call(T) or {}
+            print(f"{label} [{tag}] class {kind}: host time of call(T) {(time.perf_counter() - t0) * 1e3:.3f} ms")
+        if placement not in ("ordinary", "pending"):
             T.check(written=written, partial=partial)
         res = {n: T.get(n) for n in written}
         res.update(extra)
@@ -153,6 +232,7 @@ def drive(label, spec, inputs, call, written, placements=ABD, partial=(), flips=
                     assert not (bits(res[n]) == SENTINEL_BITS).any(), (label, n, "an output entry was not written")
             base = res
         if placement != "ordinary":
+            assert sorted(res) == sorted(base), (label, tag)
             differ = [k for k in base if not same_bits(res[k], base[k])]
             print(f"{label} [{tag}] the ordinary call's bits: {not differ}")
             assert not differ, (label, tag, differ, "differs from the ordinary call and placement A by bits", _first_diff(res[differ[0]], base[differ[0]]))
@@ -270,11 +350,12 @@ def test_apply_and_diagonal(ctx, gname):
 
     def verify(res, what):                                      # tests/test_gpu_poisson.py:39-41
         assert abs(res["y"] - ref).max() <= 1e-13 * scale, what
-    drive(f"{gname} fl_poisson_apply", [("x", N, "in"), ("y", N, "out")], {"x": x}, quiet(lambda T: P.apply(T["x"], T["y"])), ["y"], verify=verify, nx=c.n[0])
+    drive(f"{gname} fl_poisson_apply", [("x", N, "in"), ("y", N, "out")], {"x": x}, quiet(lambda T: P.apply(T["x"], T["y"])), ["y"], verify=verify, nx=c.n[0],
+          P=P, fns=["fl_poisson_apply"])
 
     def verify_d(res, what):                                    # tests/test_gpu_poisson.py:43
         assert np.allclose(res["d"], S.diag(), rtol=1e-14, atol=0), what
-    drive(f"{gname} fl_poisson_diagonal", [("d", N, "out")], {}, lambda T: raw(P, "fl_poisson_diagonal", P.h, ptr(T["d"])), ["d"], verify=verify_d, nx=c.n[0])
+    drive(f"{gname} fl_poisson_diagonal", [("d", N, "out")], {}, lambda T: raw(P, "fl_poisson_diagonal", P.h, ptr(T["d"])), ["d"], verify=verify_d, nx=c.n[0], P=P, fns=["fl_poisson_diagonal"])
 
 
 @GN
@@ -294,7 +375,7 @@ def test_rhs(ctx, gname, with_contrhs):
 
     def verify(res, what):
         assert abs(res["b"] - ref).max() <= bound, what
-    drive(f"{gname} fl_poisson_rhs", spec, dict(Vx=Vf[0], Vy=Vf[1], Vz=Vf[2], contrhs=cr), call, ["b"], verify=verify, nx=c.n[0])
+    drive(f"{gname} fl_poisson_rhs", spec, dict(Vx=Vf[0], Vy=Vf[1], Vz=Vf[2], contrhs=cr), call, ["b"], verify=verify, nx=c.n[0], P=P, fns=["fl_poisson_rhs"])
 
 
 # ------------------------------------------------------------------------------------------------------------------ the projection
@@ -346,7 +427,7 @@ def run_project(label, P, nx, spec, inputs, use, placements, flips, several, wan
     def verify(res, what):                                      # tests/test_gpu_poisson.py:66-73
         for n in use:
             assert abs(res[n] - want[n]).max() <= 1e-12 * max(1.0, abs(want[n]).max()), (what, n)
-    return drive(label, spec, inputs, call, sorted(use), placements=placements, flips=flips, verify=verify, nx=nx)
+    return drive(label, spec, inputs, call, sorted(use), placements=placements, flips=flips, verify=verify, nx=nx, P=P, fns=["fl_poisson_project"], ranks=several)
 
 
 def project_fields(g, seed=11):
@@ -433,7 +514,7 @@ def test_boundary_kernels(ctx, gname, b):
             rest[lay] = before[lay]
             assert same_bits(rest, before), what + " wrote outside its layer"
         drive(f"{gname} {fn} boundary {b}", [("plane", plane.size, "in"), ("target", m, "inout")], {"plane": plane, "target": before}, call,
-              ["target"], verify=verify, nx=n[0])
+              ["target"], verify=verify, nx=n[0], P=P, fns=[fn])
 
 
 @GN
@@ -448,13 +529,13 @@ def test_pressure_update(ctx, gname):
     def verify_first(res, what):
         assert same_bits(res["p"], 2.0 * dp + p0) and same_bits(res["phalf"], dp + p0), what
     drive(f"{gname} fl_pressure_update first", [("dp", N, "in"), ("p0", N, "in"), ("phalf", N, "out"), ("p", N, "out")], dict(dp=dp, p0=p0),
-          lambda T: P.pressure_update(True, T["dp"], T["p0"], T["phalf"], T["p"]), ["phalf", "p"], verify=verify_first, nx=c.n[0])
+          lambda T: P.pressure_update(True, T["dp"], T["p0"], T["phalf"], T["p"]), ["phalf", "p"], verify=verify_first, nx=c.n[0], P=P, fns=["fl_pressure_update"])
 
     def verify_later(res, what):
         sr.one_ulp_of_any(res["p"], [1.5 * dp + ph, sr.fused(1.5, dp, ph)], what)
         assert same_bits(res["phalf"], ph + dp), what
     drive(f"{gname} fl_pressure_update later", [("dp", N, "in"), ("phalf", N, "inout"), ("p", N, "out")], dict(dp=dp, phalf=ph),
-          lambda T: P.pressure_update(False, T["dp"], None, T["phalf"], T["p"]), ["phalf", "p"], verify=verify_later, nx=c.n[0])
+          lambda T: P.pressure_update(False, T["dp"], None, T["phalf"], T["p"]), ["phalf", "p"], verify=verify_later, nx=c.n[0], P=P, fns=["fl_pressure_update"])
 
 
 # ------------------------------------------------------------------------------------------------------------------ the Schur solves
@@ -584,7 +665,7 @@ def test_poisson_solve(ctx, gname, solver):
     def call(T):
         _, info = P.solve(T["b"], x=T["x"], history=True, **kw)
         return solve_extras(info)
-    drive(f"{gname} fl_poisson_solve {solver}", [("b", N, "in"), ("x", N, "out")], {"b": b}, call, ["x"], verify=verify, nx=c.n[0])
+    drive(f"{gname} fl_poisson_solve {solver}", [("b", N, "in"), ("x", N, "out")], {"b": b}, call, ["x"], verify=verify, nx=c.n[0], P=P, fns=["fl_poisson_solve"])
 
 
 # ------------------------------------------------------------------------------------------------------------------ the momentum block
@@ -599,7 +680,7 @@ def test_momentum_apply_diagonal_rowsum(ctx, gname):
     v = np.random.default_rng(11).standard_normal(3 * N)
     want = A.mult(v)
     drive(f"{gname} fl_momentum_apply", [("v", 3 * N, "in"), ("y", 3 * N, "out")], {"v": v}, quiet(lambda T: M.apply(T["v"], T["y"])), ["y"],
-          placements=ABCD, verify=lambda res, what: close(res["y"], want), nx=c.n[0])
+          placements=ABCD, verify=lambda res, what: close(res["y"], want), nx=c.n[0], P=c.P, fns=["fl_momentum_apply"])
     # the state itself on caller arrays: fl_momentum_set_state_v0 reads the three V0, the nine v0interp and v0
     V0, v0 = c._state[0], c._state[1]
     dt, rho, mu = c._state[2:5]
@@ -610,9 +691,11 @@ def test_momentum_apply_diagonal_rowsum(ctx, gname):
 
     def with_state(T):
         M.set_state(dt, rho, mu, [T[f"V0{d}"] for d in range(3)], [T[f"W{q}"] for q in range(9)], v0=T["v0"])
+        T.release(*[f"V0{d}" for d in range(3)], *[f"W{q}" for q in range(9)], "v0")         # copied: the caller reuses its buffers
         M.apply(T["v"], T["y"])
     try:
-        drive(f"{gname} fl_momentum_set_state_v0 + apply", spec, inputs, with_state, ["y"], verify=lambda res, what: close(res["y"], want), nx=c.n[0])
+        drive(f"{gname} fl_momentum_set_state_v0 + apply", spec, inputs, with_state, ["y"], verify=lambda res, what: close(res["y"], want), nx=c.n[0],
+              P=c.P, fns=["fl_momentum_set_state_v0", "fl_momentum_apply"])
     finally:
         c.cheb_state()                                          # the handle keeps no pointer into an arena that is gone
     A2, dt2, rho2, mu2 = c.abf_state()                          # the stored state: k_mom2 on every grid
@@ -623,18 +706,20 @@ def test_momentum_apply_diagonal_rowsum(ctx, gname):
 
     def with_stored_state(T):
         M.set_state(dt2, rho2, mu2, [T[f"V0{d}"] for d in range(3)], [T[f"W{q}"] for q in range(9)])
+        T.release(*[f"V0{d}" for d in range(3)], *[f"W{q}" for q in range(9)])
         M.apply(T["v"], T["y"])
     try:
-        drive(f"{gname} fl_momentum_set_state + apply", spec, inputs, with_stored_state, ["y"], verify=lambda res, what: close(res["y"], want2), nx=c.n[0])
+        drive(f"{gname} fl_momentum_set_state + apply", spec, inputs, with_stored_state, ["y"], verify=lambda res, what: close(res["y"], want2), nx=c.n[0],
+              P=c.P, fns=["fl_momentum_set_state", "fl_momentum_apply"])
     finally:
         c.abf_state()
     drive(f"{gname} fl_momentum_apply stored", [("v", 3 * N, "in"), ("y", 3 * N, "out")], {"v": v}, quiet(lambda T: M.apply(T["v"], T["y"])), ["y"],
-          placements=ABCD, verify=lambda res, what: close(res["y"], want2), nx=c.n[0])
+          placements=ABCD, verify=lambda res, what: close(res["y"], want2), nx=c.n[0], P=c.P, fns=["fl_momentum_apply"])
     drive(f"{gname} fl_momentum_diagonal", [("d", 3 * N, "out")], {}, lambda T: raw(c.P, "fl_momentum_diagonal", M.h, ptr(T["d"])), ["d"],
-          verify=lambda res, what: close(res["d"], A2.diag()), nx=c.n[0])
+          verify=lambda res, what: close(res["d"], A2.diag()), nx=c.n[0], P=c.P, fns=["fl_momentum_diagonal"])
     ones = A2.mult(np.ones(3 * N))
     drive(f"{gname} fl_momentum_rowsum", [("d", 3 * N, "out")], {}, lambda T: raw(c.P, "fl_momentum_rowsum", M.h, ptr(T["d"])), ["d"],
-          verify=lambda res, what: close(res["d"], ones), nx=c.n[0])
+          verify=lambda res, what: close(res["d"], ones), nx=c.n[0], P=c.P, fns=["fl_momentum_rowsum"])
 
 
 MOM_SOLVERS = ["bcgs", "gmres", "chebyshev", "chebyshev-guess"]
@@ -707,7 +792,7 @@ def test_momentum_solve(ctx, gname, solver):
     def call(T):
         _, info = M.solve(T["b"], x=T["x"], history=True, **kw)
         return solve_extras(info)
-    drive(f"{gname} fl_momentum_solve {solver}", spec, inputs, call, ["x"], verify=verify, nx=c.n[0])
+    drive(f"{gname} fl_momentum_solve {solver}", spec, inputs, call, ["x"], verify=verify, nx=c.n[0], P=c.P, fns=["fl_momentum_solve"])
 
 
 @GN
@@ -726,7 +811,7 @@ def test_face_interp_and_interp_faces(ctx, gname):
             close(res[f"V{d}"], want[d])
     drive(f"{gname} fl_momentum_face_interp", spec, {"v": v, **{f"rhs{d}": rhs[d] for d in range(3)}},
           lambda T: raw(P, "fl_momentum_face_interp", M.h, ptr(T["v"]), ptrs([T[f"rhs{d}"] for d in range(3)]), ptrs([T[f"V{d}"] for d in range(3)])),
-          [f"V{d}" for d in range(3)], verify=verify, nx=n[0])
+          [f"V{d}" for d in range(3)], verify=verify, nx=n[0], P=P, fns=["fl_momentum_face_interp"])
     # V_d = rhs_d + alpha (T v)_d with rhs aliasing V, as NSFormFunction calls it (tests/test_gpu_step_rhs.py:383-385)
     alpha, Tv = -1.0, g.apply_T(v)
     spec = [("v", 3 * N, "in")] + [(f"V{d}", g.nface[d], "inout") for d in range(3)]
@@ -739,7 +824,7 @@ def test_face_interp_and_interp_faces(ctx, gname):
         for d in range(3):
             close(res[f"V{d}"], rhs[d] + alpha * Tv[d])
     drive(f"{gname} fl_momentum_face_interp_scaled", spec, {"v": v, **{f"V{d}": rhs[d] for d in range(3)}}, scaled, [f"V{d}" for d in range(3)],
-          verify=verify_scaled, nx=n[0])
+          verify=verify_scaled, nx=n[0], P=P, fns=["fl_momentum_face_interp_scaled"])
     # cnl->v0interp = B v + vbc: nine face arrays, [c * 3 + d] = component c on the d-faces
     wantB = g.apply_B(v)
     vbc = [rng.standard_normal(g.nface[q % 3]) for q in range(9)]
@@ -750,7 +835,7 @@ def test_face_interp_and_interp_faces(ctx, gname):
             assert np.abs(res[f"W{q}"] - (wantB[q] + vbc[q])).max() <= 2e-13 * max(np.abs(v).max(), np.abs(vbc[q]).max()), (what, q)
     drive(f"{gname} fl_momentum_interp_faces", spec, {"v": v, **{f"vbc{q}": vbc[q] for q in range(9)}},
           quiet(lambda T: M.interp_faces(T["v"], [T[f"vbc{q}"] for q in range(9)], out=[T[f"W{q}"] for q in range(9)])),
-          [f"W{q}" for q in range(9)], verify=verify_B, nx=n[0])
+          [f"W{q}" for q in range(9)], verify=verify_B, nx=n[0], P=P, fns=["fl_momentum_interp_faces"])
     # ends only: the faces at the two ends of each axis are written; an inner entry keeps what it held or takes the value of the whole field
     junk = [rng.standard_normal(g.nface[q % 3]) for q in range(9)]
     spec = [("v", 3 * N, "in")] + [(f"vbc{q}", g.nface[q % 3], "in") for q in range(9)] + [(f"W{q}", g.nface[q % 3], "inout") for q in range(9)]
@@ -770,7 +855,7 @@ def test_face_interp_and_interp_faces(ctx, gname):
                     assert written[layer(shp, d, side)].all(), (what, q, side)
     drive(f"{gname} fl_momentum_interp_faces_ends", spec, {"v": v, **{f"vbc{q}": vbc[q] for q in range(9)}, **{f"W{q}": junk[q] for q in range(9)}},
           quiet(lambda T: M.interp_faces(T["v"], [T[f"vbc{q}"] for q in range(9)], ends_only=True, out=[T[f"W{q}"] for q in range(9)])),
-          [f"W{q}" for q in range(9)], verify=verify_ends, nx=n[0])
+          [f"W{q}" for q in range(9)], verify=verify_ends, nx=n[0], P=P, fns=["fl_momentum_interp_faces_ends"])
 
 
 @GN
@@ -788,7 +873,7 @@ def test_momentum_rhs_and_jacobian_mult(ctx, gname):
     scale = sr.momrhs_scale(so, v0, p, vbc)
     drive(f"{gname} fl_momentum_rhs", [("v0", 3 * N, "in"), ("p", N, "in"), ("vbc", 3 * N, "in"), ("out", 3 * N, "out")], dict(v0=v0, p=p, vbc=vbc),
           quiet(lambda T: M.rhs(dt_r, rho_r, mu_r, T["v0"], T["p"], T["vbc"], out=T["out"])), ["out"],
-          verify=lambda res, what: sr.within(res["out"], want, scale, 2e-13, what), nx=c.n[0])
+          verify=lambda res, what: sr.within(res["out"], want, scale, 2e-13, what), nx=c.n[0], P=P, fns=["fl_momentum_rhs"])
     # the block Jacobian (tests/test_gpu_momentum.py:319-330)
     rng = np.random.default_rng(41)
     v = rng.standard_normal(3 * N)
@@ -808,7 +893,7 @@ def test_momentum_rhs_and_jacobian_mult(ctx, gname):
     drive(f"{gname} fl_abf_jacobian_mult", spec, {"v": v, "p": p, **{f"V{d}": Vf[d] for d in range(3)}},
           lambda T: raw(P, "fl_abf_jacobian_mult", M.h, ptr(T["v"]), ptrs([T[f"V{d}"] for d in range(3)]), ptr(T["p"]), ptr(T["fv"]),
                         ptrs([T[f"fV{d}"] for d in range(3)]), ptr(T["fp"])),
-          ["fv", "fp"] + [f"fV{d}" for d in range(3)], verify=verify, nx=c.n[0])
+          ["fv", "fp"] + [f"fV{d}" for d in range(3)], verify=verify, nx=c.n[0], P=P, fns=["fl_abf_jacobian_mult"])
 
 
 @GN
@@ -828,7 +913,8 @@ def test_schur_apply(ctx, gname, kind):
         M.set_ainv_types(schur=fo.AINV_DIAG)
     try:
         drive(f"{gname} fl_abf_schur_apply {kind}", [("p", N, "in"), ("y", N, "out")], {"p": p},
-              lambda T: raw(P, "fl_abf_schur_apply", M.h, ptr(T["p"]), ptr(T["y"])), ["y"], verify=lambda res, what: close(res["y"], want, tol), nx=c.n[0])
+              lambda T: raw(P, "fl_abf_schur_apply", M.h, ptr(T["p"]), ptr(T["y"])), ["y"], verify=lambda res, what: close(res["y"], want, tol), nx=c.n[0],
+              P=P, fns=["fl_abf_schur_apply"])
     finally:
         M.set_ainv_types(schur=fo.AINV_ID)
 
@@ -890,7 +976,7 @@ def test_abf_apply(ctx, gname):
         for d in range(3):
             assert np.linalg.norm(res[f"V{d}"] - V_ref[d]) <= 1e-7 * max(np.linalg.norm(V_ref[d]), 1e-30), (what, d)
     drive(f"{gname} fl_abf_apply", spec, {"momrhs": momrhs, **{f"ir{d}": interprhs[d] for d in range(3)}}, call,
-          ["v", "p"] + [f"V{d}" for d in range(3)], verify=verify, nx=n[0])
+          ["v", "p"] + [f"V{d}" for d in range(3)], verify=verify, nx=n[0], P=P, fns=["fl_abf_apply"])
 
 
 @GN
@@ -905,7 +991,7 @@ def test_add_buoyancy(ctx, gname):
     spec = [("momrhs", 3 * N, "inout")] + [(f"phi{s}", N, "in") for s in range(3)]
     drive(f"{gname} fl_momentum_add_buoyancy", spec, {"momrhs": m, **{f"phi{s}": phis[s] for s in range(3)}},
           quiet(lambda T: M.add_buoyancy(T["momrhs"], [T[f"phi{s}"] for s in range(3)], accel, refs, DT)), ["momrhs"], placements=ABCD,
-          verify=lambda res, what: check(res["momrhs"], m, phis, accel, refs, DT, what), nx=c.n[0])
+          verify=lambda res, what: check(res["momrhs"], m, phis, accel, refs, DT, what), nx=c.n[0], P=c.P, fns=["fl_momentum_add_buoyancy"])
 
 
 # ------------------------------------------------------------------------------------------------------------------ BLAS-1
@@ -918,17 +1004,18 @@ def test_vec_lincomb(ctx, gname):
     rng = np.random.default_rng(m)
     x, z = rng.uniform(0.5, 1.5, m), rng.uniform(0.5, 1.5, m)
     lin = lambda a, xx, b, zz, yy: raw(P, "fl_vec_lincomb", P.h, m, a, ptr(xx), b, ptr(zz), ptr(yy))
+    LC = dict(P=P, fns=["fl_vec_lincomb"])
     for a, b in ((-1.0, 1.0), (2.0, -1.0)):     # exact products: one rounding, fused or not
         drive(f"{gname} fl_vec_lincomb {a} {b}", [("x", m, "in"), ("z", m, "in"), ("y", m, "out")], dict(x=x, z=z), lambda T: lin(a, T["x"], b, T["z"], T["y"]),
-              ["y"], placements=ABCD, verify=lambda res, what: same_bits(res["y"], a * x + b * z) or pytest.fail(what), nx=c.n[0])
+              ["y"], placements=ABCD, verify=lambda res, what: same_bits(res["y"], a * x + b * z) or pytest.fail(what), nx=c.n[0], **LC)
     a, b = 1.7, 0.6
     cands = [a * x + b * z, sr.fused(a, x, b * z), sr.fused(b, z, a * x)]
     drive(f"{gname} fl_vec_lincomb general", [("x", m, "in"), ("z", m, "in"), ("y", m, "out")], dict(x=x, z=z), lambda T: lin(a, T["x"], b, T["z"], T["y"]),
-          ["y"], placements=ABCD, verify=lambda res, what: sr.one_ulp_of_any(res["y"], cands, what), nx=c.n[0])
+          ["y"], placements=ABCD, verify=lambda res, what: sr.one_ulp_of_any(res["y"], cands, what), nx=c.n[0], **LC)
     drive(f"{gname} fl_vec_lincomb y = x", [("x", m, "inout"), ("z", m, "in")], dict(x=x, z=z), lambda T: lin(a, T["x"], b, T["z"], T["x"]),
-          ["x"], placements=ABCD, verify=lambda res, what: sr.one_ulp_of_any(res["x"], cands, what), nx=c.n[0])
+          ["x"], placements=ABCD, verify=lambda res, what: sr.one_ulp_of_any(res["x"], cands, what), nx=c.n[0], **LC)
     drive(f"{gname} fl_vec_lincomb y = z", [("x", m, "in"), ("z", m, "inout")], dict(x=x, z=z), lambda T: lin(a, T["x"], b, T["z"], T["z"]),
-          ["z"], placements=ABCD, verify=lambda res, what: sr.one_ulp_of_any(res["z"], cands, what), nx=c.n[0])
+          ["z"], placements=ABCD, verify=lambda res, what: sr.one_ulp_of_any(res["z"], cands, what), nx=c.n[0], **LC)
 
 
 @GN
@@ -946,7 +1033,7 @@ def test_vec_dot_mdot_maxpy(ctx, gname):
         raw(P, "fl_vec_dot", P.h, m, ptr(T["x"]), ptr(T["y"]), C.byref(out))
         return {"dot": out.value}
     drive(f"{gname} fl_vec_dot", [("x", m, "in"), ("y", m, "in")], dict(x=x, y=y), dot, [],
-          verify=lambda res, what: abs(res["dot"] - exact) <= bound or pytest.fail(f"{what}: {res['dot']!r} {exact!r}"), nx=c.n[0])
+          verify=lambda res, what: abs(res["dot"] - exact) <= bound or pytest.fail(f"{what}: {res['dot']!r} {exact!r}"), nx=c.n[0], P=P, fns=["fl_vec_dot"])
     Y = rng.standard_normal((k, m))
     spec = [("x", m, "inout")] + [(f"Y{j}", m, "in") for j in range(k)]
     inputs = {"x": x, **{f"Y{j}": Y[j] for j in range(k)}}
@@ -956,11 +1043,12 @@ def test_vec_dot_mdot_maxpy(ctx, gname):
         raw(P, "fl_vec_mdot", P.h, m, ptr(T["x"]), ptrs([T[f"Y{j}"] for j in range(k)]), k, out)
         return {"mdot": np.array(out[:])}
     drive(f"{gname} fl_vec_mdot", spec, inputs, mdot, [],       # tests/test_gpu_momentum.py:498
-          verify=lambda res, what: np.allclose(res["mdot"], Y @ x, rtol=1e-12, atol=1e-12) or pytest.fail(what), nx=c.n[0])
+          verify=lambda res, what: np.allclose(res["mdot"], Y @ x, rtol=1e-12, atol=1e-12) or pytest.fail(what), nx=c.n[0], P=P, fns=["fl_vec_mdot"])
     a = rng.standard_normal(k)
     drive(f"{gname} fl_vec_maxpy", spec, inputs,
           lambda T: raw(P, "fl_vec_maxpy", P.h, m, ptr(T["x"]), (C.c_double * k)(*a), ptrs([T[f"Y{j}"] for j in range(k)]), k), ["x"],
-          verify=lambda res, what: np.allclose(res["x"], x + a @ Y, rtol=1e-13, atol=1e-13) or pytest.fail(what), nx=c.n[0])     # :502
+          verify=lambda res, what: np.allclose(res["x"], x + a @ Y, rtol=1e-13, atol=1e-13) or pytest.fail(what), nx=c.n[0],
+          P=P, fns=["fl_vec_maxpy"])     # :502
 
 
 # ------------------------------------------------------------------------------------------------------------------ layout conversions
@@ -992,13 +1080,13 @@ def test_layout_conversions(ctx, gname):
         want[index] = glob[where]
         drive(f"{gname} fl_layout_from_dmstag_global {what} {comp}", [("glob", glob.size, "in"), ("out", m, "out")], {"glob": glob},
               lambda T: raw(P, "fl_layout_from_dmstag_global", P.h, dofc, what, comp, ptr(T["glob"]), ptr(T["out"])), ["out"],
-              verify=lambda res, tag: same_bits(res["out"], want) or pytest.fail(tag), nx=n[0])
+              verify=lambda res, tag: same_bits(res["out"], want) or pytest.fail(tag), nx=n[0], P=P, fns=["fl_layout_from_dmstag_global"])
         arr = rng.standard_normal(m)
         back = glob.copy()
         back[where] = arr[index]
         drive(f"{gname} fl_layout_to_dmstag_global {what} {comp}", [("arr", m, "in"), ("glob", glob.size, "inout")], {"arr": arr, "glob": glob},
               lambda T: raw(P, "fl_layout_to_dmstag_global", P.h, dofc, what, comp, ptr(T["arr"]), ptr(T["glob"])), ["glob"],
-              verify=lambda res, tag: same_bits(res["glob"], back) or pytest.fail(tag), nx=n[0])
+              verify=lambda res, tag: same_bits(res["glob"], back) or pytest.fail(tag), nx=n[0], P=P, fns=["fl_layout_to_dmstag_global"])
     # DMStagVecGetArray's ghosted box (tests/test_gpu_layout.py:132-163): ten slots per element
     per = [c.bc[2 * d] == PER for d in range(3)]
     gstart = [-1 if per[d] else 0 for d in range(3)]
@@ -1016,13 +1104,13 @@ def test_layout_conversions(ctx, gname):
         want = loc[box].ravel()
         drive(f"{gname} fl_layout_from_dmstag_local {what} {slot}", [("loc", loc.size, "in"), ("out", m, "out")], {"loc": loc},
               lambda T: raw(P, "fl_layout_from_dmstag_local", P.h, C.byref(D), what, slot, ptr(T["loc"]), ptr(T["out"])), ["out"],
-              verify=lambda res, tag: same_bits(res["out"], want) or pytest.fail(tag), nx=n[0])
+              verify=lambda res, tag: same_bits(res["out"], want) or pytest.fail(tag), nx=n[0], P=P, fns=["fl_layout_from_dmstag_local"])
         arr = rng.standard_normal(m)
         back = loc.copy()
         back[box] = arr.reshape(back[box].shape)
         drive(f"{gname} fl_layout_to_dmstag_local {what} {slot}", [("arr", m, "in"), ("loc", loc.size, "inout")], {"arr": arr, "loc": loc},
               lambda T: raw(P, "fl_layout_to_dmstag_local", P.h, C.byref(D), what, slot, ptr(T["arr"]), ptr(T["loc"])), ["loc"],
-              verify=lambda res, tag: same_bits(res["loc"], back.ravel()) or pytest.fail(tag), nx=n[0])
+              verify=lambda res, tag: same_bits(res["loc"], back.ravel()) or pytest.fail(tag), nx=n[0], P=P, fns=["fl_layout_to_dmstag_local"])
 
 
 # ------------------------------------------------------------------------------------------------------------------ immersed boundary
@@ -1064,12 +1152,18 @@ def test_ibm(gname, kind):
     spec = ([(f"first{d}", L, "in") for d in range(3)] + [("X0", L, "in"), ("X1", L, "in"), ("X2", L, "in"), ("u", 3 * N, "in"), ("U", 3 * L, "out"),
             ("F", 3 * L, "in"), ("dV", L, "in"), ("f", 3 * N, "inout")])
     inputs = dict(first0=first[0], first1=first[1], first2=first[2], X0=X[0], X1=X[1], X2=X[2], u=u, F=F, dV=dV, f=f0)
+    # what a marker position holds while its producer is pending, and again once the set has copied it: OTHER markers inside the box, never a NaN (a
+    # position becomes a cell index: misordering must show as wrong bits, not as a fault)
+    other = [rng.uniform(0.05, 0.95, L) for _ in range(6)]
+    poison = dict(first0=other[0], first1=other[1], first2=other[2], X0=other[3], X1=other[4], X2=other[5])
 
     def call(T):
         h = C.c_void_p()
         raw(P, "fl_ibm_create", P.h, kind, L, ptr(T["first0"]), ptr(T["first1"]), ptr(T["first2"]), C.byref(h))
+        T.release("first0", "first1", "first2")                 # copied into the set
         try:
             raw(P, "fl_ibm_update", h, ptr(T["X0"]), ptr(T["X1"]), ptr(T["X2"]))
+            T.release("X0", "X1", "X2")
             raw(P, "fl_ibm_interp", h, 3, ptr(T["u"]), ptr(T["U"]))
             raw(P, "fl_ibm_spread", h, 3, ptr(T["F"]), ptr(T["dV"]), ptr(T["f"]))
             ab, force, torque = (C.c_double * 3)(*about), (C.c_double * 3)(), (C.c_double * 3)()
@@ -1085,9 +1179,52 @@ def test_ibm(gname, kind):
         assert fr.within(ref, "force", res["force"]) <= 1.0 and fr.within(ref, "torque", res["torque"]) <= 1.0, what
         assert np.array_equal(res["force"], ref["force"][0]) and np.array_equal(res["torque"], ref["torque"][0]), what
     try:
-        drive(f"{gname} fl_ibm_create / update / interp / spread / force kind {kind}", spec, inputs, call, ["U", "f"], verify=verify, nx=n[0])
+        drive(f"{gname} fl_ibm_create / update / interp / spread / force kind {kind}", spec, inputs, call, ["U", "f"], verify=verify, nx=n[0], P=P,
+              fns=["fl_ibm_create", "fl_ibm_update", "fl_ibm_interp", "fl_ibm_spread", "fl_ibm_force", "fl_poisson_synchronize", "fl_ibm_destroy"], poison=poison)
     finally:
         P.close()
+
+
+@pytest.mark.parametrize("angle", [0.0, 1e-9, math.pi / 2, 3.0], ids=["0", "1e-9", "pi/2", "3"])
+def test_ibm_rigid_pose(ctx, angle):
+    """fl_ibm_rigid_pose on 301 markers (two blocks of 256, the second partial): positions and target velocities against Rodrigues' rotation and
+    velocity + omega x r in long double (tests/ibm_reference.py::rigid_pose), per entry within the bound that function derives from the operation
+    count; the call with the velocities alone (X, Y, Z absent) and with the positions alone gives the same bits."""
+    from tests import ibm_reference as ir
+    P = ctx("G2").P
+    L = 301
+    rng = np.random.default_rng(77)
+    X0 = rng.uniform(0.1, 0.9, (3, L))
+    axis = np.array([2.0, -1.0, 2.0]) / 3.0
+    c0, c, vel, om = [0.5, 0.4375, 0.25], [0.53, 0.41, 0.27], [0.3, -0.2, 0.1], [1.5, -2.0, 0.75]
+    rotvec = axis * angle
+    wX, wU, bX, bU = ir.rigid_pose(X0, c0, c, rotvec, vel, om)
+    vec = lambda a: (C.c_double * 3)(*a)
+    spec = [("X0", L, "in"), ("Y0", L, "in"), ("Z0", L, "in"), ("X", L, "out"), ("Y", L, "out"), ("Z", L, "out"), ("Ut", 3 * L, "out")]
+    inputs = dict(X0=X0[0], Y0=X0[1], Z0=X0[2])
+
+    def pose(T, xyz=True, ut=True):
+        raw(P, "fl_ibm_rigid_pose", P.h, L, ptr(T["X0"]), ptr(T["Y0"]), ptr(T["Z0"]), vec(c0), vec(c), vec(rotvec), vec(vel), vec(om),
+            *[ptr(T[n]) if xyz else None for n in "XYZ"], ptr(T["Ut"]) if ut else None)
+
+    def verify(res, what):
+        if "X" in res:
+            got = np.stack([res[n] for n in "XYZ"])
+            q = ir.rigid_pose_within(got, wX, bX)
+            print(f"{what}: positions, largest error / bound = {q:.3f}")
+            assert q <= 1.0, (what, q)
+            if angle == 0.0:
+                assert float(np.abs(got - (X0 + (np.array(c) - np.array(c0))[:, None])).max()) <= 4 * 2.0 ** -53, what
+        if "Ut" in res:
+            q = ir.rigid_pose_within(res["Ut"].reshape(3, L), wU, bU)
+            print(f"{what}: velocities, largest error / bound = {q:.3f}")
+            assert q <= 1.0, (what, q)
+    fns = ["fl_ibm_rigid_pose"]
+    both = drive(f"fl_ibm_rigid_pose angle {angle}", spec, inputs, quiet(pose), ["X", "Y", "Z", "Ut"], verify=verify, nx=L, P=P, fns=fns)
+    only_u = drive(f"fl_ibm_rigid_pose angle {angle}, velocities alone", spec, inputs, quiet(lambda T: pose(T, xyz=False)), ["Ut"], verify=verify, nx=L, P=P, fns=fns)
+    only_x = drive(f"fl_ibm_rigid_pose angle {angle}, positions alone", spec, inputs, quiet(lambda T: pose(T, ut=False)), ["X", "Y", "Z"], verify=verify, nx=L, P=P, fns=fns)
+    for tag in both:
+        assert same_bits(only_u[tag]["Ut"], both[tag]["Ut"]) and all(same_bits(only_x[tag][n], both[tag][n]) for n in "XYZ"), tag
 
 
 # ------------------------------------------------------------------------------------------------------------------ the passive scalar
@@ -1143,7 +1280,8 @@ def test_scalar(gname):
             assert abs(got - w) <= ops * sref.U * abs(w) * (1 + 2.0 ** -10), (what, got, w)
         check_flux(res["flux"], Pr, phi, V, what)               # tests/test_gpu_scalar_flux.py:52-62
     try:
-        drive(f"{gname} fl_scalar_rhs / stats / cfl / boundary_flux", base + [("R", N, "out")], inputs, rhs, ["R"], verify=verify, nx=n[0])
+        drive(f"{gname} fl_scalar_rhs / stats / cfl / boundary_flux", base + [("R", N, "out")], inputs, rhs, ["R"], verify=verify, nx=n[0], P=Pz,
+              fns=["fl_scalar_set_velocity", "fl_scalar_rhs", "fl_scalar_stats", "fl_scalar_cfl", "fl_scalar_boundary_flux"])
         spec = [("Vx", nfs[0], "in"), ("Vy", nfs[1], "in"), ("Vz", nfs[2], "in"), ("phi", N, "inout"), ("q", N, "in")]
 
         def step(T):
@@ -1155,7 +1293,13 @@ def test_scalar(gname):
             err = np.abs(got.astype(np.longdouble) - wantS).astype(np.float64)
             assert (err <= tolS).all(), (what, float((err / tolS).max()))
             assert float(np.abs(got - phi).max()) > 1e-3, what
-        drive(f"{gname} fl_scalar_step", spec, inputs, step, ["phi"], verify=verify_step, nx=n[0])
+        drive(f"{gname} fl_scalar_step", spec, inputs, step, ["phi"], verify=verify_step, nx=n[0], P=Pz, fns=["fl_scalar_set_velocity", "fl_scalar_step"])
+
+        def rhs_alone(T):                                       # the launches alone: nothing in the case waits
+            velocity(T)
+            S.rhs(T["phi"], T["q"], out=T["R"])
+        drive(f"{gname} fl_scalar_rhs alone", base + [("R", N, "out")], inputs, rhs_alone, ["R"], placements=("A",), nx=n[0], P=Pz,
+              fns=["fl_scalar_set_velocity", "fl_scalar_rhs"])
     finally:
         S.close()
         Pz.close()
@@ -1200,7 +1344,7 @@ def _rank_flow_worker(R, case, ref):
         def call(T):
             _, info = P.solve(T["b"], x=T["x"], history=True, **ref["kw"])
             return solve_extras(info)
-        runs = drive(f"G2 {case.ranks} rank {R.rank} fl_poisson_solve", [("b", N, "in"), ("x", N, "out")], {"b": b}, call, ["x"], nx=nx)
+        runs = drive(f"G2 {case.ranks} rank {R.rank} fl_poisson_solve", [("b", N, "in"), ("x", N, "out")], {"b": b}, call, ["x"], nx=nx, P=P, fns=["fl_poisson_solve"], ranks=True)
     P.close()
     return {"solve": runs, "paths": seen}
 
@@ -1258,7 +1402,8 @@ def _rank_scalar_worker(R, case, blocks):
             S.set_velocity(T["Vx"], T["Vy"], T["Vz"])
             S.rhs(T["phi"], T["q"], out=T["R"])
             s.synchronize()
-        runs = drive(f"G2 {case.ranks} rank {R.rank} fl_scalar_rhs", spec, dict(Vx=Vb[0], Vy=Vb[1], Vz=Vb[2], phi=phi, q=q), call, ["R"], nx=int(d.len[0]))
+        runs = drive(f"G2 {case.ranks} rank {R.rank} fl_scalar_rhs", spec, dict(Vx=Vb[0], Vy=Vb[1], Vz=Vb[2], phi=phi, q=q), call, ["R"], nx=int(d.len[0]),
+                     P=P, fns=["fl_scalar_set_velocity", "fl_scalar_rhs"], ranks=True)
         S.close()
     P.close()
     return {tag: res["R"] for tag, res in runs.items()}

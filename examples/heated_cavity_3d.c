@@ -4,6 +4,8 @@
  * a scalar of NSAddScalar made active by NSSetScalarBuoyancy; the heat flux through the hot wall comes from NSGetScalarBoundaryFlux.
  * In units of the box width, the temperature difference and the free-fall velocity sqrt(g beta dT L):  nu = sqrt(Pr / Ra), alpha = 1 / sqrt(Ra Pr),
  * g beta = 1, and the Nusselt number of a wall is its total flux (convective + diffusive, along +x) over alpha x wall area.
+ * -implicit: the temperature's diffusion by backward Euler (NSSetScalarImplicit, theta = 1), a fixed number of Chebyshev launches per step that is printed
+ * beside the Courant numbers: the diffusive one then no longer limits the step (try -cart_grid_x 128 -cart_grid_y 128 with and without it).
  * A demonstration, not a test: no number printed here is asserted anywhere.  One rank.
  *
  *   gcc -O2 examples/heated_cavity_3d.c -Iinclude -Lfluca_amd/lib -lfluca_host -lflucahip -lm -Wl,-rpath,$PWD/fluca_amd/lib
@@ -39,6 +41,9 @@ int main(int argc, char **argv)
   NS      ns;
   double  Ra = 1e5, Pr = 0.71;
   int64_t maxsteps = 50, step = 0;
+  int     implicit = 0;
+  for (int a = 1; a < argc; ++a)
+    if (!strcmp(argv[a], "-implicit")) implicit = 1;
   for (int a = 1; a + 1 < argc; ++a) {
     if (!strcmp(argv[a], "-Ra")) Ra = atof(argv[a + 1]);
     if (!strcmp(argv[a], "-Pr")) Pr = atof(argv[a + 1]);
@@ -77,6 +82,7 @@ int main(int argc, char **argv)
   CHK(NSSetScalarBoundaryCondition(ns, T, 0, 0, 1.));
   CHK(NSSetScalarBoundaryCondition(ns, T, 1, 0, 0.));
   CHK(NSSetScalarBuoyancy(ns, T, 1., 0.5));
+  if (implicit) CHK(NSSetScalarImplicit(ns, T, 1., 1e-6));
   CHK(NSGetScalarArray(ns, T, &T_dev));
   {
     /* the conduction profile: the flow starts from rest and the walls' fluxes start at alpha x area (Nu = 1) */
@@ -104,8 +110,13 @@ int main(int argc, char **argv)
     CHK(NSGetScalarBoundaryFlux(ns, T, flux));
     CHK(NSGetScalarCFL(ns, T, cfl));
     /* both along +x: heat enters through the hot wall (boundary 0) and leaves through the cold one (boundary 1) */
-    printf("%lld NS time %g  outer its %d  Nu hot wall %.6f  Nu cold wall %.6f  scalar CFL %.3f / %.3f\n", (long long)step, t, its, (flux[0] + flux[1]) / (alpha * Lz),
+    int    cheb = 0;
+    double bound = 1.;
+    CHK(NSGetScalarImplicitInfo(ns, T, &cheb, &bound));
+    printf("%lld NS time %g  outer its %d  Nu hot wall %.6f  Nu cold wall %.6f  scalar CFL %.3f / %.3f", (long long)step, t, its, (flux[0] + flux[1]) / (alpha * Lz),
            (flux[2] + flux[3]) / (alpha * Lz), cfl[0], cfl[1]);
+    if (implicit) printf("  Chebyshev steps %d (error bound %.1e)", cheb, bound);
+    printf("\n");
   }
   CHK(MeshDestroy(&mesh));
   CHK(NSDestroy(&ns));

@@ -75,6 +75,10 @@ class fl_dmstag_local(C.Structure):
     _fields_ = [("gstart", C.c_int64 * 3), ("gsize", C.c_int64 * 3), ("start", C.c_int64 * 3), ("entries", C.c_int)]
 
 
+class fl_scalar_cheb_info(C.Structure):
+    _fields_ = [("steps", C.c_int), ("capped", C.c_int), ("emin", C.c_double), ("emax", C.c_double), ("bound", C.c_double)]
+
+
 class fl_halo_msg(C.Structure):
     _fields_ = [("peer", C.c_int), ("send_boundary", C.c_int), ("recv_boundary", C.c_int), ("sendtag", C.c_int), ("recvtag", C.c_int)]
 
@@ -188,7 +192,15 @@ PROTOTYPES = {
     "fl_scalar_stats": (C.c_int, [_P, _P, C.POINTER(C.c_double)]),
     "fl_scalar_boundary_flux": (C.c_int, [_P, _P, C.POINTER(C.c_double)]),
 }
-for _name, (_res, _args) in PROTOTYPES.items():
+# every symbol include/fluca_hip_implicit.h declares (tests/test_scalar_implicit_host.py checks that header against this table)
+PROTOTYPES_IMPLICIT = {
+    "fl_scalar_cheb_steps": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "fl_scalar_diffusion_interval": (C.c_int, [_P, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "fl_scalar_diffusion_apply": (C.c_int, [_P, C.c_double, _P, _P]),
+    "fl_scalar_diffusion_solve": (C.c_int, [_P, C.c_double, C.c_double, C.c_int, _P, _P, C.POINTER(fl_scalar_cheb_info)]),
+    "fl_scalar_step_imex": (C.c_int, [_P, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, _P, _P, C.POINTER(fl_scalar_cheb_info)]),
+}
+for _name, (_res, _args) in list(PROTOTYPES.items()) + list(PROTOTYPES_IMPLICIT.items()):
     _f = getattr(lib, _name)  # AttributeError if the library lacks a declared symbol
     _f.restype = _res
     _f.argtypes = _args

@@ -21,31 +21,9 @@
 #include "fl_device.h"
 #include "fl_handle.h"
 #include "fl_limiter.h"
+#include "fl_scalar_handle.h"
 
 namespace fl {
-
-struct ScGrid {
-  int           nx, ny, nz, per;  // per: bit d = axis d is periodic
-  int           kind[6];          // per boundary: 0 Dirichlet, 1 Neumann (derivative along +axis), 2 periodic
-  double        val[6];
-  double        dlo[3], dhi[3];   // distance first centre -- low boundary face, high boundary face -- last centre
-  double        gamma;
-  const ScCell *c[3];
-};
-
-// w at cell m of a line of n cells (c0: index of its cell 0, cs: stride): outside the line the periodic image, or -- at a boundary -- the
-// nearest cell (a placeholder that keeps the address legal; sc_axis replaces what the boundary rule defines and never uses the rest)
-__device__ __forceinline__ double sc_ld(const double *__restrict__ w, int64_t c0, int64_t cs, int m, int n, bool wraps)
-{
-  if (m < 0) {
-    m = wraps ? m + n : 0;
-    if (m < 0) m += n;  // (n == 1)
-  } else if (m >= n) {
-    m = wraps ? m - n : n - 1;
-    if (m >= n) m -= n;
-  }
-  return w[c0 + m * cs];
-}
 
 // phi_f = phi_u + alpha psi(r) (phi_d - phi_u), r = g_u / g_c guarded as in the reference
 template <int L>
@@ -487,23 +465,6 @@ extern "C" int fl_limiter_eval(int limiter, double r, double *psi)
 
 // ------------------------------------------------------------------------------------------------ the handle
 
-struct fl_scalar {
-  fl_poisson   *h = nullptr;  // borrowed: grid, device, stream
-  ScGrid        g;
-  int           limiter = LIM_SUPERBEE;
-  const double *V[3] = {nullptr, nullptr, nullptr};  // borrowed
-  void         *tab[3] = {nullptr, nullptr, nullptr};
-  double       *hw[3] = {nullptr, nullptr, nullptr};  // face-to-face widths
-  double       *work[2] = {nullptr, nullptr};         // the two stage vectors of fl_scalar_step
-  double       *partial = nullptr;                    // 3 * SC_REDUCE_BLOCKS
-  std::vector<double> partial_host;
-  const double *hwl[3] = {nullptr, nullptr, nullptr};  // hw cut to the rank's cells
-  // one rank's block of several (fl_scalar_create_ranks): nb as k_scalar_stage_ring takes it; the layers received and sent (ScRing)
-  bool    ring = false;
-  int     nb = 0;
-  double *slab_recv = nullptr, *slab_send = nullptr;
-};
-
 constexpr int SC_REDUCE_BLOCKS = 1024;
 
 // The launch of k_scalar_stage: the XCD band plan of k_schur_var with this kernel's residency (sc_minblocks blocks on each of an XCD's 32 CUs).
@@ -640,7 +601,7 @@ extern "C" int fl_scalar_destroy(fl_scalar *m)
     if (m->tab[d]) (void)hipFree(m->tab[d]);
     if (m->hw[d]) (void)hipFree(m->hw[d]);
   }
-  for (double *p : {m->work[0], m->work[1], m->partial})
+  for (double *p : {m->work[0], m->work[1], m->partial, m->imex_b})
     if (p) (void)hipFree(p);
   for (double *p : {m->slab_recv, m->slab_send})
     if (p) (void)hipFree(p);
@@ -818,12 +779,10 @@ extern "C" int fldbg_scalar_stage_only(fl_scalar *m, const double *phi_dev, cons
 }
 
 // w <- phi; s - 1 times w <- w + dt / (s - 1) R(w); phi <- ((s - 1) w + phi + dt R(w)) / s.  One launch per stage; the stage vectors alternate between
-// the handle's two work arrays, and the last stage writes phi in place (it reads of phi only the cell it writes).
-extern "C" int fl_scalar_step(fl_scalar *m, double dt, int nstages, const double *source_dev, double *phi_dev)
+// the handle's two work arrays, and the last stage writes phi in place (it reads of phi only the cell it writes) -- or, for fl_scalar_step_imex, into
+// an array of the handle's.
+int fl::scalar_ssp_step(fl_scalar *m, double dt, int nstages, const double *source_dev, const double *phi_dev, double *out_dev)
 {
-  if (!m || !phi_dev) return FL_ERR_ARG_NULL;
-  if (nstages < 2 || !std::isfinite(dt)) return FL_ERR_ARG_OUTOFRANGE;
-  if (!m->V[0]) return FL_ERR_ARG_WRONGSTATE;
   FL_HIP(hipSetDevice(m->h->device));
   for (int a = 0; a < (nstages > 2 ? 2 : 1); ++a)
     if (!m->work[a]) FL_HIP(hipMalloc((void **)&m->work[a], sizeof(double) * (size_t)m->h->ncell));
@@ -840,9 +799,17 @@ extern "C" int fl_scalar_step(fl_scalar *m, double dt, int nstages, const double
     if (m->ring) FL_CHK(ring_exchange(m));
     w = o;
   }
-  STAGE[m->limiter](m, StageArgs{1. / s, (s - 1.) / s, dt / s, phi_dev, w, source_dev, phi_dev, false});
+  STAGE[m->limiter](m, StageArgs{1. / s, (s - 1.) / s, dt / s, phi_dev, w, source_dev, out_dev, false});
   FL_HIP(hipGetLastError());
   return FL_SUCCESS;
+}
+
+extern "C" int fl_scalar_step(fl_scalar *m, double dt, int nstages, const double *source_dev, double *phi_dev)
+{
+  if (!m || !phi_dev) return FL_ERR_ARG_NULL;
+  if (nstages < 2 || !std::isfinite(dt)) return FL_ERR_ARG_OUTOFRANGE;
+  if (!m->V[0]) return FL_ERR_ARG_WRONGSTATE;
+  return scalar_ssp_step(m, dt, nstages, source_dev, phi_dev, phi_dev);
 }
 
 extern "C" int fl_scalar_cfl(fl_scalar *m, double dt, double out[2])

@@ -1,0 +1,62 @@
+// fl_scalar_handle.h -- the fl_scalar handle and what the kernels of fl_scalar.hip and fl_scalar_implicit.hip share: the grid as a kernel sees it and
+// the read of a cell of the caller's unpadded array.
+#pragma once
+#include "fl_handle.h"
+#include "fl_limiter.h"
+
+namespace fl {
+
+struct ScGrid {
+  int           nx, ny, nz, per;  // per: bit d = axis d is periodic
+  int           kind[6];          // per boundary: 0 Dirichlet, 1 Neumann (derivative along +axis), 2 periodic
+  double        val[6];
+  double        dlo[3], dhi[3];   // distance first centre -- low boundary face, high boundary face -- last centre
+  double        gamma;
+  const ScCell *c[3];
+};
+
+// w at cell m of a line of n cells (c0: index of its cell 0, cs: stride): outside the line the periodic image, or -- at a boundary -- the
+// nearest cell (a placeholder that keeps the address legal; sc_axis replaces what the boundary rule defines and never uses the rest)
+__device__ __forceinline__ double sc_ld(const double *__restrict__ w, int64_t c0, int64_t cs, int m, int n, bool wraps)
+{
+  if (m < 0) {
+    m = wraps ? m + n : 0;
+    if (m < 0) m += n;  // (n == 1)
+  } else if (m >= n) {
+    m = wraps ? m - n : n - 1;
+    if (m >= n) m -= n;
+  }
+  return w[c0 + m * cs];
+}
+
+}  // namespace fl
+
+struct fl_scalar {
+  fl_poisson   *h = nullptr;  // borrowed: grid, device, stream
+  fl::ScGrid    g;
+  int           limiter = fl::LIM_SUPERBEE;
+  const double *V[3] = {nullptr, nullptr, nullptr};  // borrowed
+  void         *tab[3] = {nullptr, nullptr, nullptr};
+  double       *hw[3] = {nullptr, nullptr, nullptr};  // face-to-face widths
+  double       *work[2] = {nullptr, nullptr};         // the two stage vectors of fl_scalar_step
+  double       *partial = nullptr;                    // 3 * SC_REDUCE_BLOCKS
+  std::vector<double> partial_host;
+  const double *hwl[3] = {nullptr, nullptr, nullptr};  // hw cut to the rank's cells
+  // one rank's block of several (fl_scalar_create_ranks): nb as k_scalar_stage_ring takes it; the layers received and sent (ScRing)
+  bool    ring = false;
+  int     nb = 0;
+  double *slab_recv = nullptr, *slab_send = nullptr;
+  // the implicit path (fl_scalar_implicit.hip), made on first use: the right-hand side of fl_scalar_step_imex (its second array beside work[]: the
+  // Chebyshev direction and the other iterate live in work[0], work[1], which the explicit stages have left by then); max_i omega_d(i) per axis
+  double *imex_b = nullptr;
+  bool    have_omega = false;
+  double  omega[3] = {0., 0., 0.};
+};
+
+namespace fl {
+
+// fl_scalar.hip: the stages of fl_scalar_step over dt, reading phi^n from phi_dev and writing the new phi to out_dev (phi_dev itself, or an array that
+// is neither phi_dev nor a work array); the arguments are checked by the callers
+int scalar_ssp_step(fl_scalar *m, double dt, int nstages, const double *source_dev, const double *phi_dev, double *out_dev);
+
+}  // namespace fl

@@ -727,6 +727,8 @@ FlErrorCode NSCreate(NS *ns)
   n->max_time  = 1.7976931348623157e308;
   n->errorifstepfailed = 1;
   n->scalar_stages = 5; /* the reference's -ts_type ssp default */
+  n->scalar_theta  = 0.;
+  n->scalar_rtol   = 1e-6;
   n->bc_keep           = 1;
   fl_ksp_opts_default(&n->schur);
   fl_ksp_opts_default(&n->mom);
@@ -883,6 +885,15 @@ FlErrorCode NSSetFromOptions(NS ns, int argc, char **argv)
   if (opt_int64(argc, argv, "-ns_scalar_stages", &iv)) {
     if (iv < 2 || iv > 1000) return E_ARG_OUTOFRANGE;
     ns->scalar_stages = (int)iv;
+  }
+  /* mirror only: implicit diffusion of the scalars added from here on (NSSetScalarImplicit): theta 0 (explicit) or in [0.5, 1], rtol in (0, 1) */
+  if (opt_real(argc, argv, "-ns_scalar_implicit_theta", &v)) {
+    if (!(v == 0. || (v >= 0.5 && v <= 1.))) return E_ARG_OUTOFRANGE;
+    ns->scalar_theta = v;
+  }
+  if (opt_real(argc, argv, "-ns_scalar_implicit_rtol", &v)) {
+    if (!(v > 0. && v < 1.)) return E_ARG_OUTOFRANGE;
+    ns->scalar_rtol = v;
   }
   /* mirror only: gravity of the Boussinesq term (NSSetGravity), three numbers separated by commas */
   if ((s = opt_find(argc, argv, "-ns_gravity"))) {
@@ -1339,6 +1350,7 @@ static void ibm_free_own(NS ns);
 
 /* ---- passive scalars (fluca_host.h) */
 #define MAXNSSCALARS 8
+#define NS_SCALAR_CHEB_MAXIT 100000 /* far beyond any count the bound asks for: 1e-12 at a diffusion number of 1e6 takes under 30000 steps */
 static FlErrorCode scalar_get(NS ns, int id, struct NSScalar **sc)
 {
   if (!ns) return E_ARG_NULL;
@@ -1366,7 +1378,17 @@ static FlErrorCode scalars_step(NS ns)
   for (int a = 0; a < ns->nscalar; ++a) {
     struct NSScalar *sc = &ns->scalars[a];
     FLCHK(scalar_ensure(ns, sc));
-    for (int k = 0; k < sc->substeps; ++k) FLABI(fl_scalar_step(sc->h, ns->dt / sc->substeps, ns->scalar_stages, sc->src, sc->phi));
+    if (sc->theta == 0.) {
+      for (int k = 0; k < sc->substeps; ++k) FLABI(fl_scalar_step(sc->h, ns->dt / sc->substeps, ns->scalar_stages, sc->src, sc->phi));
+      continue;
+    }
+    /* implicit diffusion (NSSetScalarImplicit): the stages without the diffusion term, then a fixed number of Chebyshev launches -- nothing waits */
+    for (int k = 0; k < sc->substeps; ++k) {
+      fl_scalar_cheb_info info;
+      FLABI(fl_scalar_step_imex(sc->h, ns->dt / sc->substeps, ns->scalar_stages, sc->theta, sc->rtol, NS_SCALAR_CHEB_MAXIT, sc->src, sc->phi, &info));
+      sc->cheb_steps = info.steps;
+      sc->cheb_bound = info.bound;
+    }
   }
   return 0;
 }
@@ -1384,6 +1406,9 @@ FlErrorCode NSAddScalar(NS ns, const char *name, double gamma, const char *limit
   sc->gamma    = gamma;
   sc->limiter  = limiter;
   sc->substeps = 1;
+  sc->theta    = ns->mesh->size > 1 ? 0. : ns->scalar_theta; /* (several ranks: the option does not apply, NSSetScalarImplicit says E_SUP) */
+  sc->rtol     = ns->scalar_rtol;
+  sc->cheb_bound = 1.;
   Mesh_Cart *cart = (Mesh_Cart *)ns->mesh->data;
   for (int b = 0; b < 6; ++b) sc->kind[b] = cart->bndTypes[b / 2] == MESHCART_BOUNDARY_PERIODIC ? 2 : 1;
   int64_t sz[4];
@@ -1428,6 +1453,25 @@ FlErrorCode NSSetScalarSubsteps(NS ns, int id, int n)
   FLCHK(scalar_get(ns, id, &sc));
   if (n < 1) return E_ARG_OUTOFRANGE;
   sc->substeps = n;
+  return 0;
+}
+FlErrorCode NSSetScalarImplicit(NS ns, int id, double theta, double rtol)
+{
+  struct NSScalar *sc = NULL;
+  FLCHK(scalar_get(ns, id, &sc));
+  if (!(theta == 0. || (theta >= 0.5 && theta <= 1.)) || !(rtol > 0. && rtol < 1.)) return E_ARG_OUTOFRANGE;
+  if (theta != 0. && ns->mesh->size > 1) return E_SUP; /* fl_scalar_step_imex runs on one rank */
+  sc->theta = theta;
+  sc->rtol  = rtol;
+  return 0;
+}
+FlErrorCode NSGetScalarImplicitInfo(NS ns, int id, int *steps, double *bound)
+{
+  struct NSScalar *sc = NULL;
+  if (!steps || !bound) return E_ARG_NULL;
+  FLCHK(scalar_get(ns, id, &sc));
+  *steps = sc->cheb_steps;
+  *bound = sc->cheb_bound;
   return 0;
 }
 FlErrorCode NSGetScalarArray(NS ns, int id, double **phi_dev)

@@ -121,3 +121,44 @@ class Scalar:
         check(lib.fl_scalar_boundary_flux(self.h, _ptr(phi), out), "fl_scalar_boundary_flux")
         self.P._post()
         return np.array(list(out), dtype=np.float64).reshape(6, 2)
+
+    # ---- implicit diffusion (include/fluca_hip_implicit.h); one rank only.  `info` of a call: dict(steps, capped, emin, emax, bound), host values
+
+    @staticmethod
+    def _info(i):
+        return dict(steps=i.steps, capped=bool(i.capped), emin=i.emin, emax=i.emax, bound=i.bound)
+
+    def diffusion_interval(self, c):
+        """-> (emin, emax) of diag^-1 (I - c L): host arithmetic, no GPU work"""
+        lo, hi = C.c_double(), C.c_double()
+        check(lib.fl_scalar_diffusion_interval(self.h, float(c), C.byref(lo), C.byref(hi)), "fl_scalar_diffusion_interval")
+        return lo.value, hi.value
+
+    def diffusion_apply(self, c, phi, out=None):
+        """out = phi - c D(phi); enqueues and returns"""
+        assert phi.numel() == self.P.ncell
+        out = self.P.empty() if out is None else out
+        self.P._pre()
+        check(lib.fl_scalar_diffusion_apply(self.h, float(c), _ptr(phi), _ptr(out)), "fl_scalar_diffusion_apply")
+        self.P._post()
+        return out
+
+    def diffusion_solve(self, c, b, x, rtol=1e-6, maxit=10000):
+        """solve x - c D(x) = b in place in x (the guess) by Chebyshev-Jacobi, rtol relative to the initial error; -> info.  Enqueues and returns"""
+        assert b.numel() == self.P.ncell and x.numel() == self.P.ncell
+        info = capi.fl_scalar_cheb_info()
+        self.P._pre()
+        check(lib.fl_scalar_diffusion_solve(self.h, float(c), float(rtol), int(maxit), _ptr(b), _ptr(x), C.byref(info)), "fl_scalar_diffusion_solve")
+        self.P._post()
+        return self._info(info)
+
+    def step_imex(self, phi, dt, nstages=5, theta=1.0, rtol=1e-6, maxit=10000, source=None):
+        """advance phi in place over dt: convection and source by the explicit stages, diffusion implicitly (theta = 1 backward Euler, 0.5
+        Crank-Nicolson); -> info.  Enqueues and returns"""
+        assert phi.numel() == self.P.ncell and (source is None or source.numel() == self.P.ncell)
+        info = capi.fl_scalar_cheb_info()
+        self.P._pre()
+        check(lib.fl_scalar_step_imex(self.h, float(dt), int(nstages), float(theta), float(rtol), int(maxit), _ptr(source), _ptr(phi), C.byref(info)),
+              "fl_scalar_step_imex")
+        self.P._post()
+        return self._info(info)

@@ -33,6 +33,7 @@
 #define FLUCA_HOST_H
 
 #include "fluca_hip.h"
+#include "fluca_hip_implicit.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -276,6 +277,18 @@ FlErrorCode NSSetScalarSource(NS ns, int id, const double *src_dev);
 FlErrorCode NSSetScalarSubsteps(NS ns, int id, int n);
 FlErrorCode NSGetScalarArray(NS ns, int id, double **phi_dev);
 FlErrorCode NSGetScalarCFL(NS ns, int id, double out[2]);
+/* IMPLICIT DIFFUSION OF A SCALAR (no reference counterpart): with theta != 0 NSStep advances scalar id by fl_scalar_step_imex (include/fluca_hip_implicit.h)
+ * once per substep -- convection and source by the explicit stages, diffusion by theta-weighted backward differences solved with a FIXED number of
+ * Chebyshev-Jacobi launches, known on the host before the first one: nothing on the step waits, and the diffusive number of NSGetScalarCFL (which keeps
+ * reporting both numbers) no longer limits the step.
+ *   NSSetScalarImplicit      theta = 0 (default): explicit, NSStep launches what it launched before, bit for bit.  theta in [0.5, 1]: 1 backward Euler,
+ *                            0.5 Crank-Nicolson.  rtol in (0, 1): the reduction of the solve's initial error (the weighted norm of the C-ABI's header).
+ *                            E_ARG_OUTOFRANGE otherwise; E_SUP with theta != 0 on a several-rank mesh.  With Gamma = 0 the step is the explicit one, bit for bit.
+ *   NSGetScalarImplicitInfo  the Chebyshev steps the last substep ran and the bound B_steps they guarantee (0 and 1 before the first implicit step)
+ * Options: -ns_scalar_implicit_theta <0 | 0.5..1>, -ns_scalar_implicit_rtol <r> (default 1e-6): what a scalar added AFTERWARDS starts with, as
+ * -ns_scalar_limiter (on a several-rank mesh the scalars stay explicit). */
+FlErrorCode NSSetScalarImplicit(NS ns, int id, double theta, double rtol);
+FlErrorCode NSGetScalarImplicitInfo(NS ns, int id, int *steps, double *bound);
 /* SCALARS THAT DRIVE THE FLOW (Boussinesq; no reference counterpart): with a gravity g != 0 and a scalar whose beta != 0 the right-hand side of the
  * step (NSFormFunction, hence NSStep) gains  momrhs += dt sum_s (-beta_s g) (phi_s - phi_ref_s),  rho = rho0 (1 - beta (phi - phi_ref)): ONE launch for
  * all active scalars (fl_momentum_add_buoyancy), added directly after the immersed-boundary term.  phi is the scalars' field as it stands when the step

@@ -129,6 +129,7 @@ struct _p_NS {
   int                  scalar_stages;    /* -ns_scalar_stages (default 5, the reference's -ts_type ssp) */
   int                  scalar_limiter;   /* -ns_scalar_limiter: the limiter of a scalar added without a name of its own (default superbee) */
   double               gravity[3];       /* NSSetGravity / -ns_gravity (default 0): with a scalar whose beta != 0 the Boussinesq term of the right-hand side */
+  double               scalar_theta, scalar_rtol; /* -ns_scalar_implicit_theta (default 0: explicit), -ns_scalar_implicit_rtol (default 1e-6): of a scalar added later */
 };
 struct NSScalar {
   char          name[32];
@@ -138,6 +139,9 @@ struct NSScalar {
   double       *phi;      /* device, owned by the NS */
   const double *src;      /* device, borrowed; may be NULL */
   double        beta, phi_ref; /* NSSetScalarBuoyancy: rho = rho0 (1 - beta (phi - phi_ref)); beta = 0 (default): passive */
+  double        theta, rtol;   /* NSSetScalarImplicit: theta = 0 (default) explicit, else fl_scalar_step_imex(theta, rtol) */
+  int           cheb_steps;    /* NSGetScalarImplicitInfo: of the last substep run */
+  double        cheb_bound;
 };
 
 /* NSCNLINEAR's data (nslinearcnimpl.h: v0interp, phalf, B) plus, in this mirror, the solution and solver vectors the

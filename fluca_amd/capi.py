@@ -200,7 +200,12 @@ PROTOTYPES_IMPLICIT = {
     "fl_scalar_diffusion_solve": (C.c_int, [_P, C.c_double, C.c_double, C.c_int, _P, _P, C.POINTER(fl_scalar_cheb_info)]),
     "fl_scalar_step_imex": (C.c_int, [_P, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, _P, _P, C.POINTER(fl_scalar_cheb_info)]),
 }
-for _name, (_res, _args) in list(PROTOTYPES.items()) + list(PROTOTYPES_IMPLICIT.items()):
+# every symbol include/fluca_hip_ibm_scalar.h declares (tests/test_ibm_scalar_host.py checks that header against this table)
+PROTOTYPES_IBM_SCALAR = {
+    "fl_ibm_scalar_force": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.POINTER(C.c_double), _P, _P, _P]),
+    "fl_ibm_scalar_rate": (C.c_int, [_P, _P, _P, _P, C.c_int, C.POINTER(C.c_double)]),
+}
+for _name, (_res, _args) in list(PROTOTYPES.items()) + list(PROTOTYPES_IMPLICIT.items()) + list(PROTOTYPES_IBM_SCALAR.items()):
     _f = getattr(lib, _name)  # AttributeError if the library lacks a declared symbol
     _f.restype = _res
     _f.argtypes = _args

@@ -36,7 +36,12 @@
 //                   arrivals ranked by number (counting, tiled through LDS), then stayers and arrivals -- both ascending -- into one ascending
 //                   list by binary search in each other's numbers: the own list of a set created afresh, without a sort
 //   k_ibm_rigid_pose  a rigid body's markers and target velocities from their reference positions (the host mirror's moving body)
+//   a scalar held on the markers (fl_ibm_scalar_force, include/fluca_hip_ibm_scalar.h): per pass the bits of interp(1), T - Phi, spread(1)
+//   k_ibm_scalar_defect  k_ibm_interp for one field whose lane 0 goes on to q = T - Phi and the running Q (one rank: the defect in the interpolation's launch)
+//   k_ibm_scalar_q       one lane per own marker: q and Q from a Phi that is complete (behind k_ibm_collect_U / the all-reduce)
+//   k_ibm_spread<1>      the spread's one-component instantiation: one staged value per marker, two accumulators per thread
 #include "fl_handle.h"
+#include "../../include/fluca_hip_ibm_scalar.h"
 
 namespace fl {
 
@@ -229,11 +234,14 @@ __global__ void __launch_bounds__(256) k_ibm_interp(IbmP P, const int *__restric
 // every marker's 1-D weights onto the tile's eight cells per axis (zero outside the support, periodic wrap and all), so the loop reads four weights and
 // three forces at addresses that depend on nothing but the thread and the loop counter -- no test, no dependent read, unrolled.  A cell outside a marker's
 // support adds an exact zero, so the sums (ascending marker id per cell) are the same bits as that loop's.
+// NC: components staged and accumulated per cell.  3 is the launch of fl_ibm_spread (ncomp <= 3 at run time); 1 is the scalar forcing's: one staged
+// value per marker and two accumulators per thread instead of three and six, the same operations per component.
+template <int NC>
 __global__ void __launch_bounds__(256) k_ibm_spread(IbmP P, const int *__restrict__ i0, const double *__restrict__ w, const int *__restrict__ off, const int *__restrict__ list, const int *__restrict__ active, int ncomp, int64_t ncell, const double *__restrict__ F,
                                                     const double *__restrict__ dV, double *__restrict__ f)
 {
   __shared__ double swl[3][BIN_CHUNK][TB];  // weight of marker e on the tile's cell c of axis d
-  __shared__ double sF[3][BIN_CHUNK];
+  __shared__ double sF[NC][BIN_CHUNK];
   const int tile = active[blockIdx.x];  // only tiles with a non-empty bin are launched
   const int beg = off[tile], end = off[tile + 1];
   if (beg == end) return;
@@ -243,7 +251,9 @@ __global__ void __launch_bounds__(256) k_ibm_spread(IbmP P, const int *__restric
   // this thread's two cells: (ci, cj, ck) and (ci, cj, ck + 4)
   const int li = threadIdx.x & 7, lj = (threadIdx.x >> 3) & 7, lk = threadIdx.x >> 6;
   const int ci = tt[0] * TB + li, cj = tt[1] * TB + lj;
-  double    acc[2][3] = {{0., 0., 0.}, {0., 0., 0.}};
+  double    acc[2][NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) acc[0][c] = acc[1][c] = 0.;
   for (int c0 = beg; c0 < end; c0 += BIN_CHUNK) {  // bins are sorted by marker id (k_ibm_sort_bins): chunks in list order keep the order
     const int n = min(BIN_CHUNK, end - c0);
     __syncthreads();
@@ -263,20 +273,20 @@ __global__ void __launch_bounds__(256) k_ibm_spread(IbmP P, const int *__restric
         }
       }
       const double dv = dV[m] * ih;
-      for (int c = 0; c < 3; ++c) sF[c][threadIdx.x] = c < ncomp ? F[(int64_t)c * P.L + m] * dv : 0.;
+#pragma unroll
+      for (int c = 0; c < NC; ++c) sF[c][threadIdx.x] = c < ncomp ? F[(int64_t)c * P.L + m] * dv : 0.;
     }
     __syncthreads();
 #pragma unroll 4
     for (int e = 0; e < n; ++e) {
       const double wxy = swl[0][e][li] * swl[1][e][lj];
       const double wt0 = wxy * swl[2][e][lk], wt1 = wxy * swl[2][e][lk + 4];
-      const double f0 = sF[0][e], f1 = sF[1][e], f2 = sF[2][e];
-      acc[0][0] += wt0 * f0;
-      acc[0][1] += wt0 * f1;
-      acc[0][2] += wt0 * f2;
-      acc[1][0] += wt1 * f0;
-      acc[1][1] += wt1 * f1;
-      acc[1][2] += wt1 * f2;
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const double fc = sF[c][e];
+        acc[0][c] += wt0 * fc;
+        acc[1][c] += wt1 * fc;
+      }
     }
   }
   if (ci < P.n[0] && cj < P.n[1])
@@ -285,8 +295,9 @@ __global__ void __launch_bounds__(256) k_ibm_spread(IbmP P, const int *__restric
       if (ck >= P.n[2]) continue;
       const int64_t cell = ((int64_t)ck * P.n[1] + cj) * P.n[0] + ci;
       const double  vinv = uni ? 1. : P.idx[0][ci] * P.idx[1][cj] * P.idx[2][ck];
-      for (int c = 0; c < ncomp && c < 3; ++c)
-        if (acc[half][c] != 0.) f[(int64_t)c * ncell + cell] += acc[half][c] * vinv;
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+        if (c < ncomp && acc[half][c] != 0.) f[(int64_t)c * ncell + cell] += acc[half][c] * vinv;
     }
 }
 
@@ -822,6 +833,56 @@ __global__ void __launch_bounds__(256) k_ibm_force_sum(ForceP Q, const double *_
   }
 }
 
+// ---- Dirichlet forcing of one scalar on the markers (fl_ibm_scalar_force) ---------------------------------------------------------------------
+// One pass: Phi = interp(phi), q = T - Phi, Q (+)= q, phi += spread(q, dV) -- the bits of fl_ibm_interp(1), fl_vec_lincomb(-1 Phi + 1 T) and
+// fl_ibm_spread(1) one after the other.  The difference is rounded once either way: a product with -1 or 1 is exact.
+struct ScalarTarget {
+  double value[FORCE_MAXBODY];  // the per-body table, passed by value: the caller's host array is read before the call returns
+};
+__device__ __forceinline__ double scalar_target(const double *__restrict__ target, const int32_t *__restrict__ body, const ScalarTarget &V, int64_t l)
+{
+  return target ? target[l] : V.value[body ? body[l] : 0];  // ids are the caller's promise: nothing is clamped or checked here
+}
+
+// k_ibm_interp for one field -- its lanes, its weights, its fixed-order reduction -- and lane 0 goes on to the defect: q[l] = T_l - Phi_l,
+// Q[l] = q[l] (first pass) or Q[l] + q[l].  One rank only: where partial sums of other ranks belong to Phi, k_ibm_scalar_q forms q behind them.
+__global__ void __launch_bounds__(256) k_ibm_scalar_defect(IbmP P, const int *__restrict__ i0, const double *__restrict__ w, const double *__restrict__ phi, const double *__restrict__ target, const int32_t *__restrict__ body,
+                                                           ScalarTarget V, int first, double *__restrict__ q, double *__restrict__ Q)
+{
+  const int     lane = threadIdx.x & 63;
+  const int64_t l    = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (l >= P.L) return;
+  const int S = P.S;
+  const int a = lane % S, b = (lane / S) % S, c3 = lane / (S * S);
+  double    wt   = 0.;
+  int64_t   cell = -1;
+  if (c3 < S) {
+    const int ci = support_cell(P, 0, i0[l], a), cj = support_cell(P, 1, i0[P.L + l], b), ck = support_cell(P, 2, i0[2 * P.L + l], c3);
+    if (ci >= 0 && cj >= 0 && ck >= 0) {
+      cell = ((int64_t)ck * P.n[1] + cj) * P.n[0] + ci;
+      wt   = w[(0 * 4 + a) * P.L + l] * w[(1 * 4 + b) * P.L + l] * w[(2 * 4 + c3) * P.L + l];
+    }
+  }
+  double v = cell >= 0 ? wt * phi[cell] : 0.;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  if (lane == 0) {
+    const double d = scalar_target(target, body, V, l) - v;
+    q[l]           = d;
+    if (Q) Q[l] = first ? d : Q[l] + d;
+  }
+}
+
+// the defect of own marker l from a Phi that is complete (behind k_ibm_collect_U on an owned set, behind the all-reduce on a replicated one)
+__global__ void k_ibm_scalar_q(int64_t L, const double *__restrict__ Phi, const double *__restrict__ target, const int32_t *__restrict__ body, ScalarTarget V, int first, double *__restrict__ q, double *__restrict__ Q)
+{
+  const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= L) return;
+  const double d = scalar_target(target, body, V, l) - Phi[l];
+  q[l]           = d;
+  if (Q) Q[l] = first ? d : Q[l] + d;
+}
+
 }  // namespace fl
 
 using namespace fl;
@@ -857,6 +918,9 @@ struct fl_ibm {
   // fl_ibm_force: workspace (FW_END doubles) and the two arrival counters (16 bytes, zeroed before every call)
   double     *fws = nullptr;
   unsigned   *ftick = nullptr;
+  // fl_ibm_scalar_force / fl_ibm_scalar_rate: q and the complete Phi of a pass (one value per marker of the set), (Q, 0, 0) for the rate's sum
+  double     *sq = nullptr, *sphi = nullptr, *sf3 = nullptr;
+  int64_t     sqcap = 0, sphicap = 0, sf3cap = 0;
 };
 
 static int ibm_rebin(fl_ibm *m)
@@ -1473,7 +1537,8 @@ static int ibm_interp_owned(fl_ibm *m, int ncomp, const double *u, double *U)
   return FL_SUCCESS;
 }
 
-static int ibm_spread_owned(fl_ibm *m, int ncomp, const double *F, const double *dV, double *f)
+// one: the one-component kernel of the scalar forcing (ncomp = 1), else fl_ibm_spread's
+static int ibm_spread_owned(fl_ibm *m, int ncomp, const double *F, const double *dV, double *f, bool one = false)
 {
   fl_poisson   *h  = m->gp;
   hipStream_t   s  = h->stream;
@@ -1493,7 +1558,8 @@ static int ibm_spread_owned(fl_ibm *m, int ncomp, const double *F, const double 
   }
   double *Fi = m->Fi, *dVi = m->Fi + (int64_t)ncomp * Lt;
   hipLaunchKernelGGL(k_ibm_stage_F, dim3((unsigned)((Lt + 255) / 256)), dim3(256), 0, s, Lo, Lt, ncomp, F, dV, m->rbuf, Fi, dVi);
-  if (m->nactive > 0) hipLaunchKernelGGL(k_ibm_spread, dim3(m->nactive), dim3(256), 0, s, m->P, m->i0, m->w, m->off, m->list, m->active, ncomp, h->ncell, Fi, dVi, f);
+  if (m->nactive > 0 && one) hipLaunchKernelGGL(k_ibm_spread<1>, dim3(m->nactive), dim3(256), 0, s, m->P, m->i0, m->w, m->off, m->list, m->active, 1, h->ncell, Fi, dVi, f);
+  else if (m->nactive > 0) hipLaunchKernelGGL(k_ibm_spread<3>, dim3(m->nactive), dim3(256), 0, s, m->P, m->i0, m->w, m->off, m->list, m->active, ncomp, h->ncell, Fi, dVi, f);
   FL_HIP(hipGetLastError());
   return FL_SUCCESS;
 }
@@ -1524,7 +1590,7 @@ extern "C" int fl_ibm_spread(fl_ibm *m, int ncomp, const double *F, const double
   FL_HIP(hipSetDevice(h->device));
   if (m->owned) return ibm_spread_owned(m, ncomp, F, dV, f);
   if (!F || !dV) return FL_ERR_ARG_NULL;
-  if (m->nactive > 0) hipLaunchKernelGGL(k_ibm_spread, dim3(m->nactive), dim3(256), 0, h->stream, m->P, m->i0, m->w, m->off, m->list, m->active, ncomp, h->ncell, F, dV, f);
+  if (m->nactive > 0) hipLaunchKernelGGL(k_ibm_spread<3>, dim3(m->nactive), dim3(256), 0, h->stream, m->P, m->i0, m->w, m->off, m->list, m->active, ncomp, h->ncell, F, dV, f);
   FL_HIP(hipGetLastError());
   return FL_SUCCESS;
 }
@@ -1613,6 +1679,85 @@ extern "C" int fl_ibm_force(fl_ibm *m, const double *F, const double *dV, const 
   return FL_SUCCESS;
 }
 
+// ---- Dirichlet forcing of one scalar, and what it hands to the fluid ------------------------------------------------------------------------
+
+extern "C" int fl_ibm_scalar_force(fl_ibm *m, int npass, const double *target_dev, const int32_t *body_dev, int nbody, const double *value, const double *dV_dev, double *phi_dev, double *Q_dev)
+{
+  if (!m) return FL_ERR_ARG_NULL;
+  fl_poisson   *h     = m->gp;
+  hipStream_t   s     = h->stream;
+  const bool    split = h->multi || ibm_split(h);
+  const int64_t L     = m->owned ? m->Lo : m->P.L;
+  const bool    null_arg = !phi_dev || (L > 0 && !dV_dev);
+  const bool    range_ok = npass >= 1 && npass <= 16 && nbody >= 1 && nbody <= FORCE_MAXBODY;
+  const bool    wrong    = (target_dev && value) || (L > 0 && !target_dev && !value);
+  FL_HIP(hipSetDevice(h->device));
+  if (m->owned && split) {  // collective: every rank leaves with the same error, or none does
+    double v[3] = {null_arg ? 1. : 0., range_ok ? 0. : 1., wrong ? 1. : 0.};
+    FL_CHK(ibm_vote(h, v, 3));
+    if (v[0] > 0.) return FL_ERR_ARG_NULL;
+    if (v[1] > 0.) return FL_ERR_ARG_OUTOFRANGE;
+    if (v[2] > 0.) return FL_ERR_ARG_WRONG;
+  } else {
+    if (null_arg) return FL_ERR_ARG_NULL;
+    if (!range_ok) return FL_ERR_ARG_OUTOFRANGE;
+    if (wrong) return FL_ERR_ARG_WRONG;
+  }
+  ScalarTarget V;
+  for (int b = 0; b < FORCE_MAXBODY; ++b) V.value[b] = (value && b < nbody) ? value[b] : 0.;
+  const int32_t *body = value ? body_dev : nullptr;
+  if (L > 0) FL_CHK(ibm_reserve(h, &m->sq, &m->sqcap, L));
+  if (L > 0 && split) FL_CHK(ibm_reserve(h, &m->sphi, &m->sphicap, L));
+  const unsigned nbq = (unsigned)((L + 255) / 256);
+  for (int k = 0; k < npass; ++k) {
+    if (!split) {
+      // one rank: every marker's support is here (P.L = L, an owned set holds no ghost) -- the defect in the interpolation's launch
+      if (L > 0) hipLaunchKernelGGL(k_ibm_scalar_defect, dim3((unsigned)((L + 3) / 4)), dim3(256), 0, s, m->P, m->i0, m->w, phi_dev, target_dev, body, V, k == 0, m->sq, Q_dev);
+      if (m->nactive > 0) hipLaunchKernelGGL(k_ibm_spread<1>, dim3(m->nactive), dim3(256), 0, s, m->P, m->i0, m->w, m->off, m->list, m->active, 1, h->ncell, m->sq, dV_dev, phi_dev);
+      FL_HIP(hipGetLastError());
+    } else if (m->owned) {
+      FL_CHK(ibm_interp_owned(m, 1, phi_dev, m->sphi));  // own + ghost markers, the ghosts' partial sums back to their owners
+      if (L > 0) hipLaunchKernelGGL(k_ibm_scalar_q, dim3(nbq), dim3(256), 0, s, L, m->sphi, target_dev, body, V, k == 0, m->sq, Q_dev);
+      FL_HIP(hipGetLastError());
+      FL_CHK(ibm_spread_owned(m, 1, m->sq, dV_dev, phi_dev, true));
+    } else {
+      hipLaunchKernelGGL(k_ibm_interp, dim3((unsigned)((L + 3) / 4)), dim3(256), 0, s, m->P, m->i0, m->w, 1, h->ncell, phi_dev, m->sphi);
+      FL_HIP(hipGetLastError());
+      if (h->comm.kind == Comm::NONE) return FL_ERR_ARG_WRONGSTATE;
+      FL_CHK(h->comm.allreduce(s, m->sphi, (int)L));  // where fl_ibm_interp has it
+      hipLaunchKernelGGL(k_ibm_scalar_q, dim3(nbq), dim3(256), 0, s, L, m->sphi, target_dev, body, V, k == 0, m->sq, Q_dev);
+      if (m->nactive > 0) hipLaunchKernelGGL(k_ibm_spread<1>, dim3(m->nactive), dim3(256), 0, s, m->P, m->i0, m->w, m->off, m->list, m->active, 1, h->ncell, m->sq, dV_dev, phi_dev);
+      FL_HIP(hipGetLastError());
+    }
+  }
+  return FL_SUCCESS;
+}
+
+// The sum is fl_ibm_force's, on F = (Q, 0, 0): its force group then holds the terms Q_l dV_l and nothing else (a zero term changes neither the
+// maximum nor an integer sum), so the split, the bound, the NaN rule, the votes and the collectives are that call's own.  The torque group it
+// also forms is not used.
+extern "C" int fl_ibm_scalar_rate(fl_ibm *m, const double *Q_dev, const double *dV_dev, const int32_t *body_dev, int nbody, double *rate)
+{
+  if (!m) return FL_ERR_ARG_NULL;
+  fl_poisson   *h = m->gp;
+  const int64_t L = m->owned ? m->Lo : m->P.L;
+  FL_HIP(hipSetDevice(h->device));
+  const double *F = nullptr;
+  if (L > 0 && Q_dev) {
+    FL_CHK(ibm_reserve(h, &m->sf3, &m->sf3cap, 3 * L));
+    FL_HIP(hipMemcpyAsync(m->sf3, Q_dev, sizeof(double) * (size_t)L, hipMemcpyDeviceToDevice, h->stream));
+    FL_HIP(hipMemsetAsync(m->sf3 + L, 0, sizeof(double) * 2 * (size_t)L, h->stream));
+    F = m->sf3;
+  }
+  const int           nb = std::min(std::max(nbody, 1), FORCE_MAXBODY);
+  std::vector<double> about(3 * (size_t)nb, 0.), force(3 * (size_t)nb, 0.);
+  // nbody out of range: fl_ibm_force says so (and votes it) before it reads or writes an array sized by it
+  const int rc = fl_ibm_force(m, F, dV_dev, body_dev, nbody, about.data(), rate ? force.data() : nullptr, nullptr);
+  if (rc) return rc;
+  for (int b = 0; b < nbody; ++b) rate[b] = force[3 * (size_t)b];
+  return FL_SUCCESS;
+}
+
 extern "C" int fl_ibm_destroy(fl_ibm *m)
 {
   if (!m) return FL_SUCCESS;
@@ -1620,7 +1765,7 @@ extern "C" int fl_ibm_destroy(fl_ibm *m)
   for (void *p : {(void *)m->X, (void *)m->Y, (void *)m->Z, (void *)m->w, (void *)m->i0, (void *)m->cnt, (void *)m->off, (void *)m->list, (void *)m->scratch, (void *)m->active, (void *)m->nact_dev, (void *)m->xcg[0],
                   (void *)m->xcg[1], (void *)m->xcg[2], (void *)m->gid_own, (void *)m->gid, (void *)m->mask, (void *)m->sendlist, (void *)m->cstart, (void *)m->clist, (void *)m->sbuf, (void *)m->rbuf, (void *)m->Ui,
                   (void *)m->Fi, (void *)m->cbuf, (void *)m->dest, (void *)m->bstay, (void *)m->boff, (void *)m->mcnt, (void *)m->gidtmp, (void *)m->stay, (void *)m->arr, (void *)m->mpos, (void *)m->attr,
-                  (void *)m->attrtmp, (void *)m->nbuf, (void *)m->fws, (void *)m->ftick})
+                  (void *)m->attrtmp, (void *)m->nbuf, (void *)m->fws, (void *)m->ftick, (void *)m->sq, (void *)m->sphi, (void *)m->sf3})
     if (p) (void)hipFree(p);
   delete m;
   return FL_SUCCESS;

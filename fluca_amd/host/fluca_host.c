@@ -729,6 +729,7 @@ FlErrorCode NSCreate(NS *ns)
   n->scalar_stages = 5; /* the reference's -ts_type ssp default */
   n->scalar_theta  = 0.;
   n->scalar_rtol   = 1e-6;
+  n->scalar_ibm_passes = 1;
   n->bc_keep           = 1;
   fl_ksp_opts_default(&n->schur);
   fl_ksp_opts_default(&n->mom);
@@ -894,6 +895,11 @@ FlErrorCode NSSetFromOptions(NS ns, int argc, char **argv)
   if (opt_real(argc, argv, "-ns_scalar_implicit_rtol", &v)) {
     if (!(v > 0. && v < 1.)) return E_ARG_OUTOFRANGE;
     ns->scalar_rtol = v;
+  }
+  /* mirror only: the passes NSSetScalarImmersedBoundary(npass = -1) takes */
+  if (opt_int64(argc, argv, "-ns_scalar_ibm_passes", &iv)) {
+    if (iv < 1 || iv > 16) return E_ARG_OUTOFRANGE;
+    ns->scalar_ibm_passes = (int)iv;
   }
   /* mirror only: gravity of the Boussinesq term (NSSetGravity), three numbers separated by commas */
   if ((s = opt_find(argc, argv, "-ns_gravity"))) {
@@ -1171,6 +1177,14 @@ static FlErrorCode NSView_Body(NS ns, FlucaViewer viewer) /* nsbasic.c:353-374 *
       if (ns->scalars[a].beta != 0.)
         FLCHK(FlucaViewerASCIIPrintf(viewer, "Buoyant scalar %s: beta %g, reference %g\n", ns->scalars[a].name, ns->scalars[a].beta, ns->scalars[a].phi_ref));
   }
+  for (int a = 0; !rc && a < ns->nscalar; ++a) /* mirror only, and only while the forcing is on */
+    if (ns->scalars[a].ibm_npass > 0 && ns->ibm) {
+      char   vals[64 * 32];
+      size_t at = 0;
+      vals[0]   = 0;
+      for (int b = 0; b < (ns->ibm_nbody ? ns->ibm_nbody : 1) && at + 32 < sizeof(vals); ++b) at += (size_t)snprintf(vals + at, 32, " %g", ns->scalars[a].ibm_value[b]);
+      FLCHK(FlucaViewerASCIIPrintf(viewer, "Scalar %s on the immersed boundary: %d pass%s, value%s\n", ns->scalars[a].name, ns->scalars[a].ibm_npass, ns->scalars[a].ibm_npass == 1 ? "" : "es", vals));
+    }
   FLCHK(FlucaViewerASCIIPopTab(viewer));
   return rc;
 }
@@ -1373,13 +1387,43 @@ static FlErrorCode scalar_ensure(NS ns, struct NSScalar *sc)
   FLABI(fl_scalar_set_velocity(sc->h, V[0], V[1], V[2]));
   return 0;
 }
+/* NSSetScalarImmersedBoundary: phi to the bodies' values on the markers as they stand, and what that hands to the fluid into the step's sums */
+static FlErrorCode scalar_ibm_force(NS ns, struct NSScalar *sc)
+{
+  const int64_t  L     = ns->ibm_L;
+  const int      nbody = ns->ibm_nbody ? ns->ibm_nbody : 1;
+  const int32_t *body  = ns->ibm_nbody ? ns->ibm_body : NULL;
+  if (!ns->ibm_Q || L > ns->ibm_Qcap) { /* the first use, or a migration has brought more markers than ever */
+    void *q = NULL;
+    FLABI(fl_poisson_synchronize(ns->poisson));
+    if (ns->ibm_Q) fl_free(ns->device, ns->ibm_Q);
+    ns->ibm_Q = NULL;
+    FLABI(fl_malloc(ns->device, sizeof(double) * (size_t)(L + L / 4 + 1), &q));
+    ns->ibm_Q    = (double *)q;
+    ns->ibm_Qcap = L + L / 4;
+  }
+  double r[64];
+  FLABI(fl_ibm_scalar_force(ns->ibm, sc->ibm_npass, NULL, body, nbody, sc->ibm_value, L > 0 ? ns->ibm_dV : NULL, sc->phi, ns->ibm_Q));
+  FLABI(fl_ibm_scalar_rate(ns->ibm, L > 0 ? ns->ibm_Q : NULL, L > 0 ? ns->ibm_dV : NULL, body, nbody, r));
+  for (int b = 0; b < nbody; ++b) sc->ibm_sum[b] += r[b];
+  return 0;
+}
 static FlErrorCode scalars_step(NS ns)
 {
   for (int a = 0; a < ns->nscalar; ++a) {
     struct NSScalar *sc = &ns->scalars[a];
     FLCHK(scalar_ensure(ns, sc));
+    const int forced = sc->ibm_npass > 0 && ns->ibm;
+    if (forced) {
+      sc->ibm_sum_ready = 0;
+      for (int b = 0; b < 64; ++b) sc->ibm_sum[b] = 0.;
+    }
     if (sc->theta == 0.) {
-      for (int k = 0; k < sc->substeps; ++k) FLABI(fl_scalar_step(sc->h, ns->dt / sc->substeps, ns->scalar_stages, sc->src, sc->phi));
+      for (int k = 0; k < sc->substeps; ++k) {
+        FLABI(fl_scalar_step(sc->h, ns->dt / sc->substeps, ns->scalar_stages, sc->src, sc->phi));
+        if (forced) FLCHK(scalar_ibm_force(ns, sc));
+      }
+      if (forced) sc->ibm_sum_ready = 1, sc->ibm_sum_dt = ns->dt;
       continue;
     }
     /* implicit diffusion (NSSetScalarImplicit): the stages without the diffusion term, then a fixed number of Chebyshev launches -- nothing waits */
@@ -1388,8 +1432,43 @@ static FlErrorCode scalars_step(NS ns)
       FLABI(fl_scalar_step_imex(sc->h, ns->dt / sc->substeps, ns->scalar_stages, sc->theta, sc->rtol, NS_SCALAR_CHEB_MAXIT, sc->src, sc->phi, &info));
       sc->cheb_steps = info.steps;
       sc->cheb_bound = info.bound;
+      if (forced) FLCHK(scalar_ibm_force(ns, sc));
     }
+    if (forced) sc->ibm_sum_ready = 1, sc->ibm_sum_dt = ns->dt;
   }
+  return 0;
+}
+/* a new marker set or new bodies: the values held no longer say which body they belong to */
+static void scalars_ibm_off(NS ns)
+{
+  for (int a = 0; a < ns->nscalar; ++a) ns->scalars[a].ibm_npass = ns->scalars[a].ibm_sum_ready = 0;
+}
+FlErrorCode NSSetScalarImmersedBoundary(NS ns, int id, int npass, const double *value)
+{
+  struct NSScalar *sc = NULL;
+  if (!ns) return E_ARG_NULL;
+  if (npass < -1 || npass > 16) return E_ARG_OUTOFRANGE;
+  if (!ns->setupcalled || !ns->ibm) return E_ARG_WRONGSTATE;
+  FLCHK(scalar_get(ns, id, &sc));
+  if (npass == -1) npass = ns->scalar_ibm_passes;
+  if (npass > 0 && !value) return E_ARG_NULL;
+  const int nbody = ns->ibm_nbody ? ns->ibm_nbody : 1;
+  for (int b = 0; b < nbody && npass > 0; ++b)
+    if (!(value[b] - value[b] == 0.)) return E_ARG_OUTOFRANGE;
+  for (int b = 0; b < 64; ++b) sc->ibm_value[b] = (npass > 0 && b < nbody) ? value[b] : 0.;
+  sc->ibm_npass     = npass;
+  sc->ibm_sum_ready = 0;
+  return 0;
+}
+FlErrorCode NSGetScalarImmersedBoundaryRate(NS ns, int id, double *rate)
+{
+  struct NSScalar *sc = NULL;
+  if (!ns || !rate) return E_ARG_NULL;
+  if (!ns->setupcalled || !ns->ibm) return E_ARG_WRONGSTATE;
+  FLCHK(scalar_get(ns, id, &sc));
+  if (sc->ibm_npass == 0 || !sc->ibm_sum_ready || !(sc->ibm_sum_dt > 0.)) return E_ARG_WRONGSTATE;
+  const int nbody = ns->ibm_nbody ? ns->ibm_nbody : 1;
+  for (int b = 0; b < nbody; ++b) rate[b] = (1. / sc->ibm_sum_dt) * sc->ibm_sum[b];
   return 0;
 }
 FlErrorCode NSAddScalar(NS ns, const char *name, double gamma, const char *limiter_name, int *id)
@@ -1564,6 +1643,7 @@ FlErrorCode NSDestroy(NS *ns)
   if ((*ns)->ops->destroy) (*ns)->ops->destroy(*ns);
   if ((*ns)->ibm) fl_ibm_destroy((*ns)->ibm);
   if ((*ns)->ibm_U) fl_free((*ns)->device, (*ns)->ibm_U);
+  if ((*ns)->ibm_Q) fl_free((*ns)->device, (*ns)->ibm_Q);
   ibm_free_own(*ns);
   if ((*ns)->momentum) fl_momentum_destroy((*ns)->momentum);
   if ((*ns)->poisson) fl_poisson_destroy((*ns)->poisson);
@@ -1686,6 +1766,7 @@ FlErrorCode NSSetImmersedBoundary(NS ns, int kind, int64_t L, const double *X_de
   if (!ns || !X_dev || !Y_dev || !Z_dev || !dV_dev) return E_ARG_NULL;
   if (!ns->setupcalled) return E_ARG_WRONGSTATE;
   if (L < 1) return E_ARG_OUTOFRANGE;
+  scalars_ibm_off(ns);
   if (ns->ibm) {
     fl_ibm_destroy(ns->ibm);
     ns->ibm = NULL;
@@ -1891,6 +1972,7 @@ FlErrorCode NSSetImmersedBoundaryBodies(NS ns, int nbody, const int32_t *body_de
   if (nbody < 1 || nbody > 64) return E_ARG_OUTOFRANGE;
   if (!ns->setupcalled || !ns->ibm) return E_ARG_WRONGSTATE;
   if (!body_dev) return E_ARG_NULL;
+  scalars_ibm_off(ns);
   if (!ns->ibm_owner) {
     ns->ibm_nbody = nbody;
     ns->ibm_body  = body_dev;

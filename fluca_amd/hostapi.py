@@ -66,6 +66,7 @@ PROTOTYPES = {
     "NSSetScalarSource": [_P, C.c_int, _P], "NSSetScalarSubsteps": [_P, C.c_int, C.c_int], "NSGetScalarArray": [_P, C.c_int, C.POINTER(_P)],
     "NSGetScalarCFL": [_P, C.c_int, C.POINTER(C.c_double)],
     "NSSetScalarImplicit": [_P, C.c_int, C.c_double, C.c_double], "NSGetScalarImplicitInfo": [_P, C.c_int, _ip, C.POINTER(C.c_double)],
+    "NSSetScalarImmersedBoundary": [_P, C.c_int, C.c_int, C.POINTER(C.c_double)], "NSGetScalarImmersedBoundaryRate": [_P, C.c_int, C.POINTER(C.c_double)],
     "NSSetGravity": [_P, C.POINTER(C.c_double)], "NSGetGravity": [_P, C.POINTER(C.c_double)],
     "NSSetScalarBuoyancy": [_P, C.c_int, C.c_double, C.c_double], "NSGetScalarBoundaryFlux": [_P, C.c_int, C.POINTER(C.c_double)],
     # the ops-table entry points (nsimpl.h:21-31, meshimpl.h:16-25) and the viewer they take

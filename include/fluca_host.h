@@ -34,6 +34,7 @@
 
 #include "fluca_hip.h"
 #include "fluca_hip_implicit.h"
+#include "fluca_hip_ibm_scalar.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -289,6 +290,18 @@ FlErrorCode NSGetScalarCFL(NS ns, int id, double out[2]);
  * -ns_scalar_limiter (on a several-rank mesh the scalars stay explicit). */
 FlErrorCode NSSetScalarImplicit(NS ns, int id, double theta, double rtol);
 FlErrorCode NSGetScalarImplicitInfo(NS ns, int id, int *steps, double *bound);
+/* A SCALAR HELD AT A VALUE ON THE IMMERSED BODIES (no reference counterpart): a heated sphere or cylinder, fl_ibm_scalar_force of
+ * include/fluca_hip_ibm_scalar.h.  Only the surface markers are forced, not the body's interior; a value per body, not per marker; no prescribed flux. */
+/* After every substep of scalar id (explicit or NSSetScalarImplicit's IMEX step) NSStep forces phi to value[body] on the markers, npass passes,
+ * with the markers where the flow step left them (t + dt under NSSetImmersedBoundaryMotion).  value: HOST, nbody entries (copied).
+ * npass = 0 (default): off -- NSStep launches and exchanges what it did before, bit for bit.  npass = -1: the option's count.
+ * E_ARG_OUTOFRANGE: npass outside {-1, 0..16}; E_ARG_WRONGSTATE without NSSetImmersedBoundary.  nbody is NSSetImmersedBoundaryBodies' (1 without it);
+ * a later NSSetImmersedBoundary or NSSetImmersedBoundaryBodies switches the forcing of every scalar off.
+ * Option: -ns_scalar_ibm_passes <n> (1..16, default 1). */
+FlErrorCode NSSetScalarImmersedBoundary(NS ns, int id, int npass, const double *value);
+/* rate[b] = (1 / dt) * sum over the substeps of the last completed step of fl_ibm_scalar_rate's sums: the scalar content per unit time body b gave
+ * the fluid.  Collective.  WRONGSTATE without an immersed boundary, with the forcing off, or before the first step. */
+FlErrorCode NSGetScalarImmersedBoundaryRate(NS ns, int id, double *rate);
 /* SCALARS THAT DRIVE THE FLOW (Boussinesq; no reference counterpart): with a gravity g != 0 and a scalar whose beta != 0 the right-hand side of the
  * step (NSFormFunction, hence NSStep) gains  momrhs += dt sum_s (-beta_s g) (phi_s - phi_ref_s),  rho = rho0 (1 - beta (phi - phi_ref)): ONE launch for
  * all active scalars (fl_momentum_add_buoyancy), added directly after the immersed-boundary term.  phi is the scalars' field as it stands when the step

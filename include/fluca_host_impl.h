@@ -130,6 +130,9 @@ struct _p_NS {
   int                  scalar_limiter;   /* -ns_scalar_limiter: the limiter of a scalar added without a name of its own (default superbee) */
   double               gravity[3];       /* NSSetGravity / -ns_gravity (default 0): with a scalar whose beta != 0 the Boussinesq term of the right-hand side */
   double               scalar_theta, scalar_rtol; /* -ns_scalar_implicit_theta (default 0: explicit), -ns_scalar_implicit_rtol (default 1e-6): of a scalar added later */
+  int                  scalar_ibm_passes;  /* -ns_scalar_ibm_passes (default 1): what NSSetScalarImmersedBoundary(npass = -1) takes */
+  double              *ibm_Q;              /* device, owned by the NS: the forcing Q of the substep run last, room for ibm_Qcap markers */
+  int64_t              ibm_Qcap;
 };
 struct NSScalar {
   char          name[32];
@@ -142,6 +145,11 @@ struct NSScalar {
   double        theta, rtol;   /* NSSetScalarImplicit: theta = 0 (default) explicit, else fl_scalar_step_imex(theta, rtol) */
   int           cheb_steps;    /* NSGetScalarImplicitInfo: of the last substep run */
   double        cheb_bound;
+  int           ibm_npass;     /* NSSetScalarImmersedBoundary: 0 (default) off */
+  double        ibm_value[64]; /* ... the value held on the markers of body b */
+  double        ibm_sum[64];   /* sum over the substeps of the last completed step of fl_ibm_scalar_rate's sums, and that step's dt */
+  double        ibm_sum_dt;
+  int           ibm_sum_ready;
 };
 
 /* NSCNLINEAR's data (nslinearcnimpl.h: v0interp, phalf, B) plus, in this mirror, the solution and solver vectors the

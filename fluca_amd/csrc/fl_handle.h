@@ -10,6 +10,7 @@
 
 #include "fl_internal.h"
 #include "fl_knobs.h"
+#include "fl_msg.h"
 
 typedef struct ncclComm *ncclComm_t;  // RCCL's opaque communicator, as <rccl/rccl.h> declares it
 
@@ -59,14 +60,7 @@ int  buoyancy_blocks(int64_t ncell, int ncu);
 int  device_cus(int device);  // compute units of the device (asked once per device), 0 if the runtime does not say
 void launch_buoyancy(hipStream_t, int nblocks, int64_t ncell, int ns, int act, const BuoyArgs &, double dt, double *momrhs);
 
-// ------------------------------------------------------------------------------------------------ transports (fl_comm.hip)
-
-struct Msg {
-  int     peer;
-  double *send, *recv;  // device
-  int64_t count;
-  int     sendtag, recvtag;
-};
+// ------------------------------------------------------------------------------------------------ transports (fl_comm.hip); struct Msg: fl_msg.h
 
 // One-shot all-reduce of up to NSLOT doubles: every rank owns a MAILBOX in fine-grained device memory --
 // two parities of nranks slots of NSLOT doubles and nranks sequence numbers each -- that its peers have mapped (hipIpc handles exchanged once

@@ -16,7 +16,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libflucahip.so")
 SOURCES = ["fl_coeff.cpp", "fl_kernels.hip", "fl_api.hip", "fl_knobs.cpp", "fl_place.hip", "fl_halo.hip", "fl_comm.hip", "fl_ksp.hip", "fl_cheb2.hip", "fl_layout.hip", "fl_ibm.hip", "fl_ibm_owner.hip", "fl_ibm_body.hip", "fl_momentum.hip", "fl_mg.hip", "fl_schur_var.hip", "fl_scalar.hip", "fl_buoyancy.hip", "fl_scalar_implicit.hip"]
 HEADERS = ["fl_internal.h", "fl_knobs.h", "fl_handle.h", "fl_msg.h", "fl_ibm_device.h", "fl_ibm_handle.h", "fl_ibm_plan.h", "fl_device.h", "fl_stencil.h", "fl_mom_tile.h", "fl_mom_tile3.h", "fl_limiter.h", "fl_scalar_handle.h", os.path.join("..", "..", "include", "fluca_hip.h"),
-           os.path.join("..", "..", "include", "fluca_hip_implicit.h"), os.path.join("..", "..", "include", "fluca_hip_ibm_scalar.h")]
+           os.path.join("..", "..", "include", "fluca_hip_implicit.h"), os.path.join("..", "..", "include", "fluca_hip_implicit_ranks.h"), os.path.join("..", "..", "include", "fluca_hip_ibm_scalar.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
 MANIFEST = os.path.join(LIBDIR, "manifest.json")
@@ -140,7 +140,7 @@ HOST_LIB = os.path.join(LIBDIR, "libfluca_host.so")
 def build_host(force=False, verbose=False):
     """The C host mirror (gcc): links against libflucahip.so through its C-ABI only."""
     src = os.path.join(HERE, "host", "fluca_host.c")
-    hdrs = [os.path.normpath(os.path.join(HERE, "..", "include", h)) for h in ("fluca_host.h", "fluca_host_impl.h", "fluca_hip.h", "fluca_hip_implicit.h", "fluca_hip_ibm_scalar.h")]
+    hdrs = [os.path.normpath(os.path.join(HERE, "..", "include", h)) for h in ("fluca_host.h", "fluca_host_impl.h", "fluca_hip.h", "fluca_hip_implicit.h", "fluca_hip_implicit_ranks.h", "fluca_hip_ibm_scalar.h")]
     cmd = [os.environ.get("CC", "gcc"), "-std=gnu99", "-O2", "-fPIC", "-shared", "-Wall", "-o", HOST_LIB, src,
            "-L" + LIBDIR, "-lflucahip", "-Wl,-rpath,$ORIGIN", "-lm", "-ldl", "-pthread"]
     if force or _stale(HOST_LIB, [src, LIB] + hdrs, cmd):
@@ -173,7 +173,7 @@ def build_cgns(force=False, verbose=False):
         if verbose:
             print(f"no HDF5 under {HDF5_ROOT}: libfluca_cgns.so not built", flush=True)
         return None
-    hdrs = [os.path.normpath(os.path.join(HERE, "..", "include", h)) for h in ("fluca_cgns.h", "fluca_host.h", "fluca_host_impl.h", "fluca_hip.h", "fluca_hip_implicit.h", "fluca_hip_ibm_scalar.h")]
+    hdrs = [os.path.normpath(os.path.join(HERE, "..", "include", h)) for h in ("fluca_cgns.h", "fluca_host.h", "fluca_host_impl.h", "fluca_hip.h", "fluca_hip_implicit.h", "fluca_hip_implicit_ranks.h", "fluca_hip_ibm_scalar.h")]
     if True:
         # RUNPATH (new dtags), not RPATH: the HDF5 directory is searched for this library's direct dependencies only
         cmd = [os.environ.get("CC", "gcc"), "-std=gnu99", "-O2", "-fPIC", "-shared", "-Wall", "-o", CGNS_LIB, src,
@@ -200,7 +200,7 @@ def build_example(force=False, verbose=False, name="cavity_pressure_step"):
     cmd = [os.environ.get("CC", "gcc"), "-std=gnu99", "-O2", "-Wall", "-o", EXAMPLE, src, "-I" + os.path.join(root, "include"),
            "-L" + LIBDIR] + (["-DFLUCA_HAVE_CGNS", "-lfluca_cgns"] if cgns else []) + ["-lfluca_host", "-lflucahip", "-lm",
            "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,/opt/rocm/lib"]
-    deps = [src, HOST_LIB, LIB] + ([CGNS_LIB] if cgns else []) + [os.path.join(root, "include", h) for h in ("fluca_host.h", "fluca_hip.h", "fluca_hip_implicit.h", "fluca_hip_ibm_scalar.h", "fluca_cgns.h")]
+    deps = [src, HOST_LIB, LIB] + ([CGNS_LIB] if cgns else []) + [os.path.join(root, "include", h) for h in ("fluca_host.h", "fluca_hip.h", "fluca_hip_implicit.h", "fluca_hip_implicit_ranks.h", "fluca_hip_ibm_scalar.h", "fluca_cgns.h")]
     if os.path.exists(src) and (force or _stale(EXAMPLE, deps, cmd)):
         if verbose:
             print(" ".join(cmd), flush=True)

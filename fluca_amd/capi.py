@@ -205,7 +205,13 @@ PROTOTYPES_IBM_SCALAR = {
     "fl_ibm_scalar_force": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.POINTER(C.c_double), _P, _P, _P]),
     "fl_ibm_scalar_rate": (C.c_int, [_P, _P, _P, _P, C.c_int, C.POINTER(C.c_double)]),
 }
-for _name, (_res, _args) in list(PROTOTYPES.items()) + list(PROTOTYPES_IMPLICIT.items()) + list(PROTOTYPES_IBM_SCALAR.items()):
+# every symbol include/fluca_hip_implicit_ranks.h declares (tests/test_scalar_implicit_ranks_host.py checks that header against this table)
+PROTOTYPES_IMPLICIT_RANKS = {
+    "fl_scalar_diffusion_apply_ranks": PROTOTYPES_IMPLICIT["fl_scalar_diffusion_apply"],
+    "fl_scalar_diffusion_solve_ranks": PROTOTYPES_IMPLICIT["fl_scalar_diffusion_solve"],
+    "fl_scalar_step_imex_ranks": PROTOTYPES_IMPLICIT["fl_scalar_step_imex"],
+}
+for _name, (_res, _args) in list(PROTOTYPES.items()) + list(PROTOTYPES_IMPLICIT.items()) + list(PROTOTYPES_IBM_SCALAR.items()) + list(PROTOTYPES_IMPLICIT_RANKS.items()):
     _f = getattr(lib, _name)  # AttributeError if the library lacks a declared symbol
     _f.restype = _res
     _f.argtypes = _args

@@ -34,22 +34,6 @@ __device__ __forceinline__ double sc_face(bool up, double Pm, double Pp, double 
   return pu + al * limiter<L>(r) * (pd - pu);
 }
 
-// Several ranks: what differs from the one-rank sweep is where the cells outside the block come from.  One end of an axis of a rank's block:
-// nlo / nhi a neighbouring rank sits behind the low / high end, r the four layers received across them (np: lines of the plane, pr: this lane's line)
-struct ScEnds {
-  bool          nlo, nhi;
-  const double *r;
-  int64_t       np, pr;
-};
-// w at cell m of the line: behind an end with a neighbouring rank the cell -2, -1 / n, n+1 is layer m + 2 / m - n + 2 of e.r; elsewhere as
-// sc_ld.  Branches, not a selected address: along y and z they are wave-uniform, along x only the waves at the ends of a row take them.
-__device__ __forceinline__ double sc_ld_ring(const double *__restrict__ w, int64_t c0, int64_t cs, int m, int n, bool wraps, const ScEnds &e)
-{
-  if (m < 0 && e.nlo) return e.r[(m + 2) * e.np + e.pr];
-  if (m >= n && e.nhi) return e.r[(m - n + 2) * e.np + e.pr];
-  return sc_ld(w, c0, cs, m, n, wraps);
-}
-
 // The contribution of one axis to R at cell a of a line: [ -(V1 f1 - V0 f0) + Gamma (g(a+1) - g(a)) ] / h_a, with V0 / V1 the velocities
 // of the faces a / a+1.  klo / khi, vlo / vhi: kind and value of the boundaries at the ends of the axis (unused where it wraps).
 // RING (k_scalar_stage_ring): the five cells may come from the slabs of e, and an end with a neighbouring rank is no physical boundary -- the cell
@@ -211,16 +195,17 @@ __global__ void __launch_bounds__(256, sc_minblocks(L)) k_scalar_stage_ring(ScGr
 }
 
 // The send layers of the caller's phi (the first stage of a step, fl_scalar_rhs), in the layout the fused pack writes: blockIdx.y = boundary, all six
-// in one launch (a boundary without a neighbouring rank returns at once).
-__global__ void __launch_bounds__(256) k_scalar_pack(int nx, int ny, int nz, int nb, const double *__restrict__ phi, double *__restrict__ send)
+// in one launch (a boundary without a neighbouring rank returns at once).  nl: the layers packed -- 2, or 1 for the 7-point star of
+// fl_scalar_implicit.hip: the outermost cell alone, into the layer it has among the two (0 at a low end, 3 at a high end).
+__global__ void __launch_bounds__(256) k_scalar_pack(int nx, int ny, int nz, int nb, int nl, const double *__restrict__ phi, double *__restrict__ send)
 {
   const int b = blockIdx.y, d = b >> 1;
   if (!((nb >> b) & 1)) return;
   const int64_t nyz = (int64_t)ny * nz, nxz = (int64_t)nx * nz, nxy = (int64_t)nx * ny;
-  const int     n = d == 0 ? nx : (d == 1 ? ny : nz), a0 = (b & 1) ? n - 2 : 0;
+  const int     n = d == 0 ? nx : (d == 1 ? ny : nz), a0 = (b & 1) ? n - nl : 0;
   const int64_t np = d == 0 ? nyz : (d == 1 ? nxz : nxy);
-  double       *out = send + (d == 0 ? 0 : (d == 1 ? 4 * nyz : 4 * (nyz + nxz))) + (b & 1 ? 2 * np : 0);
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < 2 * np; t += (int64_t)gridDim.x * blockDim.x) {
+  double       *out = send + (d == 0 ? 0 : (d == 1 ? 4 * nyz : 4 * (nyz + nxz))) + (b & 1 ? (4 - nl) * np : 0);
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < nl * np; t += (int64_t)gridDim.x * blockDim.x) {
     const int     a = a0 + (int)(t / np);
     const int64_t pr = t % np;
     int64_t       c;
@@ -643,29 +628,39 @@ int scalar_new(fl_poisson *h, const int bc[6], bool ring, fl_scalar **out)
 // slabs.  ONE pair of slabs per boundary is enough: the transports are stream-ordered on either side (RCCL's Send / Recv; the host-staged callbacks
 // copy out of the send slab and into the receive slab on the handle's stream), so the receive of stage k + 1 is posted in stream order AFTER the
 // kernel that read stage k's slab, and the kernel that overwrites a send slab after the exchange that shipped it.
-int ring_exchange(fl_scalar *m)
+// nl = 1 (scalar_ring_exchange1): the outermost layer alone -- send layer 0 / 3 of a low / high end into the peer's receive layer 2 / 1 -- under tags of
+// its own (+320), so that no message of one kind can be taken for one of the other.
+int ring_exchange(fl_scalar *m, int nl = 2)
 {
   fl_poisson *h = m->h;
   fl_halo_msg plan[12];
   const int   np = fl_halo_messages(h, false, plan);
+  const int   tag = nl == 2 ? 256 : 320;
   std::vector<Msg> msgs;
   for (int a = 0; a < np; ++a) {
     const int sb = plan[a].send_boundary, rb = plan[a].recv_boundary;
     if (!((m->nb >> sb) & 1) || !((m->nb >> rb) & 1)) return FL_ERR_ARG_WRONGSTATE;
-    msgs.push_back({plan[a].peer, m->slab_send + slab_offset(h, sb), m->slab_recv + slab_offset(h, rb), 2 * (int64_t)fl_plane_size(h, sb / 2), plan[a].sendtag + 256,
-                    plan[a].recvtag + 256});
+    const size_t plane = (size_t)fl_plane_size(h, sb / 2), so = (nl == 1 && sb % 2) ? plane : 0, ro = (nl == 1 && rb % 2 == 0) ? plane : 0;
+    msgs.push_back({plan[a].peer, m->slab_send + slab_offset(h, sb) + so, m->slab_recv + slab_offset(h, rb) + ro, nl * (int64_t)plane, plan[a].sendtag + tag, plan[a].recvtag + tag});
   }
   return h->comm.exchange(h->stream, msgs);
+}
+
+// the send slabs of the caller's phi: nl layers per rank face
+int ring_pack(fl_scalar *m, const double *phi, int nl)
+{
+  size_t most = 0;
+  for (int b = 0; b < 6; ++b)
+    if ((m->nb >> b) & 1) most = std::max(most, nl * (size_t)fl_plane_size(m->h, b / 2));
+  if (most) hipLaunchKernelGGL(k_scalar_pack, dim3((unsigned)std::min<size_t>((most + 255) / 256, 1024), 6), dim3(256), 0, m->h->stream, m->g.nx, m->g.ny, m->g.nz, m->nb, nl, phi, m->slab_send);
+  FL_HIP(hipGetLastError());
+  return FL_SUCCESS;
 }
 
 // the send slabs of the caller's phi, then the exchange
 int ring_pack_exchange(fl_scalar *m, const double *phi)
 {
-  size_t most = 0;
-  for (int b = 0; b < 6; ++b)
-    if ((m->nb >> b) & 1) most = std::max(most, 2 * (size_t)fl_plane_size(m->h, b / 2));
-  if (most) hipLaunchKernelGGL(k_scalar_pack, dim3((unsigned)std::min<size_t>((most + 255) / 256, 1024), 6), dim3(256), 0, m->h->stream, m->g.nx, m->g.ny, m->g.nz, m->nb, phi, m->slab_send);
-  FL_HIP(hipGetLastError());
+  FL_CHK(ring_pack(m, phi, 2));
   return ring_exchange(m);
 }
 
@@ -781,7 +776,25 @@ extern "C" int fldbg_scalar_stage_only(fl_scalar *m, const double *phi_dev, cons
 // w <- phi; s - 1 times w <- w + dt / (s - 1) R(w); phi <- ((s - 1) w + phi + dt R(w)) / s.  One launch per stage; the stage vectors alternate between
 // the handle's two work arrays, and the last stage writes phi in place (it reads of phi only the cell it writes) -- or, for fl_scalar_step_imex, into
 // an array of the handle's.
-int fl::scalar_ssp_step(fl_scalar *m, double dt, int nstages, const double *source_dev, const double *phi_dev, double *out_dev)
+// Not part of the public C-ABI (tests): every word of both slabs of a handle of fl_scalar_create_ranks becomes a NaN (all bits set), in stream order -- a call
+// that read a layer it had not received or packed itself would show it
+extern "C" int fldbg_scalar_poison_slabs(fl_scalar *m)
+{
+  if (!m) return FL_ERR_ARG_NULL;
+  if (!m->ring) return FL_ERR_SUP;
+  FL_HIP(hipSetDevice(m->h->device));
+  const size_t bytes = sizeof(double) * slab_offset(m->h, 6);
+  if (bytes) {
+    FL_HIP(hipMemsetAsync(m->slab_recv, 0xFF, bytes, m->h->stream));
+    FL_HIP(hipMemsetAsync(m->slab_send, 0xFF, bytes, m->h->stream));
+  }
+  return FL_SUCCESS;
+}
+
+int fl::scalar_ring_pack1(fl_scalar *m, const double *phi_dev) { return ring_pack(m, phi_dev, 1); }
+int fl::scalar_ring_exchange1(fl_scalar *m) { return ring_exchange(m, 1); }
+
+int fl::scalar_ssp_step(fl_scalar *m, double dt, int nstages, const double *source_dev, const double *phi_dev, double *out_dev, bool pack_last)
 {
   FL_HIP(hipSetDevice(m->h->device));
   for (int a = 0; a < (nstages > 2 ? 2 : 1); ++a)
@@ -799,7 +812,7 @@ int fl::scalar_ssp_step(fl_scalar *m, double dt, int nstages, const double *sour
     if (m->ring) FL_CHK(ring_exchange(m));
     w = o;
   }
-  STAGE[m->limiter](m, StageArgs{1. / s, (s - 1.) / s, dt / s, phi_dev, w, source_dev, out_dev, false});
+  STAGE[m->limiter](m, StageArgs{1. / s, (s - 1.) / s, dt / s, phi_dev, w, source_dev, out_dev, m->ring && pack_last});
   FL_HIP(hipGetLastError());
   return FL_SUCCESS;
 }
@@ -809,7 +822,7 @@ extern "C" int fl_scalar_step(fl_scalar *m, double dt, int nstages, const double
   if (!m || !phi_dev) return FL_ERR_ARG_NULL;
   if (nstages < 2 || !std::isfinite(dt)) return FL_ERR_ARG_OUTOFRANGE;
   if (!m->V[0]) return FL_ERR_ARG_WRONGSTATE;
-  return scalar_ssp_step(m, dt, nstages, source_dev, phi_dev, phi_dev);
+  return scalar_ssp_step(m, dt, nstages, source_dev, phi_dev, phi_dev, false);
 }
 
 extern "C" int fl_scalar_cfl(fl_scalar *m, double dt, double out[2])

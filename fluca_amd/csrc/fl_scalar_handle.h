@@ -29,6 +29,22 @@ __device__ __forceinline__ double sc_ld(const double *__restrict__ w, int64_t c0
   return w[c0 + m * cs];
 }
 
+// Several ranks: what differs from the one-rank sweep is where the cells outside the block come from.  One end of an axis of a rank's block:
+// nlo / nhi a neighbouring rank sits behind the low / high end, r the four layers received across them (np: lines of the plane, pr: this lane's line)
+struct ScEnds {
+  bool          nlo, nhi;
+  const double *r;
+  int64_t       np, pr;
+};
+// w at cell m of the line: behind an end with a neighbouring rank the cell -2, -1 / n, n+1 is layer m + 2 / m - n + 2 of e.r; elsewhere as
+// sc_ld.  Branches, not a selected address: along y and z they are wave-uniform, along x only the waves at the ends of a row take them.
+__device__ __forceinline__ double sc_ld_ring(const double *__restrict__ w, int64_t c0, int64_t cs, int m, int n, bool wraps, const ScEnds &e)
+{
+  if (m < 0 && e.nlo) return e.r[(m + 2) * e.np + e.pr];
+  if (m >= n && e.nhi) return e.r[(m - n + 2) * e.np + e.pr];
+  return sc_ld(w, c0, cs, m, n, wraps);
+}
+
 }  // namespace fl
 
 struct fl_scalar {
@@ -56,7 +72,15 @@ struct fl_scalar {
 namespace fl {
 
 // fl_scalar.hip: the stages of fl_scalar_step over dt, reading phi^n from phi_dev and writing the new phi to out_dev (phi_dev itself, or an array that
-// is neither phi_dev nor a work array); the arguments are checked by the callers
-int scalar_ssp_step(fl_scalar *m, double dt, int nstages, const double *source_dev, const double *phi_dev, double *out_dev);
+// is neither phi_dev nor a work array); the arguments are checked by the callers.  pack_last (several ranks): the last stage fills the send slabs
+// with what it writes, as every other stage does -- for a caller that exchanges out_dev next (fl_scalar_step_imex_ranks)
+int scalar_ssp_step(fl_scalar *m, double dt, int nstages, const double *source_dev, const double *phi_dev, double *out_dev, bool pack_last);
+
+// fl_scalar.hip, several ranks, ONE layer per rank face (the 7-point star of fl_scalar_implicit.hip): the cell 0 / n - 1 of an axis is the send layer
+// 0 / 3 of that axis, the cell -1 / n the receive layer 1 / 2 -- where the two-layer exchange of the stages keeps the same cells, so a stage that
+// packs leaves what scalar_ring_exchange1 sends.  scalar_ring_pack1: those send layers from the caller's array (a launch, no message);
+// scalar_ring_exchange1: one message of one plane per rank face, on the handle's stream.
+int scalar_ring_pack1(fl_scalar *m, const double *phi_dev);
+int scalar_ring_exchange1(fl_scalar *m);
 
 }  // namespace fl

@@ -13,21 +13,39 @@
 // from the cell's three table rows -- no diagonal array, no padded copy.  d in place, x' into the other x array.  x 8 + b 8 + d 8 read, x' 8 + d' 8
 // written = 40 B/cell (32 in the first step, which does not read d).  The sweep is k_scalar_stage's: XCD-banded rows, a wave keeps one x segment when the
 // launch allows it, b and d non-temporal.  No velocities and no limiter: 8 waves a SIMD (profiles/scalar_implicit_devcode.txt), no scratch.
+//
+// Several ranks (include/fluca_hip_implicit_ranks.h, k_scalar_cheb_ring): the same sweep over the rank's block.  The star reaches one cell across a rank face, so
+// ONE plane per face travels per step, through the slabs and the message plan of fl_scalar.hip (scalar_ring_exchange1); a step that is not the last also stores
+// the cells it writes next to a rank face into the send layers, so one exchange and one launch stand between two steps.  The interval is that of the GLOBAL
+// tables on every rank: the same count everywhere, no vote, no reduction -- and, cell for cell, the operations and operands of the one-rank kernel: the gathered
+// result has its bits.  The exchange is not overlapped with the sweep (fl_scalar.hip's decision for the stages, for the same reason).
 #include "fl_device.h"
 #include "fl_handle.h"
 #include "fl_scalar_handle.h"
 #include "../../include/fluca_hip_implicit.h"
+#include "../../include/fluca_hip_implicit_ranks.h"
 
 namespace fl {
 
 // The contribution of one axis to D at cell a of a line, and to the diagonal of -L (dg).  ic1 / ic2: 1 / distance of the faces a / a+1, ih: 1 / width.
 // The gradients are sc_axis's G1, G2 with its boundary rule; a face adds its ic to the diagonal where phi_a enters its gradient with a partner: an interior or
 // periodic face (not the face of a one-cell periodic axis, whose partner is the cell itself) and a Dirichlet face.
+// RING (k_scalar_cheb_ring): behind an end with a neighbouring rank the cell -1 / n comes from the slabs of e, and that end is no physical boundary -- its
+// face is an interior face, its ic on the diagonal.  Only the two loads and the predicates lo0 / hi0 differ; the arithmetic is this one piece of source.
+template <bool RING>
 __device__ __forceinline__ double hc_axis(double ic1, double ic2, double ih, const double *__restrict__ x, double P2, int a, int n, bool wraps, int klo, int khi, double vlo, double vhi, int64_t c0,
-                                          int64_t cs, double &dg)
+                                          int64_t cs, const ScEnds &e, double &dg)
 {
-  double     Pm = sc_ld(x, c0, cs, a - 1, n, wraps), Pp = sc_ld(x, c0, cs, a + 1, n, wraps);
-  const bool lo0 = !wraps && a == 0, hi0 = !wraps && a == n - 1, self = wraps && n == 1;
+  double Pm, Pp;
+  bool   lo0, hi0;
+  if constexpr (RING) {
+    Pm = sc_ld_ring(x, c0, cs, a - 1, n, wraps, e), Pp = sc_ld_ring(x, c0, cs, a + 1, n, wraps, e);
+    lo0 = !wraps && !e.nlo && a == 0, hi0 = !wraps && !e.nhi && a == n - 1;
+  } else {
+    Pm = sc_ld(x, c0, cs, a - 1, n, wraps), Pp = sc_ld(x, c0, cs, a + 1, n, wraps);
+    lo0 = !wraps && a == 0, hi0 = !wraps && a == n - 1;
+  }
+  const bool self = wraps && n == 1;
   if (klo == 0 && lo0) Pm = vlo;
   if (khi == 0 && hi0) Pp = vhi;
   double G1 = (P2 - Pm) * ic1, G2 = (Pp - P2) * ic2;
@@ -56,6 +74,7 @@ __global__ void __launch_bounds__(256, HC_WAVES) k_scalar_cheb(ScGrid g, double 
   const bool   fixed_seg = ((int64_t)nlb * nw) % nseg == 0;
   const int    seg0 = (int)(((int64_t)lb * nw + wv) % nseg), i0 = min(seg0 * 64 + lane, g.nx - 1);
   const double xa0 = g.c[0][i0].ic1, xb0 = g.c[0][i0].ic2, xh0 = g.c[0][i0].ih;
+  const ScEnds none = {false, false, nullptr, 0, 0};  // (one rank: not read)
   for (int64_t it = (int64_t)lb * nw + wv; it < nitem; it += (int64_t)nlb * nw) {
     const int seg = (int)(it % nseg), row = (int)(it / nseg);
     const int j = j0 + row % nj, k = row / nj, i = seg * 64 + lane;
@@ -64,9 +83,9 @@ __global__ void __launch_bounds__(256, HC_WAVES) k_scalar_cheb(ScGrid g, double 
     const ScCell &TX = g.c[0][i], &TY = g.c[1][j], &TZ = g.c[2][k];
     const double  P2 = x[c];
     double        dg = 0.;
-    double        D = hc_axis(fixed_seg ? xa0 : TX.ic1, fixed_seg ? xb0 : TX.ic2, fixed_seg ? xh0 : TX.ih, x, P2, i, g.nx, wx, g.kind[0], g.kind[1], g.val[0], g.val[1], urow, 1, dg);
-    D += hc_axis(TY.ic1, TY.ic2, TY.ih, x, P2, j, g.ny, wy, g.kind[2], g.kind[3], g.val[2], g.val[3], (int64_t)k * nxy + i, g.nx, dg);
-    D += hc_axis(TZ.ic1, TZ.ic2, TZ.ih, x, P2, k, g.nz, wz, g.kind[4], g.kind[5], g.val[4], g.val[5], (int64_t)j * g.nx + i, nxy, dg);
+    double        D = hc_axis<false>(fixed_seg ? xa0 : TX.ic1, fixed_seg ? xb0 : TX.ic2, fixed_seg ? xh0 : TX.ih, x, P2, i, g.nx, wx, g.kind[0], g.kind[1], g.val[0], g.val[1], urow, 1, none, dg);
+    D += hc_axis<false>(TY.ic1, TY.ic2, TY.ih, x, P2, j, g.ny, wy, g.kind[2], g.kind[3], g.val[2], g.val[3], (int64_t)k * nxy + i, g.nx, none, dg);
+    D += hc_axis<false>(TZ.ic1, TZ.ic2, TZ.ih, x, P2, k, g.nz, wz, g.kind[4], g.kind[5], g.val[4], g.val[5], (int64_t)j * g.nx + i, nxy, none, dg);
     if (MODE == 2) {
       __builtin_nontemporal_store(P2 - cc * D, xo + c);
     } else if (MODE == 3) {
@@ -77,6 +96,71 @@ __global__ void __launch_bounds__(256, HC_WAVES) k_scalar_cheb(ScGrid g, double 
       if (MODE == 0) dn += p * __builtin_nontemporal_load(d + c);
       __builtin_nontemporal_store(dn, d + c);
       xo[c] = P2 + dn;  // (the next step reads it through the star: not non-temporal)
+    }
+  }
+}
+
+// What a rank's block of several reads and writes beside its own arrays (wave-uniform: scalar registers): the handle's slabs (ScRing of fl_scalar.hip; of an
+// axis's four layers this star reads the receive layers 1, 2 -- the cells -1, n -- and fills the send layers 0, 3 -- the cells 0, n - 1).  nb: bit 2 d / 2 d + 1
+// = a neighbouring rank behind the low / high end of axis d.  pack: the boundaries (bits as nb) whose send layer this step fills with x' -- 0 in the last step
+// of a solve and in the modes 2, 3.
+struct HcRing {
+  const double *recv;
+  double       *send;
+  int           nb, pack;
+};
+
+// k_scalar_cheb on one rank's block of several: the same sweep, plan, modes and arithmetic; g: the block (per: the periodic axes the rank holds alone), the
+// tables cut to its rows, so a cell runs the operations of the one-rank kernel on its operands.
+template <int MODE>
+__global__ void __launch_bounds__(256, HC_WAVES) k_scalar_cheb_ring(ScGrid g, HcRing rg, double cc, double p, double q, const double *__restrict__ x, const double *__restrict__ b,
+                                                                   double *__restrict__ d, double *__restrict__ xo)
+{
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+  const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, nlb = gridDim.x >> 3;
+  const int band = (g.ny + 7) / 8, j0 = xcd * band, j1 = min(j0 + band, g.ny);
+  if (j0 >= j1) return;
+  const int     nseg = (g.nx + 63) / 64, nj = j1 - j0;
+  const int64_t nitem = (int64_t)nseg * nj * g.nz, nxy = (int64_t)g.nx * g.ny, nyz = (int64_t)g.ny * g.nz, nxz = (int64_t)g.nx * g.nz;
+  const bool    wx = g.per & 1, wy = g.per & 2, wz = g.per & 4;
+  const bool    lx = rg.nb & 1, hx = rg.nb & 2, ly = rg.nb & 4, hy = rg.nb & 8, lz = rg.nb & 16, hz = rg.nb & 32;
+  const bool    fixed_seg = ((int64_t)nlb * nw) % nseg == 0;
+  const int     seg0 = (int)(((int64_t)lb * nw + wv) % nseg), i0 = min(seg0 * 64 + lane, g.nx - 1);
+  const double  xa0 = g.c[0][i0].ic1, xb0 = g.c[0][i0].ic2, xh0 = g.c[0][i0].ih;
+  for (int64_t it = (int64_t)lb * nw + wv; it < nitem; it += (int64_t)nlb * nw) {
+    const int seg = (int)(it % nseg), row = (int)(it / nseg);
+    const int j = j0 + row % nj, k = row / nj, i = seg * 64 + lane;
+    if (i >= g.nx) continue;
+    const int64_t prx = (int64_t)k * g.ny + j, pry = (int64_t)k * g.nx + i, prz = (int64_t)j * g.nx + i;  // this cell's line in the planes across x / y / z
+    const int64_t urow = prx * g.nx, c = urow + i;
+    const ScCell &TX = g.c[0][i], &TY = g.c[1][j], &TZ = g.c[2][k];
+    const double  P2 = x[c];
+    double        dg = 0.;
+    double        D = hc_axis<true>(fixed_seg ? xa0 : TX.ic1, fixed_seg ? xb0 : TX.ic2, fixed_seg ? xh0 : TX.ih, x, P2, i, g.nx, wx, g.kind[0], g.kind[1], g.val[0], g.val[1], urow, 1,
+                                    ScEnds{lx, hx, rg.recv, nyz, prx}, dg);
+    D += hc_axis<true>(TY.ic1, TY.ic2, TY.ih, x, P2, j, g.ny, wy, g.kind[2], g.kind[3], g.val[2], g.val[3], (int64_t)k * nxy + i, g.nx, ScEnds{ly, hy, rg.recv + 4 * nyz, nxz, pry}, dg);
+    D += hc_axis<true>(TZ.ic1, TZ.ic2, TZ.ih, x, P2, k, g.nz, wz, g.kind[4], g.kind[5], g.val[4], g.val[5], prz, nxy, ScEnds{lz, hz, rg.recv + 4 * (nyz + nxz), nxy, prz}, dg);
+    if (MODE == 2) {
+      __builtin_nontemporal_store(P2 - cc * D, xo + c);
+    } else if (MODE == 3) {
+      __builtin_nontemporal_store(-(cc * D), xo + c);
+    } else {
+      const double r = __builtin_nontemporal_load(b + c) - (P2 - cc * D);
+      double       dn = q * (r / (1. + cc * dg));
+      if (MODE == 0) dn += p * __builtin_nontemporal_load(d + c);
+      __builtin_nontemporal_store(dn, d + c);
+      const double xn = P2 + dn;
+      xo[c] = xn;
+      // the fused pack: the next step's exchange sends these layers as they are
+      if (rg.pack) {
+        double *const sx = rg.send, *const sy = sx + 4 * nyz, *const sz = sy + 4 * nxz;
+        if ((rg.pack & 1) && i == 0) sx[prx] = xn;
+        if ((rg.pack & 2) && i == g.nx - 1) sx[3 * nyz + prx] = xn;
+        if ((rg.pack & 4) && j == 0) sy[pry] = xn;
+        if ((rg.pack & 8) && j == g.ny - 1) sy[3 * nxz + pry] = xn;
+        if ((rg.pack & 16) && k == 0) sz[prz] = xn;
+        if ((rg.pack & 32) && k == g.nz - 1) sz[3 * nxy + prz] = xn;
+      }
     }
   }
 }
@@ -161,10 +245,16 @@ int implicit_interval(fl_scalar *m, double c, double *emin, double *emax, double
   return FL_SUCCESS;
 }
 
+// pack (several ranks, modes 0 and 1): the step also fills the send layers with x', for the exchange of the step after it
 template <int MODE>
-void launch_cheb(const fl_scalar *m, double c, double p, double q, const double *x, const double *b, double *d, double *xo)
+void launch_cheb(const fl_scalar *m, double c, double p, double q, const double *x, const double *b, double *d, double *xo, bool pack = false)
 {
   const dim3 grid(8 * cheb_plan(m->g.nx, m->g.ny, m->g.nz).per_xcd);
+  if (m->ring) {
+    const HcRing rg = {m->slab_recv, m->slab_send, m->nb, (pack && MODE < 2) ? m->nb : 0};
+    hipLaunchKernelGGL((k_scalar_cheb_ring<MODE>), grid, dim3(256), 0, m->h->stream, m->g, rg, c, p, q, x, b, d, xo);
+    return;
+  }
   hipLaunchKernelGGL((k_scalar_cheb<MODE>), grid, dim3(256), 0, m->h->stream, m->g, c, p, q, x, b, d, xo);
 }
 
@@ -180,6 +270,9 @@ int implicit_arrays(fl_scalar *m, bool with_b)
 // the handle's other iterate, step 2 x_dev, and so on: an even count ends in x_dev.  d: work[0], the other iterate: work[1].
 //   theta_c = (emax + emin) / 2, delta = (emax - emin) / 2, sigma_1 = theta_c / delta, rho_0 = 1 / sigma_1, d_0 = r_0 / theta_c;
 //   rho_j = 1 / (2 sigma_1 - rho_{j-1}), d_j = rho_j rho_{j-1} d_{j-1} + (2 rho_j / delta) r_j             (r: the Jacobi-preconditioned residual)
+// Several ranks: the send layers hold the guess's outermost cells when this is called (scalar_ring_pack1, or a stage that packed); every step is one
+// one-plane exchange and one launch, and every step but the last fills the send layers with its x'.  The count is host arithmetic on the global tables --
+// the same on every rank -- so nothing is voted and nothing reduced.
 int cheb_launches(fl_scalar *m, double c, const fl_scalar_cheb_info &info, const double *b, const double *x0, double *x_dev)
 {
   const double theta = 0.5 * (info.emax + info.emin), delta = 0.5 * (info.emax - info.emin), sigma1 = theta / delta;
@@ -187,11 +280,13 @@ int cheb_launches(fl_scalar *m, double c, const fl_scalar_cheb_info &info, const
   double      *d = m->work[0], *other = m->work[1];
   const double *xin = x0;
   for (int j = 1; j <= info.steps; ++j) {
-    double *xout = (j & 1) ? other : x_dev;
-    if (j == 1) launch_cheb<1>(m, c, 0., 1. / theta, xin, b, d, xout);
+    double    *xout = (j & 1) ? other : x_dev;
+    const bool pack = j < info.steps;
+    if (m->ring) FL_CHK(scalar_ring_exchange1(m));
+    if (j == 1) launch_cheb<1>(m, c, 0., 1. / theta, xin, b, d, xout, pack);
     else {
       const double rho_new = 1. / (2. * sigma1 - rho);
-      launch_cheb<0>(m, c, rho_new * rho, 2. * rho_new / delta, xin, b, d, xout);
+      launch_cheb<0>(m, c, rho_new * rho, 2. * rho_new / delta, xin, b, d, xout, pack);
       rho = rho_new;
     }
     xin = xout;
@@ -250,24 +345,47 @@ extern "C" int fl_scalar_diffusion_interval(fl_scalar *m, double c, double *emin
   return implicit_interval(m, c, emin, emax, nullptr);
 }
 
-extern "C" int fl_scalar_diffusion_apply(fl_scalar *m, double c, const double *phi_dev, double *out_dev)
+// Not part of the public C-ABI (tools/scalar_implicit_bench.py --ring): fldbg_scalar_cheb_one on a handle of fl_scalar_create_ranks -- ONE launch of
+// k_scalar_cheb_ring, no exchange, the slabs as the last collective call left them -- so that one rank can time the kernel while its peers idle.  pack != 0:
+// the step also fills the send layers, as every step of a solve but the last does.
+extern "C" int fldbg_scalar_cheb_ring_one(fl_scalar *m, double c, double p, double q, int first, int pack, const double *x_dev, const double *b_dev, double *d_dev, double *xo_dev)
+{
+  if (!m || !x_dev || !b_dev || !d_dev || !xo_dev) return FL_ERR_ARG_NULL;
+  if (x_dev == xo_dev) return FL_ERR_ARG_WRONG;
+  if (!m->ring) return FL_ERR_SUP;
+  FL_HIP(hipSetDevice(m->h->device));
+  if (first) launch_cheb<1>(m, c, p, q, x_dev, b_dev, d_dev, xo_dev, pack != 0);
+  else launch_cheb<0>(m, c, p, q, x_dev, b_dev, d_dev, xo_dev, pack != 0);
+  FL_HIP(hipGetLastError());
+  return FL_SUCCESS;
+}
+
+namespace {
+
+// The three calls on either kind of handle.  ranks: entered through include/fluca_hip_implicit_ranks.h -- the names of fluca_hip_implicit.h refuse a rank's block
+// of several.  On a one-rank handle m->ring is false and every line below that asks for it is skipped: the same launches either way.
+int diffusion_apply(fl_scalar *m, double c, const double *phi_dev, double *out_dev, bool ranks)
 {
   if (!m || !phi_dev || !out_dev) return FL_ERR_ARG_NULL;
   if (bad_c(c)) return FL_ERR_ARG_OUTOFRANGE;
   if (phi_dev == out_dev) return FL_ERR_ARG_WRONG;  // neighbours still read phi
-  if (m->ring) return FL_ERR_SUP;
+  if (m->ring && !ranks) return FL_ERR_SUP;
   FL_HIP(hipSetDevice(m->h->device));
+  if (m->ring) {
+    FL_CHK(scalar_ring_pack1(m, phi_dev));
+    FL_CHK(scalar_ring_exchange1(m));
+  }
   launch_cheb<2>(m, c, 0., 0., phi_dev, nullptr, nullptr, out_dev);
   FL_HIP(hipGetLastError());
   return FL_SUCCESS;
 }
 
-extern "C" int fl_scalar_diffusion_solve(fl_scalar *m, double c, double rtol, int maxit, const double *b_dev, double *x_dev, fl_scalar_cheb_info *info)
+int diffusion_solve(fl_scalar *m, double c, double rtol, int maxit, const double *b_dev, double *x_dev, fl_scalar_cheb_info *info, bool ranks)
 {
   if (!m || !b_dev || !x_dev) return FL_ERR_ARG_NULL;
   if (bad_c(c) || bad_solve_args(rtol, maxit)) return FL_ERR_ARG_OUTOFRANGE;
   if (b_dev == x_dev) return FL_ERR_ARG_WRONG;
-  if (m->ring) return FL_ERR_SUP;
+  if (m->ring && !ranks) return FL_ERR_SUP;
   fl_scalar_cheb_info I;
   double              S = 0.;
   FL_CHK(cheb_prepare(m, c, rtol, maxit, &I, &S));
@@ -275,41 +393,79 @@ extern "C" int fl_scalar_diffusion_solve(fl_scalar *m, double c, double rtol, in
   if (S == 0.) FL_HIP(hipMemcpyAsync(x_dev, b_dev, sizeof(double) * (size_t)m->h->ncell, hipMemcpyDeviceToDevice, m->h->stream));
   else if (I.steps > 0) {
     FL_CHK(implicit_arrays(m, false));
+    if (m->ring) FL_CHK(scalar_ring_pack1(m, x_dev));
     FL_CHK(cheb_launches(m, c, I, b_dev, x_dev, x_dev));
   }
   if (info) *info = I;
   return FL_SUCCESS;
 }
 
-extern "C" int fl_scalar_step_imex(fl_scalar *m, double dt, int nstages, double theta, double rtol, int maxit, const double *source_dev, double *phi_dev,
-                                   fl_scalar_cheb_info *info)
+int step_imex(fl_scalar *m, double dt, int nstages, double theta, double rtol, int maxit, const double *source_dev, double *phi_dev, fl_scalar_cheb_info *info, bool ranks)
 {
   if (!m || !phi_dev) return FL_ERR_ARG_NULL;
   if (nstages < 2 || !std::isfinite(dt) || !(dt >= 0.) || !(theta >= 0.5) || !(theta <= 1.) || bad_solve_args(rtol, maxit)) return FL_ERR_ARG_OUTOFRANGE;
-  if (m->ring) return FL_ERR_SUP;
+  if (m->ring && !ranks) return FL_ERR_SUP;
   if (!m->V[0]) return FL_ERR_ARG_WRONGSTATE;
   const double gamma = m->g.gamma, c = theta * dt * gamma, ce = (1. - theta) * dt * gamma;
   fl_scalar_cheb_info I;
   double              S = 0.;
   FL_CHK(cheb_prepare(m, c, rtol, maxit, &I, &S));
   if (info) *info = I;
-  if (gamma == 0.) return scalar_ssp_step(m, dt, nstages, source_dev, phi_dev, phi_dev);  // fl_scalar_step, launch for launch
+  if (gamma == 0.) return scalar_ssp_step(m, dt, nstages, source_dev, phi_dev, phi_dev, false);  // fl_scalar_step, launch for launch and message for message
   FL_HIP(hipSetDevice(m->h->device));
   FL_CHK(implicit_arrays(m, true));
   const size_t ncell = (size_t)m->h->ncell;
   const bool   cn = ce != 0.;
   // theta < 1: the explicit share of the diffusion, from phi^n (before the stages overwrite it)
-  if (cn) launch_cheb<3>(m, -ce, 0., 0., phi_dev, nullptr, nullptr, m->imex_b);
+  if (cn) {
+    if (m->ring) {
+      FL_CHK(scalar_ring_pack1(m, phi_dev));
+      FL_CHK(scalar_ring_exchange1(m));
+    }
+    launch_cheb<3>(m, -ce, 0., 0., phi_dev, nullptr, nullptr, m->imex_b);
+  }
   // The stages with Gamma = 0 (the value travels with each launch).  theta = 1 with steps to run: phi* lands in the right-hand side's array, which is then
-  // also the guess -- the first step reads it there, the last writes phi_dev.  Otherwise in place.
+  // also the guess -- the first step reads it there, the last writes phi_dev.  Otherwise in place.  Several ranks: that last stage fills the send layers as
+  // well, so the first Chebyshev step's exchange follows it with no pack launch in between.
   const bool to_b = !cn && I.steps > 0;
   m->g.gamma = 0.;
-  const int rc = scalar_ssp_step(m, dt, nstages, source_dev, phi_dev, to_b ? m->imex_b : phi_dev);
+  const int rc = scalar_ssp_step(m, dt, nstages, source_dev, phi_dev, to_b ? m->imex_b : phi_dev, to_b);
   m->g.gamma = gamma;
   FL_CHK(rc);
   if (to_b) return cheb_launches(m, c, I, m->imex_b, m->imex_b, phi_dev);
   if (!cn) return FL_SUCCESS;  // (no step to run: x = b = the guess = phi*)
   hipLaunchKernelGGL(k_scalar_addto, dim3((unsigned)std::min<size_t>((ncell + 255) / 256, 8192)), dim3(256), 0, m->h->stream, (int64_t)ncell, phi_dev, m->imex_b);
   if (S == 0.) FL_HIP(hipMemcpyAsync(phi_dev, m->imex_b, sizeof(double) * ncell, hipMemcpyDeviceToDevice, m->h->stream));
+  if (m->ring && I.steps > 0) FL_CHK(scalar_ring_pack1(m, phi_dev));  // the guess phi*
   return cheb_launches(m, c, I, m->imex_b, phi_dev, phi_dev);
+}
+
+}  // namespace
+
+extern "C" int fl_scalar_diffusion_apply(fl_scalar *m, double c, const double *phi_dev, double *out_dev) { return diffusion_apply(m, c, phi_dev, out_dev, false); }
+
+extern "C" int fl_scalar_diffusion_solve(fl_scalar *m, double c, double rtol, int maxit, const double *b_dev, double *x_dev, fl_scalar_cheb_info *info)
+{
+  return diffusion_solve(m, c, rtol, maxit, b_dev, x_dev, info, false);
+}
+
+extern "C" int fl_scalar_step_imex(fl_scalar *m, double dt, int nstages, double theta, double rtol, int maxit, const double *source_dev, double *phi_dev,
+                                   fl_scalar_cheb_info *info)
+{
+  return step_imex(m, dt, nstages, theta, rtol, maxit, source_dev, phi_dev, info, false);
+}
+
+// ------------------------------------------------------------------------------------------------ include/fluca_hip_implicit_ranks.h
+
+extern "C" int fl_scalar_diffusion_apply_ranks(fl_scalar *m, double c, const double *phi_dev, double *out_dev) { return diffusion_apply(m, c, phi_dev, out_dev, true); }
+
+extern "C" int fl_scalar_diffusion_solve_ranks(fl_scalar *m, double c, double rtol, int maxit, const double *b_dev, double *x_dev, fl_scalar_cheb_info *info)
+{
+  return diffusion_solve(m, c, rtol, maxit, b_dev, x_dev, info, true);
+}
+
+extern "C" int fl_scalar_step_imex_ranks(fl_scalar *m, double dt, int nstages, double theta, double rtol, int maxit, const double *source_dev, double *phi_dev,
+                                         fl_scalar_cheb_info *info)
+{
+  return step_imex(m, dt, nstages, theta, rtol, maxit, source_dev, phi_dev, info, true);
 }

@@ -729,6 +729,7 @@ FlErrorCode NSCreate(NS *ns)
   n->scalar_stages = 5; /* the reference's -ts_type ssp default */
   n->scalar_theta  = 0.;
   n->scalar_rtol   = 1e-6;
+  n->scalar_implicit_ranks = 0;
   n->scalar_ibm_passes = 1;
   n->bc_keep           = 1;
   fl_ksp_opts_default(&n->schur);
@@ -895,6 +896,11 @@ FlErrorCode NSSetFromOptions(NS ns, int argc, char **argv)
   if (opt_real(argc, argv, "-ns_scalar_implicit_rtol", &v)) {
     if (!(v > 0. && v < 1.)) return E_ARG_OUTOFRANGE;
     ns->scalar_rtol = v;
+  }
+  /* ... and whether the two options above also reach scalars added on a several-rank mesh (NSSetScalarImplicitRanks; default 0: they stay explicit there) */
+  if (opt_int64(argc, argv, "-ns_scalar_implicit_ranks", &iv)) {
+    if (iv < 0 || iv > 1) return E_ARG_OUTOFRANGE;
+    ns->scalar_implicit_ranks = (int)iv;
   }
   /* mirror only: the passes NSSetScalarImmersedBoundary(npass = -1) takes */
   if (opt_int64(argc, argv, "-ns_scalar_ibm_passes", &iv)) {
@@ -1426,10 +1432,14 @@ static FlErrorCode scalars_step(NS ns)
       if (forced) sc->ibm_sum_ready = 1, sc->ibm_sum_dt = ns->dt;
       continue;
     }
-    /* implicit diffusion (NSSetScalarImplicit): the stages without the diffusion term, then a fixed number of Chebyshev launches -- nothing waits */
+    /* implicit diffusion (NSSetScalarImplicit): the stages without the diffusion term, then a fixed number of Chebyshev launches -- nothing waits.  On a
+     * several-rank mesh (NSSetScalarImplicitRanks) the collective call: one plane of phi across every rank face per Chebyshev launch, still no reduction */
     for (int k = 0; k < sc->substeps; ++k) {
       fl_scalar_cheb_info info;
-      FLABI(fl_scalar_step_imex(sc->h, ns->dt / sc->substeps, ns->scalar_stages, sc->theta, sc->rtol, NS_SCALAR_CHEB_MAXIT, sc->src, sc->phi, &info));
+      if (ns->mesh->size > 1)
+        FLABI(fl_scalar_step_imex_ranks(sc->h, ns->dt / sc->substeps, ns->scalar_stages, sc->theta, sc->rtol, NS_SCALAR_CHEB_MAXIT, sc->src, sc->phi, &info));
+      else
+        FLABI(fl_scalar_step_imex(sc->h, ns->dt / sc->substeps, ns->scalar_stages, sc->theta, sc->rtol, NS_SCALAR_CHEB_MAXIT, sc->src, sc->phi, &info));
       sc->cheb_steps = info.steps;
       sc->cheb_bound = info.bound;
       if (forced) FLCHK(scalar_ibm_force(ns, sc));
@@ -1485,7 +1495,8 @@ FlErrorCode NSAddScalar(NS ns, const char *name, double gamma, const char *limit
   sc->gamma    = gamma;
   sc->limiter  = limiter;
   sc->substeps = 1;
-  sc->theta    = ns->mesh->size > 1 ? 0. : ns->scalar_theta; /* (several ranks: the option does not apply, NSSetScalarImplicit says E_SUP) */
+  /* (several ranks: the option applies with -ns_scalar_implicit_ranks 1 alone, as NSSetScalarImplicit says E_SUP there and NSSetScalarImplicitRanks does not) */
+  sc->theta    = (ns->mesh->size > 1 && !ns->scalar_implicit_ranks) ? 0. : ns->scalar_theta;
   sc->rtol     = ns->scalar_rtol;
   sc->cheb_bound = 1.;
   Mesh_Cart *cart = (Mesh_Cart *)ns->mesh->data;
@@ -1541,6 +1552,15 @@ FlErrorCode NSSetScalarImplicit(NS ns, int id, double theta, double rtol)
   if (!(theta == 0. || (theta >= 0.5 && theta <= 1.)) || !(rtol > 0. && rtol < 1.)) return E_ARG_OUTOFRANGE;
   if (theta != 0. && ns->mesh->size > 1) return E_SUP; /* fl_scalar_step_imex runs on one rank */
   sc->theta = theta;
+  sc->rtol  = rtol;
+  return 0;
+}
+FlErrorCode NSSetScalarImplicitRanks(NS ns, int id, double theta, double rtol)
+{
+  struct NSScalar *sc = NULL;
+  FLCHK(scalar_get(ns, id, &sc));
+  if (!(theta == 0. || (theta >= 0.5 && theta <= 1.)) || !(rtol > 0. && rtol < 1.)) return E_ARG_OUTOFRANGE;
+  sc->theta = theta; /* (any mesh: NSStep takes fl_scalar_step_imex_ranks on several ranks) */
   sc->rtol  = rtol;
   return 0;
 }

@@ -65,7 +65,7 @@ PROTOTYPES = {
     "NSAddScalar": [_P, C.c_char_p, C.c_double, C.c_char_p, _ip], "NSSetScalarBoundaryCondition": [_P, C.c_int, C.c_int, C.c_int, C.c_double],
     "NSSetScalarSource": [_P, C.c_int, _P], "NSSetScalarSubsteps": [_P, C.c_int, C.c_int], "NSGetScalarArray": [_P, C.c_int, C.POINTER(_P)],
     "NSGetScalarCFL": [_P, C.c_int, C.POINTER(C.c_double)],
-    "NSSetScalarImplicit": [_P, C.c_int, C.c_double, C.c_double], "NSGetScalarImplicitInfo": [_P, C.c_int, _ip, C.POINTER(C.c_double)],
+    "NSSetScalarImplicit": [_P, C.c_int, C.c_double, C.c_double], "NSSetScalarImplicitRanks": [_P, C.c_int, C.c_double, C.c_double], "NSGetScalarImplicitInfo": [_P, C.c_int, _ip, C.POINTER(C.c_double)],
     "NSSetScalarImmersedBoundary": [_P, C.c_int, C.c_int, C.POINTER(C.c_double)], "NSGetScalarImmersedBoundaryRate": [_P, C.c_int, C.POINTER(C.c_double)],
     "NSSetGravity": [_P, C.POINTER(C.c_double)], "NSGetGravity": [_P, C.POINTER(C.c_double)],
     "NSSetScalarBuoyancy": [_P, C.c_int, C.c_double, C.c_double], "NSGetScalarBoundaryFlux": [_P, C.c_int, C.POINTER(C.c_double)],

@@ -43,6 +43,7 @@ class Scalar:
         create, name = (lib.fl_scalar_create_ranks, "fl_scalar_create_ranks") if several else (lib.fl_scalar_create, "fl_scalar_create")
         check(create(poisson.h, (C.c_int * 6)(*self.bc), C.byref(h)), name)
         self.h = h
+        self.several = several
         poisson._children.append(weakref.ref(self))
         self._V = None
         for b, v in enumerate(values or ()):
@@ -122,7 +123,13 @@ class Scalar:
         self.P._post()
         return np.array(list(out), dtype=np.float64).reshape(6, 2)
 
-    # ---- implicit diffusion (include/fluca_hip_implicit.h); one rank only.  `info` of a call: dict(steps, capped, emin, emax, bound), host values
+    # ---- implicit diffusion (include/fluca_hip_implicit.h); on a handle of the collective constructor apply, solve and step_imex are the collective
+    # calls of include/fluca_hip_implicit_ranks.h (one plane of phi across every rank face per Chebyshev step; the gathered result has the one-rank
+    # bits).  `info` of a call: dict(steps, capped, emin, emax, bound), host values, the same on every rank
+
+    def _implicit(self, name):
+        name += "_ranks" if self.several else ""
+        return getattr(lib, name), name
 
     @staticmethod
     def _info(i):
@@ -139,7 +146,8 @@ class Scalar:
         assert phi.numel() == self.P.ncell
         out = self.P.empty() if out is None else out
         self.P._pre()
-        check(lib.fl_scalar_diffusion_apply(self.h, float(c), _ptr(phi), _ptr(out)), "fl_scalar_diffusion_apply")
+        f, name = self._implicit("fl_scalar_diffusion_apply")
+        check(f(self.h, float(c), _ptr(phi), _ptr(out)), name)
         self.P._post()
         return out
 
@@ -148,7 +156,8 @@ class Scalar:
         assert b.numel() == self.P.ncell and x.numel() == self.P.ncell
         info = capi.fl_scalar_cheb_info()
         self.P._pre()
-        check(lib.fl_scalar_diffusion_solve(self.h, float(c), float(rtol), int(maxit), _ptr(b), _ptr(x), C.byref(info)), "fl_scalar_diffusion_solve")
+        f, name = self._implicit("fl_scalar_diffusion_solve")
+        check(f(self.h, float(c), float(rtol), int(maxit), _ptr(b), _ptr(x), C.byref(info)), name)
         self.P._post()
         return self._info(info)
 
@@ -158,7 +167,7 @@ class Scalar:
         assert phi.numel() == self.P.ncell and (source is None or source.numel() == self.P.ncell)
         info = capi.fl_scalar_cheb_info()
         self.P._pre()
-        check(lib.fl_scalar_step_imex(self.h, float(dt), int(nstages), float(theta), float(rtol), int(maxit), _ptr(source), _ptr(phi), C.byref(info)),
-              "fl_scalar_step_imex")
+        f, name = self._implicit("fl_scalar_step_imex")
+        check(f(self.h, float(dt), int(nstages), float(theta), float(rtol), int(maxit), _ptr(source), _ptr(phi), C.byref(info)), name)
         self.P._post()
         return self._info(info)

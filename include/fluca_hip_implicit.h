@@ -14,7 +14,7 @@
  * looks at a norm: every call below that touches the GPU enqueues its launches on the handle's stream and returns.
  *
  * One rank only: on a handle of fl_scalar_create_ranks over a decomposed grid apply, solve and step_imex return FL_ERR_SUP (every rank holds such a
- * handle, so every rank returns it and nobody waits). */
+ * handle, so every rank returns it and nobody waits).  The collective calls for such a handle are fluca_hip_implicit_ranks.h's. */
 #ifndef FLUCA_HIP_IMPLICIT_H
 #define FLUCA_HIP_IMPLICIT_H
 

@@ -34,6 +34,7 @@
 
 #include "fluca_hip.h"
 #include "fluca_hip_implicit.h"
+#include "fluca_hip_implicit_ranks.h"
 #include "fluca_hip_ibm_scalar.h"
 
 #ifdef __cplusplus
@@ -287,8 +288,14 @@ FlErrorCode NSGetScalarCFL(NS ns, int id, double out[2]);
  *                            E_ARG_OUTOFRANGE otherwise; E_SUP with theta != 0 on a several-rank mesh.  With Gamma = 0 the step is the explicit one, bit for bit.
  *   NSGetScalarImplicitInfo  the Chebyshev steps the last substep ran and the bound B_steps they guarantee (0 and 1 before the first implicit step)
  * Options: -ns_scalar_implicit_theta <0 | 0.5..1>, -ns_scalar_implicit_rtol <r> (default 1e-6): what a scalar added AFTERWARDS starts with, as
- * -ns_scalar_limiter (on a several-rank mesh the scalars stay explicit). */
+ * -ns_scalar_limiter (on a several-rank mesh the scalars stay explicit, unless -ns_scalar_implicit_ranks says otherwise).
+ *   NSSetScalarImplicitRanks NSSetScalarImplicit with the same checks, accepted on ANY mesh: on several ranks NSStep advances the scalar by the collective
+ *                            fl_scalar_step_imex_ranks (include/fluca_hip_implicit_ranks.h) -- one plane of phi across every rank face per Chebyshev launch,
+ *                            the count known on every rank's host alike, no reduction; the IBM scalar forcing after each substep and
+ *                            NSGetScalarImplicitInfo as on one rank.  On one rank it IS NSSetScalarImplicit.  Every rank calls it with the same values.
+ * Option: -ns_scalar_implicit_ranks <0|1> (default 0): with 1, -ns_scalar_implicit_theta / _rtol also reach scalars added on a several-rank mesh. */
 FlErrorCode NSSetScalarImplicit(NS ns, int id, double theta, double rtol);
+FlErrorCode NSSetScalarImplicitRanks(NS ns, int id, double theta, double rtol);
 FlErrorCode NSGetScalarImplicitInfo(NS ns, int id, int *steps, double *bound);
 /* A SCALAR HELD AT A VALUE ON THE IMMERSED BODIES (no reference counterpart): a heated sphere or cylinder, fl_ibm_scalar_force of
  * include/fluca_hip_ibm_scalar.h.  Only the surface markers are forced, not the body's interior; a value per body, not per marker; no prescribed flux. */

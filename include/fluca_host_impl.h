@@ -130,6 +130,7 @@ struct _p_NS {
   int                  scalar_limiter;   /* -ns_scalar_limiter: the limiter of a scalar added without a name of its own (default superbee) */
   double               gravity[3];       /* NSSetGravity / -ns_gravity (default 0): with a scalar whose beta != 0 the Boussinesq term of the right-hand side */
   double               scalar_theta, scalar_rtol; /* -ns_scalar_implicit_theta (default 0: explicit), -ns_scalar_implicit_rtol (default 1e-6): of a scalar added later */
+  int                  scalar_implicit_ranks; /* -ns_scalar_implicit_ranks (default 0): 1 = the two options above also reach scalars added on a several-rank mesh */
   int                  scalar_ibm_passes;  /* -ns_scalar_ibm_passes (default 1): what NSSetScalarImmersedBoundary(npass = -1) takes */
   double              *ibm_Q;              /* device, owned by the NS: the forcing Q of the substep run last, room for ibm_Qcap markers */
   int64_t              ibm_Qcap;
@@ -142,7 +143,7 @@ struct NSScalar {
   double       *phi;      /* device, owned by the NS */
   const double *src;      /* device, borrowed; may be NULL */
   double        beta, phi_ref; /* NSSetScalarBuoyancy: rho = rho0 (1 - beta (phi - phi_ref)); beta = 0 (default): passive */
-  double        theta, rtol;   /* NSSetScalarImplicit: theta = 0 (default) explicit, else fl_scalar_step_imex(theta, rtol) */
+  double        theta, rtol;   /* NSSetScalarImplicit[Ranks]: theta = 0 (default) explicit, else fl_scalar_step_imex[_ranks](theta, rtol) */
   int           cheb_steps;    /* NSGetScalarImplicitInfo: of the last substep run */
   double        cheb_bound;
   int           ibm_npass;     /* NSSetScalarImmersedBoundary: 0 (default) off */

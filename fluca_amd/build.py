@@ -14,8 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libflucahip.so")
-SOURCES = ["fl_coeff.cpp", "fl_kernels.hip", "fl_api.hip", "fl_knobs.cpp", "fl_place.hip", "fl_halo.hip", "fl_comm.hip", "fl_ksp.hip", "fl_cheb2.hip", "fl_layout.hip", "fl_ibm.hip", "fl_ibm_owner.hip", "fl_ibm_body.hip", "fl_momentum.hip", "fl_mg.hip", "fl_schur_var.hip", "fl_scalar.hip", "fl_buoyancy.hip", "fl_scalar_implicit.hip"]
-HEADERS = ["fl_internal.h", "fl_knobs.h", "fl_handle.h", "fl_msg.h", "fl_ibm_device.h", "fl_ibm_handle.h", "fl_ibm_plan.h", "fl_device.h", "fl_stencil.h", "fl_mom_tile.h", "fl_mom_tile3.h", "fl_limiter.h", "fl_scalar_handle.h", os.path.join("..", "..", "include", "fluca_hip.h"),
+SOURCES = ["fl_coeff.cpp", "fl_kernels.hip", "fl_api.hip", "fl_knobs.cpp", "fl_place.hip", "fl_halo.hip", "fl_comm.hip", "fl_ksp.hip", "fl_cheb2.hip", "fl_layout.hip", "fl_ibm.hip", "fl_ibm_owner.hip", "fl_ibm_body.hip", "fl_momentum.hip", "fl_mom_solve.hip", "fl_abf.hip", "fl_vec.hip", "fl_mg.hip", "fl_schur_var.hip", "fl_scalar.hip", "fl_buoyancy.hip", "fl_scalar_implicit.hip"]
+HEADERS = ["fl_internal.h", "fl_knobs.h", "fl_handle.h", "fl_msg.h", "fl_ibm_device.h", "fl_ibm_handle.h", "fl_ibm_plan.h", "fl_devbuf.h", "fl_mom_handle.h", "fl_gmres_lsq.h", "fl_device.h", "fl_stencil.h", "fl_mom_tile.h", "fl_mom_tile3.h", "fl_limiter.h", "fl_scalar_handle.h", os.path.join("..", "..", "include", "fluca_hip.h"),
            os.path.join("..", "..", "include", "fluca_hip_implicit.h"), os.path.join("..", "..", "include", "fluca_hip_implicit_ranks.h"), os.path.join("..", "..", "include", "fluca_hip_ibm_scalar.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-result"]

@@ -9,7 +9,7 @@
 // Operation order per cell and component (pinned by tests/test_gpu_buoyancy.py): x_s = phi_s - ref_s; t = a_0 x_0; t = fma(a_s, x_s, t), s = 1 ..;
 // momrhs = fma(dt, t, momrhs).
 #include "fl_device.h"
-#include "fl_handle.h"
+#include "fl_mom_handle.h"
 
 namespace fl {
 
@@ -114,12 +114,6 @@ void launch_buoyancy(hipStream_t st, int nblocks, int64_t N, int ns, int act, co
 
 using namespace fl;
 
-// struct fl_momentum is private to fl_momentum.hip, and the text of that file is what the counter pass of k_mom3 quoted by bench.py is tied to
-// (fluca_amd/provenance.py, profiles/pmc_k_mom3.json).  The entry point lives here so that file keeps its text; of the handle it needs only the
-// borrowed fl_poisson, which is the struct's FIRST member (`fl_poisson *p`, no virtual functions): read through the handle's address.  To be moved
-// into fl_momentum.hip, with a plain m->p, together with the next counter pass of that file.
-static fl_poisson *momentum_grid(const fl_momentum *m) { return *reinterpret_cast<fl_poisson *const *>(m); }
-
 // momrhs += dt sum_s a_s (phi_s - ref_s): the Boussinesq term, one launch for all scalars.  No reference counterpart.  Every argument is checked
 // before the handle is read.
 extern "C" int fl_momentum_add_buoyancy(fl_momentum *m, int nscalar, const double *const phi_dev[], const double accel[], const double phi_ref[], double dt, double *momrhs_dev)
@@ -141,7 +135,7 @@ extern "C" int fl_momentum_add_buoyancy(fl_momentum *m, int nscalar, const doubl
     }
   }
   if (!act) return FL_SUCCESS;  // nothing to add: no launch
-  fl_poisson *h = momentum_grid(m);
+  fl_poisson *h = m->p;  // of the handle only the borrowed grid is needed
   FL_HIP(hipSetDevice(h->device));
   launch_buoyancy(h->stream, buoyancy_blocks(h->ncell, device_cus(h->device)), h->ncell, nscalar, act, A, dt, momrhs_dev);
   FL_HIP(hipGetLastError());

@@ -1,9 +1,8 @@
-// fl_ibm_handle.h -- the fl_ibm handle, the one type that owns its device memory, and the host functions that cross between fl_ibm.hip (the marker
+// fl_ibm_handle.h -- the fl_ibm handle (its device memory: DevBuf, fl_devbuf.h) and the host functions that cross between fl_ibm.hip (the marker
 // set), fl_ibm_owner.hip (owner-rank markers, migration) and fl_ibm_body.hip (per-body sums, the scalar on the markers).  Every __global__ function
 // lives in exactly one of the three; a unit that needs another's kernel calls one of the launchers declared below.
 #pragma once
-#include <utility>
-
+#include "fl_devbuf.h"
 #include "fl_handle.h"
 #include "fl_ibm_device.h"
 #include "fl_ibm_plan.h"
@@ -11,48 +10,6 @@
 #pragma GCC visibility push(hidden)  // internal to the library: its dynamic symbols stay the C-ABI's
 
 namespace fl {
-
-// A device array of T that frees itself.  Three ways to get memory, each with its own rule for what is there already; none keeps old contents.
-// A release in mid-life waits for the handle's stream first (work that reads the array may be pending); the destructor does not wait:
-// fl_ibm_destroy synchronises once before it deletes the handle.
-template <class T>
-struct DevBuf {
-  T      *p   = nullptr;
-  int64_t cap = 0;  // elements behind p
-
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  operator T *() const { return p; }
-  void swap(DevBuf &o) { std::swap(p, o.p), std::swap(cap, o.cap); }
-  void release(fl_poisson *h)
-  {
-    if (p) {
-      (void)hipStreamSynchronize(h->stream);
-      (void)hipFree(p);
-    }
-    p   = nullptr;
-    cap = 0;
-  }
-  // at least `need` elements: grown by a quarter beyond the need, never shrunk, zeroed
-  int reserve(fl_poisson *h, int64_t need)
-  {
-    if (p && need <= cap) return 0;
-    need = std::max<int64_t>(need + need / 4, 64);
-    return exact(h, need, true) ? FL_ERR_MEM : 0;
-  }
-  // exactly n elements, afresh
-  int exact(fl_poisson *h, int64_t n, bool zero)
-  {
-    release(h);
-    const int rc = fl_dev_alloc(h, (void **)&p, sizeof(T) * (size_t)n, zero);
-    if (!rc) cap = n;
-    return rc;
-  }
-  // n elements the first time, the same ones ever after
-  int once(fl_poisson *h, int64_t n, bool zero) { return p ? 0 : exact(h, n, zero); }
-};
 
 struct RouteP {
   int peer_lo[3], peer_hi[3];  // ibm_plan_peers'

@@ -497,8 +497,8 @@ bool sc_ring_side(const fl_poisson *h, int b) { return h->multi && h->nbr[b] >= 
 ScRing ring_args(const fl_scalar *m, bool pack)
 {
   ScRing rg;
-  rg.recv = m->slab_recv;
-  rg.send = m->slab_send;
+  rg.recv = m->slab_recv.p;
+  rg.send = m->slab_send.p;
   rg.pack = pack ? m->nb : 0;
   for (int d = 0; d < 3; ++d) rg.vhi[d] = (m->nb >> (2 * d + 1)) & 1 ? m->h->hiface[d] : nullptr;
   return rg;
@@ -549,16 +549,16 @@ int scalar_init(fl_scalar *m, fl_poisson *h, const int bc[6])
     FL_CHK(build_axis_scalar(A, rows));
     std::vector<double> hw((size_t)A.n);
     for (int64_t i = 0; i < A.n; ++i) hw[(size_t)i] = A.xf[(size_t)i + 1] - A.xf[(size_t)i];
-    FL_HIP(hipMalloc(&m->tab[d], sizeof(ScCell) * rows.size()));
-    FL_HIP(hipMalloc((void **)&m->hw[d], sizeof(double) * hw.size()));
-    FL_HIP(hipMemcpy(m->tab[d], rows.data(), sizeof(ScCell) * rows.size(), hipMemcpyHostToDevice));
-    FL_HIP(hipMemcpy(m->hw[d], hw.data(), sizeof(double) * hw.size(), hipMemcpyHostToDevice));
+    FL_CHK(m->tab[d].plain(h, (int64_t)rows.size()));
+    FL_CHK(m->hw[d].plain(h, (int64_t)hw.size()));
+    FL_HIP(hipMemcpy(m->tab[d].p, rows.data(), sizeof(ScCell) * rows.size(), hipMemcpyHostToDevice));
+    FL_HIP(hipMemcpy(m->hw[d].p, hw.data(), sizeof(double) * hw.size(), hipMemcpyHostToDevice));
     // h->ax[d] is the GLOBAL axis: the rank's rows are the one-rank rows of its cells, bit for bit (one rank: lo = 0)
     const int64_t lo = h->multi ? h->dec.lo[d] : 0;
-    g.c[d]    = (const ScCell *)m->tab[d] + lo;
-    m->hwl[d] = m->hw[d] + lo;
+    g.c[d]    = m->tab[d].p + lo;
+    m->hwl[d] = m->hw[d].p + lo;
   }
-  FL_HIP(hipMalloc((void **)&m->partial, sizeof(double) * 3 * SC_REDUCE_BLOCKS));
+  FL_CHK(m->partial.plain(h, 3 * SC_REDUCE_BLOCKS));
   m->partial_host.resize((size_t)3 * SC_REDUCE_BLOCKS);
   return FL_SUCCESS;
 }
@@ -582,15 +582,7 @@ extern "C" int fl_scalar_destroy(fl_scalar *m)
     (void)hipSetDevice(m->h->device);
     if (m->h->stream) (void)hipStreamSynchronize(m->h->stream);
   }
-  for (int d = 0; d < 3; ++d) {
-    if (m->tab[d]) (void)hipFree(m->tab[d]);
-    if (m->hw[d]) (void)hipFree(m->hw[d]);
-  }
-  for (double *p : {m->work[0], m->work[1], m->partial, m->imex_b})
-    if (p) (void)hipFree(p);
-  for (double *p : {m->slab_recv, m->slab_send})
-    if (p) (void)hipFree(p);
-  delete m;
+  delete m;  // the DevBufs free what they hold
   return FL_SUCCESS;
 }
 
@@ -612,8 +604,8 @@ int scalar_new(fl_poisson *h, const int bc[6], bool ring, fl_scalar **out)
   int        rc = scalar_init(m, h, bc);
   if (!rc && ring) {
     for (int b = 0; b < 6; ++b) m->nb |= sc_ring_side(h, b) ? 1 << b : 0;
-    const size_t bytes = sizeof(double) * slab_offset(h, 6);
-    if (hipMalloc((void **)&m->slab_recv, bytes) != hipSuccess || hipMalloc((void **)&m->slab_send, bytes) != hipSuccess) rc = FL_ERR_GPU;
+    const int64_t n = (int64_t)slab_offset(h, 6);
+    if (m->slab_recv.plain(h, n) || m->slab_send.plain(h, n)) rc = FL_ERR_GPU;
   }
   m->ring = ring;
   if (rc) {
@@ -652,7 +644,7 @@ int ring_pack(fl_scalar *m, const double *phi, int nl)
   size_t most = 0;
   for (int b = 0; b < 6; ++b)
     if ((m->nb >> b) & 1) most = std::max(most, nl * (size_t)fl_plane_size(m->h, b / 2));
-  if (most) hipLaunchKernelGGL(k_scalar_pack, dim3((unsigned)std::min<size_t>((most + 255) / 256, 1024), 6), dim3(256), 0, m->h->stream, m->g.nx, m->g.ny, m->g.nz, m->nb, nl, phi, m->slab_send);
+  if (most) hipLaunchKernelGGL(k_scalar_pack, dim3((unsigned)std::min<size_t>((most + 255) / 256, 1024), 6), dim3(256), 0, m->h->stream, m->g.nx, m->g.ny, m->g.nz, m->nb, nl, phi, m->slab_send.p);
   FL_HIP(hipGetLastError());
   return FL_SUCCESS;
 }
@@ -798,7 +790,7 @@ int fl::scalar_ssp_step(fl_scalar *m, double dt, int nstages, const double *sour
 {
   FL_HIP(hipSetDevice(m->h->device));
   for (int a = 0; a < (nstages > 2 ? 2 : 1); ++a)
-    if (!m->work[a]) FL_HIP(hipMalloc((void **)&m->work[a], sizeof(double) * (size_t)m->h->ncell));
+    if (!m->work[a]) FL_CHK(m->work[a].plain(m->h, m->h->ncell));
   const int     s = nstages;
   const double *w = phi_dev;
   // several ranks: V is frozen during the step (one exchange of its high faces); phi's slabs are packed by a kernel once, then by the stages
@@ -836,10 +828,10 @@ extern "C" int fl_scalar_cfl(fl_scalar *m, double dt, double out[2])
     ScHiface vh;
     for (int d = 0; d < 3; ++d) vh.v[d] = (m->nb >> (2 * d + 1)) & 1 ? m->h->hiface[d] : nullptr;
     hipLaunchKernelGGL(k_scalar_cfl_ring, dim3(nb), dim3(256), 0, m->h->stream, m->g.nx, m->g.ny, m->g.nz, m->g.per, m->nb, vh, dt, m->g.gamma, m->hwl[0], m->hwl[1], m->hwl[2], m->V[0],
-                       m->V[1], m->V[2], m->partial);
+                       m->V[1], m->V[2], m->partial.p);
   } else
     hipLaunchKernelGGL(k_scalar_cfl, dim3(nb), dim3(256), 0, m->h->stream, m->g.nx, m->g.ny, m->g.nz, m->g.per, dt, m->g.gamma, m->hwl[0], m->hwl[1], m->hwl[2], m->V[0], m->V[1], m->V[2],
-                       m->partial);
+                       m->partial.p);
   FL_CHK(fetch_partials(m, nb));
   out[0] = out[1] = 0.;
   for (int b = 0; b < nb; ++b) {
@@ -858,7 +850,7 @@ extern "C" int fl_scalar_stats(fl_scalar *m, const double *phi_dev, double out[3
   if (!m || !phi_dev || !out) return FL_ERR_ARG_NULL;
   FL_HIP(hipSetDevice(m->h->device));
   const int nb = reduce_blocks(m);
-  hipLaunchKernelGGL(k_scalar_stats, dim3(nb), dim3(256), 0, m->h->stream, m->g.nx, m->g.ny, m->g.nz, m->hwl[0], m->hwl[1], m->hwl[2], phi_dev, m->partial);
+  hipLaunchKernelGGL(k_scalar_stats, dim3(nb), dim3(256), 0, m->h->stream, m->g.nx, m->g.ny, m->g.nz, m->hwl[0], m->hwl[1], m->hwl[2], phi_dev, m->partial.p);
   FL_CHK(fetch_partials(m, nb));
   out[0] = m->partial_host[0];
   out[1] = m->partial_host[1];
@@ -901,7 +893,7 @@ extern "C" int fl_scalar_boundary_flux(fl_scalar *m, const double *phi_dev, doub
   if (nblk) {
     const bool hx = (m->nb >> 1) & 1, hy = (m->nb >> 3) & 1;
     const int  fx = ((g.per & 1) || hx) ? g.nx : g.nx + 1, fy = ((g.per & 2) || hy) ? g.ny : g.ny + 1;
-    hipLaunchKernelGGL(k_scalar_flux, dim3(nblk), dim3(256), 0, m->h->stream, g, pl, fx, fy, m->hwl[0], m->hwl[1], m->hwl[2], phi_dev, m->V[0], m->V[1], m->V[2], m->partial);
+    hipLaunchKernelGGL(k_scalar_flux, dim3(nblk), dim3(256), 0, m->h->stream, g, pl, fx, fy, m->hwl[0], m->hwl[1], m->hwl[2], phi_dev, m->V[0], m->V[1], m->V[2], m->partial.p);
     FL_CHK(fetch_partials(m, nblk));
     for (int b = 0; b < 6; ++b)
       for (int k = pl.first[b]; k < pl.first[b + 1]; ++k) {

@@ -1,6 +1,7 @@
 // fl_scalar_handle.h -- the fl_scalar handle and what the kernels of fl_scalar.hip and fl_scalar_implicit.hip share: the grid as a kernel sees it and
 // the read of a cell of the caller's unpadded array.
 #pragma once
+#include "fl_devbuf.h"
 #include "fl_handle.h"
 #include "fl_limiter.h"
 
@@ -47,27 +48,32 @@ __device__ __forceinline__ double sc_ld_ring(const double *__restrict__ w, int64
 
 }  // namespace fl
 
+#pragma GCC visibility push(hidden)  // the handle is internal to the library (what its kernels take, above, is not)
+
 struct fl_scalar {
   fl_poisson   *h = nullptr;  // borrowed: grid, device, stream
   fl::ScGrid    g;
   int           limiter = fl::LIM_SUPERBEE;
   const double *V[3] = {nullptr, nullptr, nullptr};  // borrowed
-  void         *tab[3] = {nullptr, nullptr, nullptr};
-  double       *hw[3] = {nullptr, nullptr, nullptr};  // face-to-face widths
-  double       *work[2] = {nullptr, nullptr};         // the two stage vectors of fl_scalar_step
-  double       *partial = nullptr;                    // 3 * SC_REDUCE_BLOCKS
+  // device arrays the handle owns (DevBuf: freed with the handle)
+  fl::DevBuf<fl::ScCell> tab[3];
+  fl::DevBuf<double>     hw[3];    // face-to-face widths
+  fl::DevBuf<double>     work[2];  // the two stage vectors of fl_scalar_step
+  fl::DevBuf<double>     partial;  // 3 * SC_REDUCE_BLOCKS
   std::vector<double> partial_host;
   const double *hwl[3] = {nullptr, nullptr, nullptr};  // hw cut to the rank's cells
   // one rank's block of several (fl_scalar_create_ranks): nb as k_scalar_stage_ring takes it; the layers received and sent (ScRing)
   bool    ring = false;
   int     nb = 0;
-  double *slab_recv = nullptr, *slab_send = nullptr;
+  fl::DevBuf<double> slab_recv, slab_send;
   // the implicit path (fl_scalar_implicit.hip), made on first use: the right-hand side of fl_scalar_step_imex (its second array beside work[]: the
   // Chebyshev direction and the other iterate live in work[0], work[1], which the explicit stages have left by then); max_i omega_d(i) per axis
-  double *imex_b = nullptr;
+  fl::DevBuf<double> imex_b;
   bool    have_omega = false;
   double  omega[3] = {0., 0., 0.};
 };
+
+#pragma GCC visibility pop
 
 namespace fl {
 

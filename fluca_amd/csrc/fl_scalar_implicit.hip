@@ -251,7 +251,7 @@ void launch_cheb(const fl_scalar *m, double c, double p, double q, const double 
 {
   const dim3 grid(8 * cheb_plan(m->g.nx, m->g.ny, m->g.nz).per_xcd);
   if (m->ring) {
-    const HcRing rg = {m->slab_recv, m->slab_send, m->nb, (pack && MODE < 2) ? m->nb : 0};
+    const HcRing rg = {m->slab_recv.p, m->slab_send.p, m->nb, (pack && MODE < 2) ? m->nb : 0};
     hipLaunchKernelGGL((k_scalar_cheb_ring<MODE>), grid, dim3(256), 0, m->h->stream, m->g, rg, c, p, q, x, b, d, xo);
     return;
   }
@@ -261,8 +261,8 @@ void launch_cheb(const fl_scalar *m, double c, double p, double q, const double 
 int implicit_arrays(fl_scalar *m, bool with_b)
 {
   for (int a = 0; a < 2; ++a)
-    if (!m->work[a]) FL_HIP(hipMalloc((void **)&m->work[a], sizeof(double) * (size_t)m->h->ncell));
-  if (with_b && !m->imex_b) FL_HIP(hipMalloc((void **)&m->imex_b, sizeof(double) * (size_t)m->h->ncell));
+    if (!m->work[a]) FL_CHK(m->work[a].plain(m->h, m->h->ncell));
+  if (with_b && !m->imex_b) FL_CHK(m->imex_b.plain(m->h, m->h->ncell));
   return FL_SUCCESS;
 }
 
@@ -429,12 +429,12 @@ int step_imex(fl_scalar *m, double dt, int nstages, double theta, double rtol, i
   // well, so the first Chebyshev step's exchange follows it with no pack launch in between.
   const bool to_b = !cn && I.steps > 0;
   m->g.gamma = 0.;
-  const int rc = scalar_ssp_step(m, dt, nstages, source_dev, phi_dev, to_b ? m->imex_b : phi_dev, to_b);
+  const int rc = scalar_ssp_step(m, dt, nstages, source_dev, phi_dev, to_b ? m->imex_b.p : phi_dev, to_b);
   m->g.gamma = gamma;
   FL_CHK(rc);
   if (to_b) return cheb_launches(m, c, I, m->imex_b, m->imex_b, phi_dev);
   if (!cn) return FL_SUCCESS;  // (no step to run: x = b = the guess = phi*)
-  hipLaunchKernelGGL(k_scalar_addto, dim3((unsigned)std::min<size_t>((ncell + 255) / 256, 8192)), dim3(256), 0, m->h->stream, (int64_t)ncell, phi_dev, m->imex_b);
+  hipLaunchKernelGGL(k_scalar_addto, dim3((unsigned)std::min<size_t>((ncell + 255) / 256, 8192)), dim3(256), 0, m->h->stream, (int64_t)ncell, phi_dev, m->imex_b.p);
   if (S == 0.) FL_HIP(hipMemcpyAsync(phi_dev, m->imex_b, sizeof(double) * ncell, hipMemcpyDeviceToDevice, m->h->stream));
   if (m->ring && I.steps > 0) FL_CHK(scalar_ring_pack1(m, phi_dev));  // the guess phi*
   return cheb_launches(m, c, I, m->imex_b, phi_dev, phi_dev);

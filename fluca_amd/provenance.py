@@ -12,8 +12,8 @@ KERNEL_SOURCES = {
     "k_cg_A": [_C + "fl_kernels.hip", _C + "fl_stencil.h", _C + "fl_device.h"],
     "k_cg_Bq": [_C + "fl_kernels.hip", _C + "fl_stencil.h", _C + "fl_device.h"],
     "k_cheb2": [_C + "fl_cheb2.hip", _C + "fl_stencil.h", _C + "fl_device.h"],
-    "k_mom3": [_C + "fl_mom_tile3.h", _C + "fl_momentum.hip", _C + "fl_device.h"],
-    "k_mom2": [_C + "fl_mom_tile.h", _C + "fl_momentum.hip", _C + "fl_device.h"],
+    "k_mom3": [_C + "fl_mom_tile3.h", _C + "fl_mom_tile.h", _C + "fl_momentum.hip", _C + "fl_mom_handle.h", _C + "fl_stencil.h", _C + "fl_device.h"],
+    "k_mom2": [_C + "fl_mom_tile.h", _C + "fl_momentum.hip", _C + "fl_mom_handle.h", _C + "fl_stencil.h", _C + "fl_device.h"],
 }
 
 

@@ -409,7 +409,7 @@ def _part_CF():
     return out
 
 
-# D: fl_momentum.hip promises that KSPCHEBYSHEV on the default interval with -ksp_norm_type none is never left unwatched.  The operator is
+# D: fl_mom_solve.hip promises that KSPCHEBYSHEV on the default interval with -ksp_norm_type none is never left unwatched.  The operator is
 # A = I + weight dt C - (mu dt / 2 rho) L (Momentum.set_coefficients): at the weights below the diagonal of A changes sign, the spectrum of D^-1 A
 # leaves the heuristic interval and the oracle's Chebyshev on that interval (preconditioned norm, no convergence test, dtol 1e5) crosses dtol at
 # step K; at weight 1 the same recurrence converges, and 20 steps end with CONVERGED_ITS.

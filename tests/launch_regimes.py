@@ -7,7 +7,8 @@ grid stride that wraps), with the fields of the plans it must get; the multigrid
 (mg_plans).  tests/test_launch_regimes.py checks the table against the library on the CPU; tests/test_gpu_launch_regimes.py,
 tests/test_gpu_momentum_regimes.py and tests/test_gpu_mg_regimes.py check every kernel on these grids against the oracle.  RANK_REGIMES names
 rank grids whose blocks take the same 8-wave plans (and k_schur_var_ring's 128 blocks per XCD); tests/test_gpu_rank_regimes.py runs the several-rank
-kernels on them."""
+kernels on them.  ranks_std_z3 is the one among them with an interior block: three ranks along z, so the middle block keeps q on its first and
+its last plane for two different peers (tests/interior_ranks.py has the toy grids with interior ranks)."""
 import ctypes as C
 
 from oracle import fluca_oracle as fo
@@ -305,12 +306,7 @@ class RankRegime:
         """the fl_decomp of a rank: the default split, or the ownership ranges"""
         from fluca_amd import capi
         from tests import mp_common as mpc
-        d = mpc.decomp_of(capi, self.n, self.ranks, rank)
-        if self.own is not None:
-            for a in range(3):
-                d.len[a] = self.own[a][d.coord[a]]
-                d.lo[a] = sum(self.own[a][:d.coord[a]])
-        return d
+        return mpc.decomp_of(capi, self.n, self.ranks, rank, self.own)
 
     def periodic(self, bc):
         return [bc[2 * a] == PER for a in range(3)]
@@ -327,6 +323,9 @@ RANK_REGIMES = [
     RankRegime("ranks_std_z", (300, 680, 42), (1, 1, 2), None, [CAVITY, CHANNEL], [(300, 680, 21)] * 2, _RSTD,
                "the 2-GPU layout of the bench: the exchanged face is a whole 300 x 680 plane; the stored q planes are plane 0 (first of chunk 0) and "
                "plane 20 (last of the short chunk of 10); CHANNEL: z periodic across the two ranks (the same peer on both sides)"),
+    RankRegime("ranks_std_z3", (300, 680, 63), (1, 1, 3), None, [CAVITY, CHANNEL], [(300, 680, 21)] * 3, _RSTD,
+               "an interior block in the standard plan: the middle rank has a different peer below and above, its stored q planes 0 and 20 go to two "
+               "ranks, it has no wall row in z; CHANNEL: z periodic over three ranks, the seam joins rank 2 to rank 0"),
     RankRegime("ranks_std_xy", (601, 1359, 21), (2, 2, 1), None, [XPER, CAVITY], [(301, 680, 21), (300, 680, 21), (301, 679, 21), (300, 679, 21)], _RSTD,
                "2 x 2 ranks: the edge cells of the deep exchange travel in two hops; blocks with odd nx (301: the last cell alone in its lane's pair) "
                "and odd ny (679: the last row alone in its wave's pair); XPER: x periodic across ranks, z wraps inside the block"),
@@ -360,4 +359,7 @@ RANK_BY_NAME = {r.name: r for r in RANK_REGIMES}
 TOY_RANK_BLOCKS = [(24, 20, 8), (12, 20, 16), (24, 10, 16), (70, 18, 12), (68, 20, 12), (70, 6, 10), (20, 18, 12), (16, 16, 16), (24, 16, 16),
                    (12, 20, 8), (16, 16, 8), (8, 16, 8),                                                             # test_gpu_multirank
                    (32, 24, 16), (21, 19, 15), (20, 18, 14), (24, 20, 16), (20, 16, 12), (64, 32, 16), (64, 32, 15),   # test_gpu_config5
-                   (5, 9, 8), (8, 9, 8), (9, 6, 4), (9, 7, 7), (5, 6, 3), (7, 5, 7), (7, 6, 7), (12, 16, 12)]          # test_gpu_schur_var_multirank
+                   (5, 9, 8), (8, 9, 8), (9, 6, 4), (9, 7, 7), (5, 6, 3), (7, 5, 7), (7, 6, 7), (12, 16, 12),          # test_gpu_schur_var_multirank
+                   (4, 9, 8), (9, 6, 7), (9, 3, 7), (10, 9, 4), (10, 9, 6), (10, 9, 5),                                # ... its three-rank cases
+                   (10, 12, 8), (12, 8, 9), (12, 7, 9), (7, 10, 8), (16, 12, 6), (16, 12, 4), (16, 12, 5), (9, 8, 8),
+                   (32, 32, 32), (32, 32, 31)]                                                                         # test_gpu_interior_ranks

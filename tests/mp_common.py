@@ -91,10 +91,16 @@ def allreduce_calls():
     return _ALLREDUCE_CALLS[0]
 
 
-def decomp_of(capi, n, ranks, rank):
+def decomp_of(capi, n, ranks, rank, own=None):
+    """the fl_decomp of a rank: DMStag's default split, or with own = (ranges of x, of y, of z) the caller's ownership ranges
+    (MeshCartSetOwnershipRanges) on the same rank grid (x fastest)"""
     d = capi.fl_decomp()
     rc = capi.lib.fl_decomp_default((C.c_int64 * 3)(*n), (C.c_int * 3)(*ranks), rank, C.byref(d))
     assert rc == 0
+    if own is not None:
+        for a in range(3):
+            d.len[a] = own[a][d.coord[a]]
+            d.lo[a] = sum(own[a][:d.coord[a]])
     return d
 
 

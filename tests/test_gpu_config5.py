@@ -425,13 +425,13 @@ def test_two_threads_drive_two_handles_without_colliding():
 CH_BOX = (2.0, 1.5, 1.0)      # Lx, Ly, Lz of the channel below (uniform spacing 1/16: the direct-forcing IBM of the mirror wants it)
 
 
-def _mirror_run(R, n, ranks, nsteps, ibm):
+def _mirror_run(R, n, ranks, nsteps, ibm, box=CH_BOX, markers=None):
     """NSSolve of the C host mirror on config 5's set-up (parabolic VELOCITY inlet, PRESSURE_OUTLET with a pressure that varies in space and
     time, no-slip walls in y, periodic span; optionally the cylinder of markers held at rest by direct forcing): this rank's blocks of v, V, p.
-    R = None: the undecomposed run."""
+    R = None: the undecomposed run.  box: Lx, Ly, Lz; markers: [x, y, z] of a body of its own instead of the cylinder."""
     from fluca_amd import capi, hostapi as H
     P = C.c_void_p
-    Lx, Ly, Lz = CH_BOX
+    Lx, Ly, Lz = box
     rank, size = (0, 1) if R is None else (R.rank, R.size)
     rk = ranks if size > 1 else (1, 1, 1)
     mesh = P()
@@ -473,7 +473,7 @@ def _mirror_run(R, n, ranks, nsteps, ibm):
     keep = []
     if ibm:
         h = Lx / n[0]
-        X = _cylinder([(0.0, Lx), (0.0, Ly), (0.0, Lz)], h, radius_cells=3.0)
+        X = _cylinder([(0.0, Lx), (0.0, Ly), (0.0, Lz)], h, radius_cells=3.0) if markers is None else [np.ascontiguousarray(a) for a in markers]
         L = X[0].size
         arrs = X + [np.full(L, h ** 3)]
         for a in arrs:
@@ -507,11 +507,11 @@ def _mirror_run(R, n, ranks, nsteps, ibm):
     return res
 
 
-def _gather(parts, n):
+def _gather(parts, n, box=CH_BOX):
     """blocks of the ranks -> global v (3 ncell), V[d] on the global face arrays, p (tests/step_rhs.py: the face counts come from the boundary types)"""
     from oracle import fluca_oracle as fo
     from tests.step_rhs import gather
-    Lx, Ly, Lz = CH_BOX
+    Lx, Ly, Lz = box
     return gather(parts, fo.Grid.uniform(n, [(0, Lx), (0, Ly), (0, Lz)], C5_BC, 1.0))
 
 

@@ -71,7 +71,7 @@ def _decomps(case):
     from fluca_amd import capi
     from tests import mp_common as mpc
     size = case.ranks[0] * case.ranks[1] * case.ranks[2]
-    return [mpc.decomp_of(capi, case.n, case.ranks, r) for r in range(size)]
+    return [mpc.decomp_of(capi, case.n, case.ranks, r, getattr(case, "own", None)) for r in range(size)]
 
 
 def _index(case, a, x):

@@ -63,6 +63,8 @@ class Problem:
 PROBLEMS = {
     "std_z-cavity": ("ranks_std_z", CAVITY, False),
     "std_z-channel": ("ranks_std_z", CHANNEL, False),
+    "ranks_std_z3-cavity": ("ranks_std_z3", CAVITY, False),
+    "ranks_std_z3-channel": ("ranks_std_z3", CHANNEL, False),
     "std_xy-xper": ("ranks_std_xy", XPER, False),
     "std_xy-cavity": ("ranks_std_xy", CAVITY, False),
     # on a uniform grid a rank that reads the coefficient rows of the wrong column / row / plane (an offset by its lo) reads the same numbers
@@ -73,6 +75,9 @@ PROBLEMS = {
 PIECES = {
     "std_z-cavity": ["operator", "cg", "cg_none", "cg_converged", "cg_sr"],
     "std_z-channel": ["operator", "cg", "cg_converged", "cg_sr", "cheb"],
+    # three ranks along z: the middle block keeps q on plane 0 and plane 20 for two different peers; CHANNEL: the seam joins rank 2 to rank 0
+    "ranks_std_z3-cavity": ["operator", "cg", "cg_sr"],
+    "ranks_std_z3-channel": ["operator", "cg", "cg_sr", "cheb"],
     "std_xy-xper": ["operator", "cg", "cg_converged", "cg_sr", "cheb"],
     "std_xy-cavity": ["operator", "cg", "cg_converged", "cg_sr"],
     "std_xy-xper-stretched": ["operator", "cg_head", "cheb7"],

@@ -107,6 +107,8 @@ def test_rank_table_covers_every_edge_of_the_several_rank_path():
         "periodic axis over two ranks": [r.name for r in w8 for bc in r.bcs for a in range(3) if r.periodic(bc)[a] and r.ranks[a] == 2],
         "periodic axis inside the block next to a split axis": [r.name for r in w8 for bc in r.bcs for a in range(3)
                                                                 if r.periodic(bc)[a] and r.ranks[a] == 1 and max(r.ranks) > 1],
+        # three ranks on an axis: the middle block has two different peers (and, on a non-periodic axis, no wall row)
+        "an interior block": [r.name for r in w8 if max(r.ranks) >= 3],
         # 2 x 2 ranks: the edge cells of fl_fill_ghosts_deep travel in two hops
         "2 x 2 rank grid": [r.name for r in w8 if sorted(r.ranks) == [1, 2, 2]],
         # ragged block edges: odd nx / ny (the last cell / row alone in its pair), partial last tiles, a short last z chunk
